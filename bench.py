@@ -13,11 +13,21 @@ exact-f32 mode -- inside HALF the north star's 1e-3 (`tolerance`); the bf16 figu
 names and the plain-fp16 figure are side fields (`bf16_operands`, `f16_operands`), each with its own
 measured errors and roofline fraction.
 
-Extra objects:
+A plain run sets up, warms up, times EXACTLY K steps (`ms_per_step` = elapsed / K, `value` = frames / elapsed)
+and prints the line.  Everything else is measured only under `--full` (without it, `tolerance` states the
+static table of tests/):
   roofline     dominant kernel family of the forward (by summed device time), timed live with HIP
-               events on the launch stream (soccdpt_profile_*): achieved = algorithmic FLOPs / time.
+               events on the launch stream (soccdpt_profile_*): achieved = algorithmic FLOPs / time;
+               also roofline_hbm, kernels, device_ms_per_step, ms_per_step_with_events.
+  repeats      further regions of the same K steps (at least ~50 steps in all): min / median beside `value`.
+  side legs    latency_b1, {mixed,f16,bf16}_operands with the live errors against the exact-f32 mode,
+               other_weights, pipelined (--in-flight).
   cpu_baseline the CPU oracle (oracle/soccdpt_ref.py, fp32 PyTorch-CPU restatement, kind "port")
                timed on this host's cores on a bounded sample (rank 0, N = 1 only).
+
+`--dump-outputs DIR` writes what the last timed step returned (inverse depth, segmentation, points, occupancy;
+--train-step: the last patch's inverse depth, segmentation and loss) as DIR/<name>.npy; the inputs and weights are
+seeded, so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -36,6 +46,27 @@ PEAK_HBM_GBS = 8000.0       # HBM3E spec (same table)
 
 
 FWD_GFLOP_PER_FRAME = {"dpt_swin2_tiny_256": 78.82, "dpt_swin2_base_384": 259.6, "dpt_hybrid_384": 293.0}   # SURVEY.md 8d (algorithmic, forward)
+DUMP_BUDGET_BYTES = 64_000_000   # --dump-outputs: all files together
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: each tensor of `arrays` (name -> tensor) as <path>/<name>.npy, float32 (float64 stays float64).  A tensor with more
+    elements than its equal share of DUMP_BUDGET_BYTES is written as a fixed sample: the flat elements at sorted indices drawn without
+    replacement by a generator seeded with the name, so the same shape gives the same indices in every run and every build."""
+    import zlib
+    import numpy as np
+    import torch
+    os.makedirs(path, exist_ok=True)
+    arrays = {k: v for k, v in arrays.items() if v is not None}
+    share = (DUMP_BUDGET_BYTES - 256 * len(arrays)) // max(1, len(arrays))   # 256: room for each .npy header
+    for name, t in arrays.items():
+        t = t.detach()
+        t = t.to(torch.float64 if t.dtype == torch.float64 else torch.float32).reshape(-1)
+        cap = share // t.element_size()
+        if t.numel() > cap:
+            idx = np.sort(np.random.default_rng(zlib.crc32(name.encode())).choice(t.numel(), cap, replace=False))
+            t = t[torch.from_numpy(idx).to(t.device)]
+        np.save(os.path.join(path, name + ".npy"), t.cpu().numpy())
 
 
 def train_step_bench(args):
@@ -74,6 +105,8 @@ def train_step_bench(args):
     mask_disp, mask_seg = mask_disp.to(dev, torch.bool), mask_seg.to(dev, torch.bool)
     opt = Adam(net.parameters(), lr=1e-5)
 
+    last = {}
+
     def one_batch():
         n = 0
         for net_patch in PatchWiseInplace(net, args.patchwise_percentage):
@@ -82,12 +115,13 @@ def train_step_bench(args):
             opt.zero_grad(set_to_none=True)
             net_patch.backward(out["d_inv"], out["d_seg"])
             opt.step()
+            last.update(inv_depth=inv, segmentation=seg, loss=out["loss"])
             n += 1
         return n
 
     from soccdpt_amd.lib import load_library
-    steps = max(1, min(args.steps, 50))
-    for _ in range(max(1, min(args.warmup, 5))):
+    steps = args.steps
+    for _ in range(args.warmup):
         one_batch()
     torch.cuda.synchronize()
     l0 = int(load_library().soccdpt_launch_counter())
@@ -99,11 +133,19 @@ def train_step_bench(args):
     dt = time.perf_counter() - t0
     launches = (int(load_library().soccdpt_launch_counter()) - l0) / n   # kernels of libsoccdpt_hip.so per step (forward + criterion + backward + Adam)
     sps = B * n / dt
-    ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
-    ev[0].record(); inv, seg = net.train_forward(x, seed=0); ev[1].record()
-    out = training_loss(inv, seg, y_disp, mask_disp, y_seg, mask_seg, 0.5, 0.5, compute_scale_and_shift=True); ev[2].record()
-    net.backward(out["d_inv"], out["d_seg"]); ev[3].record()
-    torch.cuda.synchronize()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, last)
+    loss = float(last["loss"])
+    split_ms = None
+    if args.full:
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
+        ev[0].record(); inv, seg = net.train_forward(x, seed=0); ev[1].record()
+        out = training_loss(inv, seg, y_disp, mask_disp, y_seg, mask_seg, 0.5, 0.5, compute_scale_and_shift=True); ev[2].record()
+        net.backward(out["d_inv"], out["d_seg"]); ev[3].record()
+        torch.cuda.synchronize()
+        split_ms = {"train_forward": round(ev[0].elapsed_time(ev[1]), 2), "criterion": round(ev[1].elapsed_time(ev[2]), 2),
+                    "backward_all_unfrozen": round(ev[2].elapsed_time(ev[3]), 2)}
+        loss = float(out["loss"])
     all_trainable = args.encoder_percentage >= 1.0 and args.patchwise_percentage >= 1.0
     roof = None
     if all_trainable:
@@ -127,7 +169,7 @@ def train_step_bench(args):
                 "kernel": "whole step; only the train-mode forward's FLOPs are counted (the backward's share depends on the frozen set of each patch)",
                 "flops_per_sample_gflop": round(FWD_GFLOP_PER_FRAME[args.model_type], 1)}
     cpu = None
-    if not args.no_cpu_baseline and not args.headline_only:
+    if args.full and not args.no_cpu_baseline and not args.headline_only:
         from oracle import soccdpt_ref as R
         sd_o = {k: (v.clone().requires_grad_(True) if v.is_floating_point() and "running_" not in k else v.clone()) for k, v in sd.items()}
         torch.set_num_threads(min(16, os.cpu_count() or 1))
@@ -138,16 +180,15 @@ def train_step_bench(args):
         cpu = {"value": round(xc.shape[0] / (time.perf_counter() - t0), 3), "unit": "samples/s", "cores": torch.get_num_threads(), "kind": "port",
                "sample": f"oracle forward + torch autograd backward on {xc.shape[0]} samples (no criterion / optimizer)"}
     result = {"metric": f"samples/sec SOccDPT_V3 {args.model_type.replace('dpt_', '')} training step (train forward + criterion + backward + Adam)",
-              "value": round(sps, 2), "unit": "samples/s", "n_gpus": 1, "steps": n, "warmup": max(1, min(args.warmup, 5)), "ms_per_step": round(1e3 * dt / n, 3),
+              "value": round(sps, 2), "unit": "samples/s", "n_gpus": 1, "steps": n, "warmup": args.warmup, "ms_per_step": round(1e3 * dt / n, 3),
               "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": ("f16x3 (split-fp16 operands, f32 accumulate) in every GEMM, f32 tape" if args.amp == "x3" else f"f32 forward, {args.amp}-operand gradient GEMMs" if args.amp else "f32"), "data": "synthetic",
               "config": {"workload": f"SOccDPT_V3 {args.model_type} patch-wise training step, synthetic 1080x1920 targets", "batch_per_gpu": B, "image": S,
                          "encoder_percentage": args.encoder_percentage, "patchwise_percentage": args.patchwise_percentage,
                          "trainable_tensors": sum(1 for q in net.parameters() if q.requires_grad),
                          "drop_path_rate": float(getattr(net, "drop_path_rate", 0.0)), "seg_head_dropout_p": float(net.seg_head[3].p)},
-              "split_ms": {"train_forward": round(ev[0].elapsed_time(ev[1]), 2), "criterion": round(ev[1].elapsed_time(ev[2]), 2),
-                           "backward_all_unfrozen": round(ev[2].elapsed_time(ev[3]), 2)},
+              **({"split_ms": split_ms} if split_ms else {}),
               "launches_per_step": round(launches, 1),
-              "roofline": roof, "cpu_baseline": cpu, "loss": round(float(out["loss"]), 6),
+              "roofline": roof, "cpu_baseline": cpu, "loss": round(loss, 6),
               "train_workspace_gib": round(net._engine(dev).train_workspace(B).numel() / 2 ** 30, 2)}
     os.dup2(real_stdout, 1)
     print(json.dumps(result), flush=True)
@@ -270,12 +311,19 @@ def main():
     ap.add_argument("--prewarm", type=int, default=100, help="untimed clock/allocator pre-warm forwards before the W warm-up steps")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--headline-only", action="store_true",
-                    help="only the timed headline leg + its per-kernel event pass: no fp16 / two-stream / CPU-baseline legs "
+                    help="with --full: only the timed headline leg + its per-kernel event pass: no fp16 / two-stream / CPU-baseline legs "
                          "(what tools/collect_profiles.sh runs under rocprofv3, so profiles/*_kernel_stats.csv describe the headline launches alone)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline, everything else the line reports: the per-kernel event pass (kernels, roofline, roofline_hbm), repeats, "
+                         "latency_b1, the side arithmetic modes with their live errors, other_weights, pipelined and cpu_baseline (--train-step: split_ms and "
+                         "cpu_baseline).  Without it a run sets up, warms up, times --steps steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned as DIR/<name>.npy (float32; an output larger than its share of "
+                         "64 MB in all as a fixed seeded sample of its elements)")
     ap.add_argument("--with-two-streams", action="store_true",
                     help="also time the EXPERIMENTAL two-concurrent-sub-batches mode (soccdpt_set_streams(2); opt-in, DESIGN.md section 4)")
     ap.add_argument("--in-flight", type=int, default=2,
-                    help="side object `pipelined`: this many whole forwards in flight -- independent engines / workspaces, step i + 1 issued on another stream while "
+                    help="--full: side object `pipelined`: this many whole forwards in flight -- independent engines / workspaces, step i + 1 issued on another stream while "
                          "step i drains, no synchronisation in between (the reference's timing loop never synchronises between forwards either: "
                          "scripts/eval_SOccDPT.py:246-259); 1 = off.  `value` and the per-kernel rooflines stay single-stream")
     ap.add_argument("--cpu-sample-frames", type=int, default=2)
@@ -288,6 +336,8 @@ def main():
     ap.add_argument("--encoder-percentage", type=float, default=1.0, help="--train-step: unfreeze_pretrained_encoder_by_percentage")
     ap.add_argument("--patchwise-percentage", type=float, default=1.0, help="--train-step: PatchWiseInplace")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if args.config == 2:
         args.model_type = "dpt_hybrid_384"
         args.batch = args.batch or 4
@@ -364,19 +414,16 @@ def main():
     torch.cuda.synchronize()
     for _ in range(args.warmup):
         out = net(x)
-    # R repeats of EXACTLY K timed steps, each bracketed by barrier + synchronize on both sides; R is chosen so that at least ~50 steps are
-    # timed in all (20 steps of this forward are 37 ms: one repeat alone moves +-2 % with the clock state the previous process left).
-    # `value` comes from the MEDIAN repeat; every repeat, the minimum and the median are printed.
-    repeats = 1 if args.steps >= 50 else min(5, -(-50 // max(args.steps, 1)))
-    rep_elapsed = []
-    for _ in range(repeats):
-        barrier()
-        t0 = time.perf_counter()
-        for _ in range(args.steps):
-            out = net(x)
-        barrier()
-        rep_elapsed.append(time.perf_counter() - t0)
-    elapsed = sorted(rep_elapsed)[(len(rep_elapsed) - 1) // 2]
+    # EXACTLY K timed steps, bracketed by barrier + synchronize on both sides: `value` and `ms_per_step` come from this one region.
+    barrier()
+    t0 = time.perf_counter()
+    for _ in range(args.steps):
+        out = net(x)
+    barrier()
+    elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, dict(zip(("inv_depth", "segmentation", "points", "occupancy"), out)))
+    rep_elapsed = [elapsed]
     per_rank_ms = [round(elapsed / args.steps * 1e3, 3)]
     rccl_ranks = 1
     if world > 1:
@@ -391,20 +438,34 @@ def main():
     frames = world * B * args.steps
     fps = frames / elapsed
 
-    # ---- per-kernel timing (separate, equally sized region): every launch carries a HIP start / stop event pair bound to its own dispatch
+    # ---- --full: R - 1 more regions of the same K steps, so that at least ~50 steps are timed in all (20 steps of this forward are 37 ms: one
+    # region alone moves +-2 % with the clock state the previous process left); every region, the minimum and the median are
+    # printed beside `value`, which stays the first region ----
+    repeats = 1 if not args.full or args.steps >= 50 else min(5, -(-50 // args.steps))
+    for _ in range(repeats - 1):
+        barrier()
+        t0 = time.perf_counter()
+        for _ in range(args.steps):
+            out = net(x)
+        barrier()
+        rep_elapsed.append(time.perf_counter() - t0)
+
+    # ---- per-kernel timing (--full; separate, equally sized region): every launch carries a HIP start / stop event pair bound to its own dispatch
     # (hipExtLaunchKernelGGL, csrc/launch.h), so a kernel's time is its begin -> end on the device -- what rocprofv3 --kernel-trace reports --
     # and device_ms_per_step, their sum, excludes the gaps between dependent launches (it is <= ms_per_step) ----
     eng = net._engine(dev)
     prof_steps = max(3, min(args.steps, 10))
-    eng.profile_enable(True)
-    barrier()
-    t1 = time.perf_counter()
-    for _ in range(prof_steps):
-        out = net(x)
-    torch.cuda.synchronize()
-    elapsed_prof = time.perf_counter() - t1
-    stats = eng.profile_collect()
-    eng.profile_enable(False)
+    stats = None
+    if args.full:
+        eng.profile_enable(True)
+        barrier()
+        t1 = time.perf_counter()
+        for _ in range(prof_steps):
+            out = net(x)
+        torch.cuda.synchronize()
+        elapsed_prof = time.perf_counter() - t1
+        stats = eng.profile_collect()
+        eng.profile_enable(False)
 
     def load_pmc():
         """HBM bytes / MFMA-pipe utilisation per launch: PMC counters cannot be read inside this process; they come from the committed rocprofv3
@@ -438,42 +499,48 @@ def main():
 
     result = None
     if rank == 0:
-        kernels, total_ms = kernel_table(stats, prof_steps)
-        # The dominant KERNEL is the igemm_kernel template (igemm.hip): every Linear layer and convolution of the network is one of its tile
-        # instantiations ("igemm_<dtype>_<BM>x<BN>x<BK>_s<stages>" families).  The roofline object prices the template as a whole (sum of
-        # algorithmic FLOPs / sum of launch durations) and lists every instantiation under by_config.
-        pmc, pmc_file, pmc_stale = load_pmc()
-        roofline = igemm_roofline(stats, prof_steps, args.precision, pmc)
-        if roofline is not None:   # every algorithmic FLOP of the forward over the wall time of a step, against the 16-bit MFMA peak
-            roofline["whole_forward_frac"] = round(world * B * FWD_GFLOP_PER_FRAME[args.model_type] / (elapsed / args.steps) / 1e3 / PEAK_BF16_TFLOPS, 4)
-            roofline["whole_forward_note"] = f"B x {FWD_GFLOP_PER_FRAME[args.model_type]} GFLOP per frame / ms_per_step / 2500 TFLOP/s per GPU (projection and every non-GEMM launch included in the time)"
-            if world > 1:
-                roofline["whole_forward_frac"] = round(roofline["whole_forward_frac"] / world, 4)
-        if pmc_file and roofline and roofline.get("traffic") is not None:
-            roofline["traffic_source"] = pmc_file
-        elif roofline is not None and pmc_stale:
-            roofline["traffic_note"] = "null: " + pmc_stale
-        # second regime (SURVEY.md 8d "two regimes, report both"): the HBM-bound projection + occupancy expansion
-        hb = {n: stats[n] for n in ("project_voxelise", "occ_expand") if n in stats and stats[n]["bytes"] > 0}
-        roofline_hbm = None
-        if hb:
-            hb_bytes, hb_ms, hb_l = sum(v["bytes"] for v in hb.values()), sum(v["ms"] for v in hb.values()), sum(v["launches"] for v in hb.values())
-            ach = hb_bytes / (hb_ms * 1e-3) / 1e9
-            roofline_hbm = dict(bound="hbm", kernel="project_rows_kernel + occ_expand_kernel", achieved=round(ach, 1), peak=PEAK_HBM_GBS, unit="GB/s",
-                                frac=round(ach / PEAK_HBM_GBS, 4), traffic=None, bytes_per_step=hb_bytes / prof_steps, us_per_step=round(hb_ms * 1e3 / prof_steps, 2),
-                                by_kernel=[dict(kernel=n, avg_launch_us=round(v["ms"] * 1e3 / v["launches"], 2), achieved=round(v["bytes"] / (v["ms"] * 1e-3) / 1e9, 1),
-                                                frac=round(v["bytes"] / (v["ms"] * 1e-3) / 1e9 / PEAK_HBM_GBS, 4),
-                                                **({"traffic": round(pmc[n]["hbm_bytes_per_launch"])} if n in pmc else {})) for n, v in hb.items()])
-            if all(n in pmc for n in hb):
-                roofline_hbm["traffic"] = round(sum(pmc[n]["hbm_bytes_per_launch"] * hb[n]["launches"] for n in hb) / hb_l)
+        prof = {}   # --full: the per-kernel event pass
+        if stats is not None:
+            kernels, total_ms = kernel_table(stats, prof_steps)
+            # The dominant KERNEL is the igemm_kernel template (igemm.hip): every Linear layer and convolution of the network is one of its tile
+            # instantiations ("igemm_<dtype>_<BM>x<BN>x<BK>_s<stages>" families).  The roofline object prices the template as a whole (sum of
+            # algorithmic FLOPs / sum of launch durations) and lists every instantiation under by_config.
+            pmc, pmc_file, pmc_stale = load_pmc()
+            roofline = igemm_roofline(stats, prof_steps, args.precision, pmc)
+            if roofline is not None:   # every algorithmic FLOP of the forward over the wall time of a step, against the 16-bit MFMA peak
+                roofline["whole_forward_frac"] = round(world * B * FWD_GFLOP_PER_FRAME[args.model_type] / (elapsed / args.steps) / 1e3 / PEAK_BF16_TFLOPS, 4)
+                roofline["whole_forward_note"] = f"B x {FWD_GFLOP_PER_FRAME[args.model_type]} GFLOP per frame / ms_per_step / 2500 TFLOP/s per GPU (projection and every non-GEMM launch included in the time)"
+                if world > 1:
+                    roofline["whole_forward_frac"] = round(roofline["whole_forward_frac"] / world, 4)
+            if pmc_file and roofline and roofline.get("traffic") is not None:
+                roofline["traffic_source"] = pmc_file
+            elif roofline is not None and pmc_stale:
+                roofline["traffic_note"] = "null: " + pmc_stale
+            # second regime (SURVEY.md 8d "two regimes, report both"): the HBM-bound projection + occupancy expansion
+            hb = {n: stats[n] for n in ("project_voxelise", "occ_expand") if n in stats and stats[n]["bytes"] > 0}
+            roofline_hbm = None
+            if hb:
+                hb_bytes, hb_ms, hb_l = sum(v["bytes"] for v in hb.values()), sum(v["ms"] for v in hb.values()), sum(v["launches"] for v in hb.values())
+                ach = hb_bytes / (hb_ms * 1e-3) / 1e9
+                roofline_hbm = dict(bound="hbm", kernel="project_rows_kernel + occ_expand_kernel", achieved=round(ach, 1), peak=PEAK_HBM_GBS, unit="GB/s",
+                                    frac=round(ach / PEAK_HBM_GBS, 4), traffic=None, bytes_per_step=hb_bytes / prof_steps, us_per_step=round(hb_ms * 1e3 / prof_steps, 2),
+                                    by_kernel=[dict(kernel=n, avg_launch_us=round(v["ms"] * 1e3 / v["launches"], 2), achieved=round(v["bytes"] / (v["ms"] * 1e-3) / 1e9, 1),
+                                                    frac=round(v["bytes"] / (v["ms"] * 1e-3) / 1e9 / PEAK_HBM_GBS, 4),
+                                                    **({"traffic": round(pmc[n]["hbm_bytes_per_launch"])} if n in pmc else {})) for n, v in hb.items()])
+                if all(n in pmc for n in hb):
+                    roofline_hbm["traffic"] = round(sum(pmc[n]["hbm_bytes_per_launch"] * hb[n]["launches"] for n in hb) / hb_l)
+            prof = {"roofline": roofline, "roofline_hbm": roofline_hbm, "kernels": kernels, "device_ms_per_step": round(total_ms / prof_steps, 3),
+                    "ms_per_step_with_events": round(elapsed_prof / prof_steps * 1e3, 3)}
         dtype_name = {"mixed": "mixed fp16 + f16x3 (SOCCDPT_PREC_MIXED: fp16 MFMA operands, x3 split per the shipped precision map; f32 accumulate)"}.get(args.precision, args.precision)
         result = {
             "metric": f"frames/sec SOccDPT_V3 {args.model_type.replace('dpt_', '')} @{img}px (depth+seg+points+occupancy forward)",
             "value": round(fps, 2), "unit": "frames/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": round(elapsed / args.steps * 1e3, 3), "higher_is_better": True, "scaling": "weak",
-            "repeats": {"count": repeats, "steps_each": args.steps, "ms_per_step": [round(e / args.steps * 1e3, 4) for e in rep_elapsed],
-                        "min_ms_per_step": round(min(rep_elapsed) / args.steps * 1e3, 4), "median_ms_per_step": round(elapsed / args.steps * 1e3, 4),
-                        "note": "value / ms_per_step are the median repeat (rank-0 clock; with N > 1 the maximum over ranks of each rank's median)"},
+            **({"repeats": {"count": repeats, "steps_each": args.steps, "ms_per_step": [round(e / args.steps * 1e3, 4) for e in rep_elapsed],
+                            "min_ms_per_step": round(min(rep_elapsed) / args.steps * 1e3, 4),
+                            "median_ms_per_step": round(sorted(rep_elapsed)[(len(rep_elapsed) - 1) // 2] / args.steps * 1e3, 4),
+                            "note": "rank-0 clock; value / ms_per_step are the first repeat (with N > 1 the maximum over ranks of each rank's first repeat)"}}
+               if args.full else {}),
             "vs_baseline": None, "dtype": dtype_name, "data": "synthetic",
             "config": {"workload": f"SOccDPT_V3 {args.model_type} full forward, compute_occ=True, camera 1920x1080",
                        "batch_per_gpu": B, "global_batch": B * world, "image": img, "weights": args.weights, "streams_per_gpu": args.streams, "hip_graph": args.graph,
@@ -483,12 +550,8 @@ def main():
                        # shipped = the compiled-in map on the synthetic weights it was derived from; calibrated = soccdpt_prec_calibrate ran (--calibrate)
                        "precision_map_source": (net.precision_map_source(dev) if args.precision == "mixed" else None),
                        "precision_map_calibration": ({k: v for k, v in calib_report.items() if k != "x3_groups"} if calib_report else None)},
-            "roofline": roofline,
-            "roofline_hbm": roofline_hbm,
+            **prof,
             "rccl_ranks": rccl_ranks, "per_rank_ms_per_step": per_rank_ms,
-            "kernels": kernels,
-            "device_ms_per_step": round(total_ms / prof_steps, 3),
-            "ms_per_step_with_events": round(elapsed_prof / prof_steps * 1e3, 3),
             "launches_per_step": eng.launch_count() + 2,
         }
         if world > 1 and getattr(net, "occ_exchange", None) is not None and hasattr(net.occ_exchange, "window_ms"):
@@ -496,7 +559,7 @@ def main():
             result["exchange_window_ms"] = None if wms is None else round(wms, 4)
 
     single = rank == 0 and world == 1 and not args.graph and args.streams == 1
-    side_ok = single and not args.headline_only and not args.no_side_modes
+    side_ok = single and args.full and not args.headline_only and not args.no_side_modes
 
     def build(prec_name, streams=1, weights=None):
         with contextlib.redirect_stdout(io.StringIO()):
@@ -519,7 +582,7 @@ def main():
 
     # ---- B = 1 latency: the protocol behind the paper's 47 Hz (/root/reference/SOccDPT/scripts/eval_SOccDPT.py:246-259: 50 forwards of ONE frame,
     # fps = 50 / elapsed), here WITH a device synchronisation on both sides of the 50 forwards.  x_paper_hz compares like with like.
-    if single and not args.headline_only:
+    if single and args.full and not args.headline_only:
         x1 = x[:1].contiguous()
         for _ in range(10):
             net(x1)
@@ -677,7 +740,7 @@ def main():
     # the stream order of each engine's own launches.  The HBM-bound tail of one step (depth tail -> projection -> expansion: little MFMA / LDS use) and the
     # latency-bound encoder launches of the next overlap.  Outputs are bit-compared with the sequential run first.  Not the headline: the kernels of
     # `roofline` are timed running alone.
-    if single and args.in_flight > 1 and not args.headline_only:
+    if single and args.full and args.in_flight > 1 and not args.headline_only:
         nets = [net] + [build(args.precision) for _ in range(args.in_flight - 1)]
         if args.precision == "mixed" and calib_report is not None:
             for m in nets[1:]:
@@ -713,7 +776,7 @@ def main():
         del nets, outs
 
     # ---- CPU baseline: the oracle on this host's cores, bounded sample, rank 0 at N = 1 only ----
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         from oracle import soccdpt_ref as R
         # the GPU box gives one GPU's share of the host: 16 cores (more threads only oversubscribe)
         try:
@@ -737,7 +800,8 @@ def main():
                                             f"(oracle/soccdpt_ref.py), {tcpu:.1f} s"}
     if rank == 0 and "cpu_baseline" not in result:   # the key is always there: a consumer of the N > 1 line need not special-case it
         result["cpu_baseline"] = None
-        result["cpu_baseline_note"] = "timed on rank 0 at N = 1 only (bench contract)" if world > 1 else "switched off (--no-cpu-baseline / --headline-only)"
+        result["cpu_baseline_note"] = ("timed on rank 0 at N = 1 only (bench contract)" if world > 1 else
+                                       "switched off (--no-cpu-baseline / --headline-only)" if args.full else "timed under --full only")
     if rank == 0:
         sys.stdout.flush()
         os.write(real_stdout, (json.dumps(result) + "\n").encode())

@@ -43,7 +43,7 @@ def test_bench_two_rank_rehearsal_on_one_gpu(gpu_device, tmp_path):
     # bench.py is called the way the driver may call it: plainly, with --gpus 2 and no launcher around it.  The parent starts the two ranks itself
     # (python -m torch.distributed.run as a child process, before anything touches the GPU), relays rank 0's line and checks rccl_ranks == 2.
     env.pop("WORLD_SIZE", None); env.pop("RANK", None); env.pop("LOCAL_RANK", None)
-    r = subprocess.run([sys.executable, bench, "--gpus", "2", "--steps", "5", "--warmup", "2", "--prewarm", "3", "--batch", "2"],
+    r = subprocess.run([sys.executable, bench, "--gpus", "2", "--steps", "5", "--warmup", "2", "--prewarm", "3", "--batch", "2", "--full"],
                        env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]

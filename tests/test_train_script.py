@@ -38,11 +38,13 @@ def test_sweep_json_and_cli_surface(tmp_path):
     assert args.device == "cpu" and args.count == 1 and args.version == 3     # the reference's defaults (train_SOccDPT.py:485-546)
     with pytest.raises(SystemExit):
         build_parser().parse_args(["-v", "4", "-dt", "bdd", "-t", "dpt_swin2_tiny_256", "--sweep_json", "x.json"])
-    if os.path.isdir("/root/reference/config"):     # build container only: every sweep file of the reference parses
-        for f in sorted(os.listdir("/root/reference/config")):
-            if f.endswith(".json"):
-                m, p = read_sweep(os.path.join("/root/reference/config", f))
-                assert p and all(isinstance(v, list) and v for v in p.values()), f
+    # every sweep file of the reference parses (its config/*.json, stored as data fixtures under tests/golden/sweep_configs)
+    cfg_dir = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "sweep_configs")
+    files = sorted(f for f in os.listdir(cfg_dir) if f.endswith(".json"))
+    assert len(files) == 23, files
+    for f in files:
+        m, p = read_sweep(os.path.join(cfg_dir, f))
+        assert p and all(isinstance(v, list) and v for v in p.values()), f
 
 
 def test_freeze_unfreeze_is_index_based_like_the_reference(tmp_path):

@@ -1,7 +1,7 @@
 """Six optimisation steps on one synthetic batch; prints the SHA-1 of the resulting weights / buffers (bit-reproducibility across processes).
 AMP=bf16|f16 selects the 16-bit operand mode (no GradScaler here: the hash, not the trajectory, is the point)."""
 import os, sys, tempfile, hashlib, torch
-sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))   # the repository root
 from soccdpt_amd.lib import PREC_F32
 from soccdpt_amd.model.SOccDPT import SOccDPT_V3
 from soccdpt_amd.scripts.train_SOccDPT import SyntheticDepthSegDataset, get_batch

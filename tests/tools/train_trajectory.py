@@ -1,5 +1,5 @@
 import os, sys, tempfile, torch
-sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))   # the repository root
 from soccdpt_amd.lib import PREC_F32
 from soccdpt_amd.model.SOccDPT import SOccDPT_V3
 from soccdpt_amd.model.spec import MODEL_TYPE_TO_BACKBONE, backbone_image_size

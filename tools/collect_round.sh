@@ -21,25 +21,25 @@ fi
 if [ "$PART" = "all" ] || [ "$PART" = "2" ]; then
 bash tools/collect_profiles.sh ${TAG}_hybrid384 --config 2 > $OUT/collect_hybrid.log 2>&1
 echo "hybrid done"
-for p in f16 f16x3 f32; do python3 bench.py --precision $p --no-cpu-baseline > $OUT/bench_$p.json 2>> $OUT/bench.err; done
-for w in salt1 salt2 trained_like; do python3 bench.py --weights $w --no-cpu-baseline --no-other-weights > $OUT/bench_weights_$w.json 2>> $OUT/bench.err; done
-python3 bench.py --no-cpu-baseline --no-side-modes --in-flight 3 > $OUT/bench_in_flight3.json 2>> $OUT/bench.err
-python3 bench.py --config 2 --precision f16x3 --no-cpu-baseline > $OUT/bench_hybrid384_f16x3.json 2>> $OUT/bench.err
-python3 bench.py --config 2 --precision f32 --no-cpu-baseline > $OUT/bench_hybrid384_f32.json 2>> $OUT/bench.err
-python3 bench.py --config 3 --precision f16x3 --no-cpu-baseline > $OUT/bench_base384_f16x3.json 2>> $OUT/bench.err
+for p in f16 f16x3 f32; do python3 bench.py --full --precision $p --no-cpu-baseline > $OUT/bench_$p.json 2>> $OUT/bench.err; done
+for w in salt1 salt2 trained_like; do python3 bench.py --full --weights $w --no-cpu-baseline --no-other-weights > $OUT/bench_weights_$w.json 2>> $OUT/bench.err; done
+python3 bench.py --full --no-cpu-baseline --no-side-modes --in-flight 3 > $OUT/bench_in_flight3.json 2>> $OUT/bench.err
+python3 bench.py --full --config 2 --precision f16x3 --no-cpu-baseline > $OUT/bench_hybrid384_f16x3.json 2>> $OUT/bench.err
+python3 bench.py --full --config 2 --precision f32 --no-cpu-baseline > $OUT/bench_hybrid384_f32.json 2>> $OUT/bench.err
+python3 bench.py --full --config 3 --precision f16x3 --no-cpu-baseline > $OUT/bench_base384_f16x3.json 2>> $OUT/bench.err
 echo "modes done"
 fi
 if [ "$PART" = "1" ] || [ "$PART" = "2" ]; then exit 0; fi
-python3 bench.py --train-step > $OUT/bench_train_step.json 2>> $OUT/bench.err
-python3 bench.py --train-step --amp x3 > $OUT/bench_train_step_x3.json 2>> $OUT/bench.err
-python3 bench.py --train-step --amp bf16 > $OUT/bench_train_step_amp.json 2>> $OUT/bench.err
-python3 bench.py --train-step --amp f16 > $OUT/bench_train_step_amp_f16.json 2>> $OUT/bench.err
-python3 bench.py --train-step --batch 3 --encoder-percentage 0.5 --patchwise-percentage 0.5 > $OUT/bench_train_step_B3_enc50_patch50.json 2>> $OUT/bench.err
-python3 bench.py --train-step --amp bf16 --batch 3 --encoder-percentage 0.5 --patchwise-percentage 0.5 > $OUT/bench_train_step_amp_B3_enc50_patch50.json 2>> $OUT/bench.err
-python3 bench.py --train-step --model-type dpt_swin2_base_384 --batch 8 > $OUT/bench_train_step_base384.json 2>> $OUT/bench.err
-python3 bench.py --train-step --model-type dpt_swin2_base_384 --batch 8 --amp bf16 > $OUT/bench_train_step_amp_base384.json 2>> $OUT/bench.err
-python3 bench.py --train-step --model-type dpt_hybrid_384 --batch 4 > $OUT/bench_train_step_hybrid384.json 2>> $OUT/bench.err
-python3 bench.py --train-step --model-type dpt_hybrid_384 --batch 4 --amp bf16 > $OUT/bench_train_step_amp_hybrid384.json 2>> $OUT/bench.err
+python3 bench.py --full --train-step > $OUT/bench_train_step.json 2>> $OUT/bench.err
+python3 bench.py --full --train-step --amp x3 > $OUT/bench_train_step_x3.json 2>> $OUT/bench.err
+python3 bench.py --full --train-step --amp bf16 > $OUT/bench_train_step_amp.json 2>> $OUT/bench.err
+python3 bench.py --full --train-step --amp f16 > $OUT/bench_train_step_amp_f16.json 2>> $OUT/bench.err
+python3 bench.py --full --train-step --batch 3 --encoder-percentage 0.5 --patchwise-percentage 0.5 > $OUT/bench_train_step_B3_enc50_patch50.json 2>> $OUT/bench.err
+python3 bench.py --full --train-step --amp bf16 --batch 3 --encoder-percentage 0.5 --patchwise-percentage 0.5 > $OUT/bench_train_step_amp_B3_enc50_patch50.json 2>> $OUT/bench.err
+python3 bench.py --full --train-step --model-type dpt_swin2_base_384 --batch 8 > $OUT/bench_train_step_base384.json 2>> $OUT/bench.err
+python3 bench.py --full --train-step --model-type dpt_swin2_base_384 --batch 8 --amp bf16 > $OUT/bench_train_step_amp_base384.json 2>> $OUT/bench.err
+python3 bench.py --full --train-step --model-type dpt_hybrid_384 --batch 4 > $OUT/bench_train_step_hybrid384.json 2>> $OUT/bench.err
+python3 bench.py --full --train-step --model-type dpt_hybrid_384 --batch 4 --amp bf16 > $OUT/bench_train_step_amp_hybrid384.json 2>> $OUT/bench.err
 echo "train lines done"
 for a in 0 x3 bf16; do
   TRAIN_AMP=$a rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/train_$a -o t -- python3 tools/train_bench.py 8 6 > $OUT/train_$a.json 2>> $OUT/bench.err
