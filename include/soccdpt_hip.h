@@ -31,8 +31,11 @@ extern "C" {
  *   3 round 4 (SOCCDPT_PREC_MIXED + the precision map entry points, soccdpt_sizeof, soccdpt_occ_zero / soccdpt_occ_set,
  *     soccdpt_set_stage_xcd / soccdpt_stage_xcd_status);
  *   4 round 5 (the opt-in XCD-local persistent stage kernel and its three entry points are gone: measured 13-15 % slower than the launch
- *     chain in round 4; soccdpt_prec_calibrate and the precision-map source query are new). */
-#define SOCCDPT_ABI_VERSION 5
+ *     chain in round 4; soccdpt_prec_calibrate and the precision-map source query are new);
+ *   5 round 6 (soccdpt_calib_report gained the hold-out / head-room / per-pixel fields; soccdpt_calib_options, soccdpt_prec_calibrate_ex and
+ *     soccdpt_op_window_attention_qkv are new);
+ *   6 (soccdpt_igemm_args gained the fused-epilogue fields res2_h .. halo_fmt; soccdpt_op_depth_tail and soccdpt_op_seg_tail are new). */
+#define SOCCDPT_ABI_VERSION 6
 
 /* backbone ids: model/loader.py:65-77 (model_type switch), model/blocks.py:59-78 */
 #define SOCCDPT_BACKBONE_SWIN2T16_256 0 /* dpt_swin2_tiny_256 */
@@ -422,8 +425,37 @@ typedef struct soccdpt_igemm_args {
     int32_t sk_defer; /* with splitk > 1: every split only stores its partial tile and a second launch sums the splits in order into out_f32 (no
                          bias / residual / activation / operand output); what the training step's weight-gradient GEMMs use with the 8-wave
                          128 x 128 tiles (tune 46 for bf16 / fp16 operands, 3 for f32 / f16x3) */
+    /* ---- ABI 6: the fused epilogues of the forward (kernel-level tests; zeros / NULLs keep the behaviour above) ----
+     * res2_h, res2_w > 0: res2 is a LOW-RES f32 NHWC map [B][res2_h][res2_w][N] sampled bilinearly (align_corners) at the H x W output pixel (needs H, W).
+     * ln_g != NULL: Swin-V2 post-norm epilogue instead of the generic one, N <= 128: ln_xf[m][:] = (ln_residual ? ln_xf[m][:] : 0) + LN(acc + bias)[m][:] * ln_g
+     *   + ln_b (eps 1e-5, biased variance); the operand copy goes to out_bf16 (plain [M][N]) and, when ln_halo != NULL, to the zero-halo image ln_halo
+     *   [B][H+2][W+2][N] (border untouched).  res1 / res2 / act / out_f32 do not apply.
+     * dot3 != 0: the seg head's 3x3 convolution with its three-class 1x1 classifier in the epilogue (16-bit operands; taps 9, Cin % 64 == 0, N % 128 == 0):
+     *   out_dot[(t * M + m) * 4 + c] = sum over channel tile t (128 wide, or 256 with tune 47 where igemm_dot3_bn allows it; tune 21 forces 128) of
+     *   act(v)[n] * dot_w[c * N + n], lane 3 = 0; no other output.  soccdpt_op_seg_tail finishes it.
+     * out_fmt, halo_fmt: format of out_bf16 / ln_halo.  -1 or 0 = the launch's own; 1 = IEEE fp16 from an SOCCDPT_PREC_F16X3 launch; 3 = x3 from an
+     *   SOCCDPT_PREC_F16 / _F16X2W launch (the mixed-precision forward's cross-format stores). */
+    int32_t res2_h, res2_w;
+    const float* ln_g;
+    const float* ln_b;
+    float* ln_xf;
+    void* ln_halo;
+    int32_t ln_residual;
+    int32_t dot3;
+    int32_t out_fmt, halo_fmt;
 } soccdpt_igemm_args;
 int soccdpt_op_igemm(const soccdpt_igemm_args* args, void* stream);
+
+/* Kernel-level entries (tests) of the 16-bit heads' fused tails (csrc/depth_tail.hip, csrc/elementwise.hip).
+ * soccdpt_op_depth_tail: dev_d1 [B][h][w][128] 16-bit NHWC (SOCCDPT_PREC_BF16 or _F16 by precision), dev_wt [32][9*128] tap-major 16-bit, dev_bias [32],
+ *   dev_w4 [32] f32 -> dev_out [B][2h][2w] f32 = relu(w4 . relu(conv3x3(up2(d1)) + bias) + b4), up2 = bilinear x2 with align_corners, the up-sampled patch
+ *   rounded to the operand format (model/dpt.py:207-216).  2h % 8 == 0, 2w % 16 == 0.
+ * soccdpt_op_seg_tail: dev_part [nplanes][M][4] partial logits of a dot3 launch (M = B*h*w), dev_bias [3] -> dev_tmp [M][3] logits, dev_out [B][3][2h][2w]
+ *   = act(bilinear x2 align_corners(logits)), act = sigmoid when sigmoid != 0, else 0.5 tanh + 0.5 (model/SOccDPT.py:660-674). */
+int soccdpt_op_depth_tail(const void* dev_d1, const void* dev_wt, const float* dev_bias, const float* dev_w4, float b4, float* dev_out, int precision,
+                          int B, int h, int w, void* stream);
+int soccdpt_op_seg_tail(const float* dev_part, int nplanes, const float* dev_bias, float* dev_tmp, float* dev_out, int B, int h, int w, int sigmoid,
+                        void* stream);
 
 /* Kernel-level entries (tests): the reader side of the hybrid's GroupNorm -- timm GroupNormAct after every StdConv2dSame of the ResNetV2 stem / stages
  * (created by _make_pretrained_vitb_rn50_384, /root/reference/SOccDPT/model/backbones/vit.py:147-201; restated in oracle/soccdpt_ref.py rn_bottleneck).

@@ -570,6 +570,32 @@ int soccdpt_op_igemm(const soccdpt_igemm_args* a, void* stream) {
     d.gn_stats = a->gn_stats; d.gn_part = a->gn_part; d.gn_bm_out = &gn_bm; d.gn_cpg = a->gn_cpg; d.gn_hw = a->gn_hw;
     d.gn_part_floats = a->gn_part_floats;
     d.stamps = reinterpret_cast<unsigned long long*>(a->stamps);
+    // ABI 6: the fused epilogues (zeros / NULLs: the generic epilogue, operand copies in the launch's own format)
+    d.res2_h = a->res2_h; d.res2_w = a->res2_w;
+    d.ln_g = a->ln_g; d.ln_b = a->ln_b; d.ln_xf = a->ln_xf; d.ln_halo = a->ln_halo; d.ln_residual = a->ln_residual;
+    d.dot3 = a->dot3;
+    d.out_fmt = a->out_fmt == 0 ? -1 : a->out_fmt; d.halo_fmt = a->halo_fmt == 0 ? -1 : a->halo_fmt;
+    if ((a->res2_h != 0 || a->res2_w != 0) && (a->res2_h <= 0 || a->res2_w <= 0 || !a->res2))
+        return fail(nullptr, "soccdpt_op_igemm: a sampled residual needs res2 and its source size (res2_h, res2_w > 0)");
+    if (a->res2_h && (a->ln_g || a->dot3)) return fail(nullptr, "soccdpt_op_igemm: the sampled residual belongs to the generic epilogue");
+    if (a->ln_g && (a->res1 || a->res2 || a->act || a->out_f32 || a->out_halo || a->dot3 || a->out_dot))
+        return fail(nullptr, "soccdpt_op_igemm: the LayerNorm epilogue writes ln_xf / out_bf16 / ln_halo only (no res1, res2, act, out_f32, out_halo or dot)");
+    if (a->ln_halo && !a->ln_g) return fail(nullptr, "soccdpt_op_igemm: ln_halo needs the LayerNorm epilogue (ln_g)");
+    if (a->ln_g && a->taps != 1) return fail(nullptr, "soccdpt_op_igemm: the LayerNorm epilogue is a plain-GEMM (taps == 1) feature");
+    if (a->ln_residual != 0 && a->ln_residual != 1) return fail(nullptr, "soccdpt_op_igemm: ln_residual is 0 or 1");
+    if (a->dot3 && (a->taps != 9 || a->Cin % 64 || a->N % 128 || !a->dot_w || !a->out_dot))
+        return fail(nullptr, "soccdpt_op_igemm: dot3 needs taps == 9, Cin % 64 == 0, N % 128 == 0, dot_w and out_dot");
+    if (a->dot3 && a->precision != SOCCDPT_PREC_BF16 && a->precision != SOCCDPT_PREC_F16)
+        return fail(nullptr, "soccdpt_op_igemm: dot3 needs SOCCDPT_PREC_BF16 or _F16 operands");
+    if (a->dot3 && a->tune != -1 && a->tune != 21 && a->tune != 47) return fail(nullptr, "soccdpt_op_igemm: dot3 takes tune -1, 21 (128-wide) or 47 (256-wide)");
+    for (int f : {a->out_fmt, a->halo_fmt}) {
+        const bool same = f == 0 || f == -1;
+        const bool to_f16 = f == 1 && a->precision == SOCCDPT_PREC_F16X3;
+        const bool to_x3 = f == 3 && (a->precision == SOCCDPT_PREC_F16 || a->precision == SOCCDPT_PREC_F16X2W);
+        if (!same && !to_f16 && !to_x3)
+            return fail(nullptr, "soccdpt_op_igemm: out_fmt / halo_fmt is -1 or 0 (the launch's format), 1 (fp16 from an x3 launch) or 3 (x3 from an fp16 launch)");
+    }
+    if (a->halo_fmt > 0 && !a->ln_halo) return fail(nullptr, "soccdpt_op_igemm: halo_fmt without ln_halo");
     std::string err;
     if (a->gn_stats && a->gn_count && (a->gn_hw <= 0 || a->gn_cpg <= 0 || a->M % a->gn_hw || a->N % a->gn_cpg))
         return fail(nullptr, "soccdpt_op_igemm: GroupNorm statistics requested with gn_hw / gn_cpg that do not divide M / N");
@@ -580,6 +606,28 @@ int soccdpt_op_igemm(const soccdpt_igemm_args* a, void* stream) {
     // gn_count are no longer touched): a finish launch behind the convolution.  gn_count == NULL: partials only, as the forward launches it.
     if (a->gn_stats && a->gn_count && launch_gn_finish(a->gn_part, a->gn_stats, a->M / a->gn_hw, a->gn_hw / gn_bm, a->N / a->gn_cpg, a->gn_hw, a->gn_cpg, 1e-5f, (hipStream_t)stream, err))
         return fail(nullptr, err);
+    return 0;
+}
+
+int soccdpt_op_depth_tail(const void* dev_d1, const void* dev_wt, const float* dev_bias, const float* dev_w4, float b4, float* dev_out, int precision,
+                          int B, int h, int w, void* stream) {
+    std::string err;
+    if (!dev_d1 || !dev_wt || !dev_bias || !dev_w4 || !dev_out) return fail(nullptr, "soccdpt_op_depth_tail: null argument");
+    if (precision != SOCCDPT_PREC_BF16 && precision != SOCCDPT_PREC_F16) return fail(nullptr, "soccdpt_op_depth_tail: precision is SOCCDPT_PREC_BF16 or _F16");
+    if (B <= 0 || h <= 0 || w <= 0) return fail(nullptr, "soccdpt_op_depth_tail: B, h, w must be positive");
+    if ((2 * h) % 8 || (2 * w) % 16) return fail(nullptr, "soccdpt_op_depth_tail: the output (2h x 2w) must be a multiple of 8 x 16");
+    if (launch_depth_tail(static_cast<const bf16_t*>(dev_d1), static_cast<const bf16_t*>(dev_wt), dev_bias, dev_w4, b4, dev_out, precision == SOCCDPT_PREC_F16 ? 1 : 0,
+                          B, h, w, (hipStream_t)stream, err))
+        return fail(nullptr, err);
+    return 0;
+}
+
+int soccdpt_op_seg_tail(const float* dev_part, int nplanes, const float* dev_bias, float* dev_tmp, float* dev_out, int B, int h, int w, int sigmoid,
+                        void* stream) {
+    std::string err;
+    if (!dev_part || !dev_bias || !dev_tmp || !dev_out) return fail(nullptr, "soccdpt_op_seg_tail: null argument");
+    if (nplanes < 1 || B <= 0 || h <= 0 || w <= 0) return fail(nullptr, "soccdpt_op_seg_tail: nplanes, B, h and w must be positive");
+    if (launch_seg_tail_parts(dev_part, nplanes, dev_bias, dev_tmp, dev_out, B, h, w, sigmoid ? 1 : 0, (hipStream_t)stream, err)) return fail(nullptr, err);
     return 0;
 }
 

@@ -15,7 +15,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SOCCDPT_LIB_PATH") or os.path.join(_HERE, "libsoccdpt_hip.so")   # override: A/B of two builds in one GPU call (tools/ab_bench.sh)
 
-ABI_VERSION = 5
+ABI_VERSION = 6
 BACKBONE_IDS = {"swin2t16_256": 0, "swin2b24_384": 1, "vitb_rn50_384": 2}
 PREC_BF16 = 0
 PREC_F32 = 1
@@ -92,6 +92,10 @@ class IgemmArgs(ctypes.Structure):
         ("gn_stats", ctypes.c_void_p), ("gn_part", ctypes.c_void_p), ("gn_count", ctypes.c_void_p),
         ("gn_cpg", ctypes.c_int32), ("gn_hw", ctypes.c_int32), ("gn_part_floats", ctypes.c_size_t), ("gn_count_words", ctypes.c_size_t),
         ("stamps", ctypes.c_void_p), ("sk_defer", ctypes.c_int32),
+        # ABI 6: the fused epilogues (sampled residual, LayerNorm, three-class classifier, cross-format operand stores)
+        ("res2_h", ctypes.c_int32), ("res2_w", ctypes.c_int32),
+        ("ln_g", ctypes.c_void_p), ("ln_b", ctypes.c_void_p), ("ln_xf", ctypes.c_void_p), ("ln_halo", ctypes.c_void_p),
+        ("ln_residual", ctypes.c_int32), ("dot3", ctypes.c_int32), ("out_fmt", ctypes.c_int32), ("halo_fmt", ctypes.c_int32),
     ]
 
 
@@ -232,6 +236,10 @@ def load_library() -> ctypes.CDLL:
     L.soccdpt_op_wino_weights.restype = ci
     L.soccdpt_op_wino_conv.argtypes = [vp, vp, ci, ci, ci, ci, ci, vp, vp, vp, ci, ci, ci, ci, vp, vp, ci, ci, ci, vp, vp]
     L.soccdpt_op_wino_conv.restype = ci
+    L.soccdpt_op_depth_tail.argtypes = [vp, vp, vp, vp, ctypes.c_float, vp, ci, ci, ci, ci, vp]
+    L.soccdpt_op_depth_tail.restype = ci
+    L.soccdpt_op_seg_tail.argtypes = [vp, ci, vp, vp, vp, ci, ci, ci, ci, vp]
+    L.soccdpt_op_seg_tail.restype = ci
     L.soccdpt_op_wgrad_tn.argtypes = [vp, ctypes.c_long, vp, ctypes.c_long, ctypes.c_size_t, ci, ci, ci, ci, ci, vp, ctypes.c_size_t, vp, vp]
     L.soccdpt_op_wgrad_tn.restype = ci
     L.soccdpt_workspace_tensor.argtypes = [vp, ci, ctypes.c_char_p, ctypes.POINTER(cs), ctypes.POINTER(cs),
@@ -659,9 +667,12 @@ class Engine:
 def op_igemm(x, wt, M, N, Cin, taps=1, ldx=0, H=0, W=0, bias=None, res1=None, res2=None, act=0, out_f32=None,
              act_on_f32=0, out_bf16=None, out_halo=0, dot_w=None, dot_b=0.0, out_dot=None, tune=-1, f32=0, precision=None, splitk=1, sk_part=None, sk_count=None,
              conv=None, gather1=0, grp_rows=0, grp_off=0, grp_stride=0, seg2_k=0, seg2_off=0, gn_stats=None, gn_part=None, gn_count=None, gn_cpg=0, gn_hw=0,
-             stamps=None, sk_defer=0):
+             stamps=None, sk_defer=0, res2_h=0, res2_w=0, ln_g=None, ln_b=None, ln_xf=None, ln_halo=None, ln_residual=1, dot3=0, out_fmt=-1,
+             halo_fmt=-1):
     """Kernel-level entry (tests): one implicit-GEMM launch on the current stream.  conv = dict(stride, pad, in_halo, Hi, Wi) selects
-    the generalised convolution addressing."""
+    the generalised convolution addressing.  res2_h / res2_w: res2 is a low-res map sampled bilinearly; ln_*: the LayerNorm epilogue; dot3: the
+    three-class classifier epilogue; out_fmt / halo_fmt: -1 = the launch's format, 1 = fp16 (x3 launch), 3 = x3 (fp16 launch) -- see
+    include/soccdpt_hip.h soccdpt_igemm_args."""
     L = load_library()
     c = conv or {}
     a = IgemmArgs(_ptr(x), _ptr(wt), M, N, Cin, taps, ldx, H, W, _ptr(bias), _ptr(res1), _ptr(res2), act, _ptr(out_f32),
@@ -671,10 +682,32 @@ def op_igemm(x, wt, M, N, Cin, taps=1, ldx=0, H=0, W=0, bias=None, res1=None, re
                   1 if conv else 0, c.get("stride", 1), c.get("pad", 1), c.get("in_halo", 1), c.get("Hi", 0), c.get("Wi", 0), int(gather1),
                   int(grp_rows), int(grp_off), int(seg2_k), int(seg2_off), int(grp_stride),
                   _ptr(gn_stats), _ptr(gn_part), _ptr(gn_count), int(gn_cpg), int(gn_hw),
-                  0 if gn_part is None else gn_part.numel(), 0 if gn_count is None else gn_count.numel(), _ptr(stamps), int(sk_defer))
+                  0 if gn_part is None else gn_part.numel(), 0 if gn_count is None else gn_count.numel(), _ptr(stamps), int(sk_defer),
+                  int(res2_h), int(res2_w), _ptr(ln_g), _ptr(ln_b), _ptr(ln_xf), _ptr(ln_halo), int(ln_residual), int(dot3), int(out_fmt),
+                  int(halo_fmt))
     rc = L.soccdpt_op_igemm(ctypes.byref(a), _stream_ptr(x.device))
     if rc != 0:
         raise RuntimeError("soccdpt_op_igemm failed: " + L.soccdpt_last_error(None).decode())
+
+
+def op_depth_tail(d1, wt, bias, w4, b4, out, B, h, w, precision=PREC_BF16):
+    """Kernel-level entry (tests): the fused depth tail (soccdpt_op_depth_tail) on the current stream: d1 [B][h][w][128] and wt [32][9*128]
+    16-bit (bf16 / fp16 by precision), bias / w4 [32] f32 -> out [B][2h][2w] f32."""
+    L = load_library()
+    rc = L.soccdpt_op_depth_tail(_ptr(d1), _ptr(wt), _ptr(bias), _ptr(w4), float(b4), _ptr(out), int(precision), int(B), int(h), int(w),
+                                 _stream_ptr(d1.device))
+    if rc != 0:
+        raise RuntimeError("soccdpt_op_depth_tail failed: " + L.soccdpt_last_error(None).decode())
+
+
+def op_seg_tail(part, nplanes, bias, tmp, out, B, h, w, sigmoid):
+    """Kernel-level entry (tests): finish of a dot3 launch (soccdpt_op_seg_tail) on the current stream: part [nplanes][B*h*w][4] + bias [3] ->
+    tmp [B*h*w][3] logits and out [B][3][2h][2w] = sigmoid / ScaledTanh of their x2 bilinear (align_corners) up-sampling."""
+    L = load_library()
+    rc = L.soccdpt_op_seg_tail(_ptr(part), int(nplanes), _ptr(bias), _ptr(tmp), _ptr(out), int(B), int(h), int(w), 1 if sigmoid else 0,
+                               _stream_ptr(part.device))
+    if rc != 0:
+        raise RuntimeError("soccdpt_op_seg_tail failed: " + L.soccdpt_last_error(None).decode())
 
 
 def op_gn_finish(part, stats, B, tps, groups, hw, cpg, eps=1e-5):

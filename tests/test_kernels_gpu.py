@@ -108,7 +108,9 @@ def test_igemm_big_tiles_ragged(gpu_device, tune, prec):
 
 
 def test_igemm_depth_tail(gpu_device):
-    """conv3x3 128->32 + bias, ReLU, 1x1 32->1 + bias, ReLU fused (model/dpt.py:209-216)."""
+    """conv3x3 128->32 + bias, ReLU, 1x1 32->1 + bias, ReLU fused (model/dpt.py:209-216) as igemm's unfused `dot_w` tail: the form the
+    forward takes when the head is not 16-bit.  The fused depth_tail.hip kernel of the 16-bit modes (up-sampling included) is tested in
+    tests/test_fused_kernels_gpu.py."""
     from soccdpt_amd.lib import op_igemm
     g = torch.Generator().manual_seed(5)
     B, H, Cin = 2, 16, 128
