@@ -546,7 +546,15 @@ int soccdpt_train_backward_encoder(void* handle, int B, const float* const* dev_
 /* Location of a saved activation / gradient inside the training workspace (tests, debugging): f32 [pixels][channels], NHWC order.
  * "seg_conv" (seg_head.0 output), "seg_act" (after BatchNorm + ReLU + Dropout), "seg_logits", "depth_conv0", "depth_conv2", "lrn_raw<l>"
  * (layer<l+1>_rn output), "fused_raw<l>" (RCU2 input of refinenet<l+1>, l < 3), "rcu2_out<l>", "fusion_out<l>" (out_conv output, before
- * the resize), and after a backward "d_path1", "d_feat<l>" (gradient w.r.t. the hooked encoder map l).  Non-zero for unknown names. */
+ * the resize), and after a backward "d_path1", "d_feat<l>" (gradient w.r.t. the hooked encoder map l).
+ * Zero-halo images, f32 [B][r_l + 2][r_l + 2][C] with a zero border (r_l = resolution of level l): "feat<l>" (the hooked encoder map l as the
+ * decoder reads it), "lrn_relu<l>" (relu(lrn_raw<l>)), "rcu1_mid<l>" (relu after resConfUnit1.conv1, l < 3), "fused_relu<l>" (relu(fused_raw<l>),
+ * l < 3), "rcu2_mid<l>" (relu after resConfUnit2.conv1).
+ * uint8 [pixels][channels] (elems counts bytes): "seg_keep" (the seg head's Dropout keep pattern, 1 = kept).
+ * dpt_hybrid_384 only: "hy.stem_pool" (f32 [B*96*96][64], the stem's GroupNorm + ReLU + max-pool output), "hy.pool_idx" (uint8, same shape: window
+ * position ky * 3 + kx of the max-pool's first maximum; written by soccdpt_train_backward, so valid only after a backward), and per ResNetV2
+ * bottleneck i (stage order, 0..15) "hy.blk<i>.t1" (relu(norm1), f32 zero-halo [B][r_in + 2][r_in + 2][mid]), "hy.blk<i>.t2" (relu(norm2), f32
+ * [B*r_out^2][mid]), "hy.blk<i>.out" (block output after the final ReLU, f32 [B*r_out^2][cout]).  Non-zero for unknown names. */
 int soccdpt_train_workspace_tensor(void* handle, int B, const char* name, size_t* byte_offset, size_t* elems);
 
 /* Location of a named intermediate inside the workspace handed to soccdpt_network for batch B:

@@ -24,6 +24,7 @@ Every function cites the reference file:line it follows (paths relative to
 """
 from __future__ import annotations
 
+import contextlib
 import math
 from dataclasses import dataclass
 from typing import Dict, List, Optional, Sequence, Tuple
@@ -33,6 +34,112 @@ import torch
 import torch.nn.functional as F
 
 Tensor = torch.Tensor
+
+
+# ----------------------------------------------------------------------------
+# Mask pinning (tests only).  Inside `pinned_masks(masks)` every ReLU on the gradient path multiplies by the mask supplied for its site instead
+# of taking the sign of its own input, and MaxPool2dSame gathers at the supplied window position.  The network is then a fixed piecewise-linear
+# function: its float64 gradient differs from another implementation's only by that implementation's arithmetic, not by the pre-activations that
+# round to the other side of zero.  Sites are named by module path (`<prefix>.relu1`, `seg_head.2`, `...stem.pool`), not by call order.
+# Outside the context nothing changes: F.relu / F.max_pool2d / F.dropout exactly as before.
+# ----------------------------------------------------------------------------
+class MaskPins:
+    """masks: site -> multiplicative mask (the ReLU input's shape, NCHW), or (mask, counted) where `counted` (bool) limits the flip
+    count to the positions where the sign decides the mask (the seg head's Dropout zeros are not flips); max-pool sites: site -> window
+    position ky * 3 + kx (int [B, C, Ho, Wo]).  Strict: reaching a site without a mask raises KeyError, and so does leaving the context with
+    a mask that no site consumed.  After the run, `flips[site]` is the number of positions where the supplied mask disagrees with the sign of
+    the pre-activation this run computed (the max-pool: with its own first argmax) and `sizes[site]` the positions counted, `pooled[site]` = (gathered values, window maxima)."""
+
+    def __init__(self, masks: Dict[str, object], record: bool = False):
+        self.record = record      # record_masks(): take the sign / first argmax of this run and store it under the site instead
+        self.masks = dict(masks)
+        self.used: set = set()
+        self.flips: Dict[str, int] = {}
+        self.sizes: Dict[str, int] = {}
+        self.pooled: Dict[str, Tuple[Tensor, Tensor]] = {}
+
+    def _take(self, site: str):
+        if site not in self.masks:
+            raise KeyError(f"mask pinning: no mask for site {site!r}")
+        if site in self.used:
+            raise KeyError(f"mask pinning: site {site!r} reached twice")
+        self.used.add(site)
+        return self.masks[site]
+
+    def relu(self, x: Tensor, site: str) -> Tensor:
+        if self.record:
+            self.masks[site] = x.detach() > 0
+        m = self._take(site)
+        counted = None
+        if isinstance(m, tuple):
+            m, counted = m
+        m = m.to(x.dtype)
+        if m.shape != x.shape:
+            raise ValueError(f"mask pinning: site {site!r} mask {tuple(m.shape)} for input {tuple(x.shape)}")
+        dis = (m > 0) != (x.detach() > 0)
+        if counted is not None:
+            dis = dis & counted
+        self.flips[site] = int(dis.sum())
+        self.sizes[site] = x.numel() if counted is None else int(counted.sum())
+        return x * m
+
+    def max_pool(self, xp: Tensor, site: str) -> Tensor:
+        win = xp.unfold(2, 3, 2).unfold(3, 3, 2)
+        win = win.reshape(*win.shape[:4], 9)
+        if self.record:
+            self.masks[site] = win.detach().argmax(-1)
+        idx = self._take(site)
+        if tuple(idx.shape) != tuple(win.shape[:4]):
+            raise ValueError(f"mask pinning: site {site!r} index {tuple(idx.shape)} for pooled {tuple(win.shape[:4])}")
+        out = win.gather(-1, idx.long().unsqueeze(-1)).squeeze(-1)
+        wd = win.detach()
+        self.flips[site] = int((idx.long() != wd.argmax(-1)).sum())
+        self.sizes[site] = idx.numel()
+        self.pooled[site] = (out.detach(), wd.amax(-1))
+        return out
+
+    def check_consumed(self) -> None:
+        left = sorted(set(self.masks) - self.used)
+        if left:
+            raise KeyError(f"mask pinning: {len(left)} supplied masks were never consumed, e.g. {left[:3]}")
+
+
+_PINS: Optional[MaskPins] = None
+
+
+@contextlib.contextmanager
+def pinned_masks(masks: Dict[str, object]):
+    """Run the oracle with the ReLU / Dropout masks and max-pool positions given by `masks` (see MaskPins); yields the MaskPins."""
+    global _PINS
+    prev, pins = _PINS, MaskPins(masks)
+    _PINS = pins
+    try:
+        yield pins
+    finally:
+        _PINS = prev
+    pins.check_consumed()
+
+
+@contextlib.contextmanager
+def record_masks():
+    """Run the oracle through the pinned path with the masks of its own pre-activations (sign, first argmax); yields the MaskPins whose
+    `masks` then hold them, ready for pinned_masks()."""
+    global _PINS
+    prev, pins = _PINS, MaskPins({}, record=True)
+    _PINS = pins
+    try:
+        yield pins
+    finally:
+        _PINS = prev
+
+
+def _relu(x: Tensor, site: str) -> Tensor:
+    return F.relu(x) if _PINS is None else _PINS.relu(x, site)
+
+
+def _max_pool_same(x: Tensor, site: str) -> Tensor:
+    xp = pad_same(x, 3, 2, value=float("-inf"))
+    return F.max_pool2d(xp, 3, 2) if _PINS is None else _PINS.max_pool(xp, site)
 
 
 # ----------------------------------------------------------------------------
@@ -264,10 +371,10 @@ def std_conv_same(x: Tensor, w: Tensor, stride: int = 1, eps: float = 1e-8) -> T
     return F.conv2d(pad_same(x, k, stride), ws, None, stride, 0)
 
 
-def group_norm_act(x: Tensor, w: Tensor, b: Tensor, relu: bool = True) -> Tensor:
-    """timm GroupNormAct(num_groups=32, eps=1e-5) (+ ReLU)."""
+def group_norm_act(x: Tensor, w: Tensor, b: Tensor, relu: bool = True, site: str = "") -> Tensor:
+    """timm GroupNormAct(num_groups=32, eps=1e-5) (+ ReLU; `site` names it for mask pinning)."""
     y = F.group_norm(x, 32, w, b, 1e-5)
-    return F.relu(y) if relu else y
+    return _relu(y, site) if relu else y
 
 
 def resnetv2_bottleneck(sd, p: str, x: Tensor, stride: int) -> Tensor:
@@ -278,20 +385,20 @@ def resnetv2_bottleneck(sd, p: str, x: Tensor, stride: int) -> Tensor:
         sc = std_conv_same(x, sd[p + "downsample.conv.weight"], stride)
         sc = group_norm_act(sc, sd[p + "downsample.norm.weight"], sd[p + "downsample.norm.bias"], relu=False)
     y = std_conv_same(x, sd[p + "conv1.weight"])
-    y = group_norm_act(y, sd[p + "norm1.weight"], sd[p + "norm1.bias"])
+    y = group_norm_act(y, sd[p + "norm1.weight"], sd[p + "norm1.bias"], site=p + "norm1")
     y = std_conv_same(y, sd[p + "conv2.weight"], stride)
-    y = group_norm_act(y, sd[p + "norm2.weight"], sd[p + "norm2.bias"])
+    y = group_norm_act(y, sd[p + "norm2.weight"], sd[p + "norm2.bias"], site=p + "norm2")
     y = std_conv_same(y, sd[p + "conv3.weight"])
     y = group_norm_act(y, sd[p + "norm3.weight"], sd[p + "norm3.bias"], relu=False)
-    return F.relu(y + sc)
+    return _relu(y + sc, p + "act3")
 
 
 def resnetv2_backbone(sd, p: str, x: Tensor, arch: HybridArch = HYBRID) -> List[Tensor]:
     """timm ResNetV2(layers=(3,4,9), preact=False, stem_type='same', conv_layer=StdConv2dSame(eps=1e-8)): outputs of the three stages
     ([B,256,96,96], [B,512,48,48], [B,1024,24,24] at 384 x 384)."""
     y = std_conv_same(x, sd[p + "stem.conv.weight"], 2)
-    y = group_norm_act(y, sd[p + "stem.norm.weight"], sd[p + "stem.norm.bias"])
-    y = F.max_pool2d(pad_same(y, 3, 2, value=float("-inf")), 3, 2)     # MaxPool2dSame
+    y = group_norm_act(y, sd[p + "stem.norm.weight"], sd[p + "stem.norm.bias"], site=p + "stem.norm")
+    y = _max_pool_same(y, p + "stem.pool")     # MaxPool2dSame
     outs = []
     for s, depth in enumerate(arch.layers):
         for j in range(depth):
@@ -367,9 +474,9 @@ def hybrid_encoder(sd: Dict[str, Tensor], x: Tensor, arch: HybridArch = HYBRID, 
 # ----------------------------------------------------------------------------
 def rcu(sd, pfx, x: Tensor) -> Tensor:
     """ResidualConvUnit_custom (model/blocks.py:391-414), bn=False."""
-    out = F.relu(x)
+    out = _relu(x, pfx + "relu1")
     out = F.conv2d(out, sd[pfx + "conv1.weight"], sd[pfx + "conv1.bias"], padding=1)
-    out = F.relu(out)
+    out = _relu(out, pfx + "relu2")
     out = F.conv2d(out, sd[pfx + "conv2.weight"], sd[pfx + "conv2.bias"], padding=1)
     return out + x
 
@@ -402,9 +509,9 @@ def dpt_decoder(sd, layers: Sequence[Tensor], pfx: str = "depth_net.scratch.") -
     h = F.conv2d(p1, sd[pfx + "output_conv.0.weight"], sd[pfx + "output_conv.0.bias"], padding=1)
     h = F.interpolate(h, scale_factor=2, mode="bilinear", align_corners=True)
     h = F.conv2d(h, sd[pfx + "output_conv.2.weight"], sd[pfx + "output_conv.2.bias"], padding=1)
-    h = F.relu(h)
+    h = _relu(h, pfx + "output_conv.3")
     h = F.conv2d(h, sd[pfx + "output_conv.4.weight"], sd[pfx + "output_conv.4.bias"])
-    h = F.relu(h)
+    h = _relu(h, pfx + "output_conv.5")
     return h.squeeze(1), p1
 
 
@@ -415,9 +522,12 @@ def seg_logits(sd, feats: Tensor, pfx: str = "seg_head.", training: bool = False
     h = F.conv2d(feats, sd[pfx + "0.weight"], padding=1)
     h = F.batch_norm(h, sd[pfx + "1.running_mean"], sd[pfx + "1.running_var"],
                      sd[pfx + "1.weight"], sd[pfx + "1.bias"], training, 0.1, 1e-5)
-    h = F.relu(h)
-    if training and dropout_p > 0.0:
-        h = F.dropout(h, dropout_p, True)
+    if _PINS is not None:
+        h = _relu(h, pfx + "2")     # pinned: one mask (ReLU x Dropout keep / (1 - p)) for both modules
+    else:
+        h = F.relu(h)
+        if training and dropout_p > 0.0:
+            h = F.dropout(h, dropout_p, True)
     return F.conv2d(h, sd[pfx + "4.weight"], sd[pfx + "4.bias"])
 
 
@@ -531,11 +641,11 @@ def points_to_occupancy(points: Tensor, sem: Tensor, cfg: ProjConfig = ProjConfi
 # Whole forward (model/SOccDPT.py:681-685)
 # ----------------------------------------------------------------------------
 def soccdpt_v3_network(sd, x: Tensor, backbone: str = "swin2t16_256", sigmoid: bool = True, training: bool = False,
-                       dropout_p: float = 0.0):
+                       dropout_p: float = 0.0, drop_path=None):
     """Encoder + decoder + heads only: (inv_depth [B,H,W], seg [B,C,H,W], path_1).  training=True: the train-mode forward the
     reference's training loop differentiates (scripts/train_SOccDPT.py:360-393) -- torch autograd over this function is the
-    gradient oracle of tests/test_train_step_gpu.py."""
-    layers = hybrid_encoder(sd, x) if backbone == "vitb_rn50_384" else swin_encoder(sd, x, ARCHS[backbone])
+    gradient oracle of tests/test_train_step_gpu.py.  drop_path: the Swin encoder's DropPath scales (see swin_encoder)."""
+    layers = hybrid_encoder(sd, x) if backbone == "vitb_rn50_384" else swin_encoder(sd, x, ARCHS[backbone], drop_path=drop_path)
     inv, p1 = dpt_decoder(sd, layers)
     seg = seg_head(sd, p1, sigmoid, training=training, dropout_p=dropout_p)
     return inv, seg, p1

@@ -607,15 +607,39 @@ int train_workspace_tensor(Handle& h, int B, const char* name, size_t* byte_offs
         int s2 = -1, j2 = -1;
         if (sscanf(k.c_str() + 10, "%d.%d", &s2, &j2) == 2 && s2 >= 0 && s2 < 4 && j2 >= 0 && j2 < a.depths[s2]) { p = T.blk[s2][j2].dp; n = 2 * (size_t)B; }
     }
+    else if (k == "seg_keep") { p = reinterpret_cast<const float*>(T.keep); n = M1 * F; }   // uint8
+    else if (k.compare(0, 3, "hy.") == 0 && a.hybrid) {
+        const HyTape& Y = T.hy;
+        const int H2 = a.img / 4;
+        if (k == "hy.stem_pool") { p = Y.pool; n = (size_t)B * H2 * H2 * a.stem_ch; }
+        else if (k == "hy.pool_idx") { p = reinterpret_cast<const float*>(Y.pool_idx); n = (size_t)B * H2 * H2 * a.stem_ch; }   // uint8
+        else if (k.compare(0, 6, "hy.blk") == 0) {                    // "hy.blk<i>.t1" / ".t2" / ".out", i in HyTape::blk order
+            int i = -1, used = 0;
+            if (sscanf(k.c_str() + 6, "%d%n", &i, &used) == 1 && i >= 0 && i < (int)Y.blk.size()) {
+                const RnBlkT& b = Y.blk[i];
+                const std::string part = k.substr(6 + used);
+                if (part == ".t1") { p = b.t1; n = (size_t)B * (b.rin + 2) * (b.rin + 2) * b.mid; }
+                else if (part == ".t2") { p = b.t2; n = (size_t)B * b.rout * b.rout * b.mid; }
+                else if (part == ".out") { p = b.out; n = (size_t)B * b.rout * b.rout * b.cout; }
+            }
+        }
+    }
     else {
         for (int l = 0; l < 4 && !p; ++l) {
-            const size_t M = (size_t)B * a.fres(l) * a.fres(l);
+            const int r = a.fres(l);
+            const size_t M = (size_t)B * r * r, Mh = (size_t)B * (r + 2) * (r + 2);
             const std::string sl = std::to_string(l);
             if (k == "lrn_raw" + sl) { p = T.lrn_raw[l]; n = M * F; }
             else if (k == "fusion_out" + sl) { p = T.oc[l]; n = M * F; }
             else if (k == "rcu2_out" + sl) { p = T.u[l]; n = M * F; }
             else if (k == "fused_raw" + sl && l < 3) { p = T.out_raw[l]; n = M * F; }
             else if (k == "d_feat" + sl) { p = T.DF[l]; n = M * a.fdim(l); }
+            // zero-halo images [B][r+2][r+2][C]
+            else if (k == "feat" + sl) { p = T.feat[l]; n = Mh * a.fdim(l); }
+            else if (k == "lrn_relu" + sl) { p = T.lrn_relu[l]; n = Mh * F; }
+            else if (k == "rcu1_mid" + sl && l < 3) { p = T.t1[l]; n = Mh * F; }
+            else if (k == "fused_relu" + sl && l < 3) { p = T.out_relu[l]; n = Mh * F; }
+            else if (k == "rcu2_mid" + sl) { p = T.t2[l]; n = Mh * F; }
         }
     }
     if (!p) return 1;

@@ -586,6 +586,14 @@ class Engine:
         ws = self.train_workspace(B)
         return ws[off.value: off.value + 4 * n.value].view(torch.float32).view(-1, channels)
 
+    def train_bytes(self, B: int, name: str, channels: int) -> torch.Tensor:
+        """A uint8 buffer of the training workspace ("seg_keep", "hy.pool_idx") as a [pixels, channels] view."""
+        off, n = ctypes.c_size_t(), ctypes.c_size_t()
+        if self.L.soccdpt_train_workspace_tensor(self._h, B, name.encode(), ctypes.byref(off), ctypes.byref(n)) != 0:
+            raise KeyError(name)
+        ws = self.train_workspace(B)
+        return ws[off.value: off.value + n.value].view(-1, channels)
+
     def train_forward(self, x: torch.Tensor, inv: torch.Tensor, seg: torch.Tensor, dropout_p: float = 0.1, seed: int = 0):
         B = x.shape[0]
         ws = self.train_workspace(B)
