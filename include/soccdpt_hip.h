@@ -34,8 +34,10 @@ extern "C" {
  *     chain in round 4; soccdpt_prec_calibrate and the precision-map source query are new);
  *   5 round 6 (soccdpt_calib_report gained the hold-out / head-room / per-pixel fields; soccdpt_calib_options, soccdpt_prec_calibrate_ex and
  *     soccdpt_op_window_attention_qkv are new);
- *   6 (soccdpt_igemm_args gained the fused-epilogue fields res2_h .. halo_fmt; soccdpt_op_depth_tail and soccdpt_op_seg_tail are new). */
-#define SOCCDPT_ABI_VERSION 6
+ *   6 (soccdpt_igemm_args gained the fused-epilogue fields res2_h .. halo_fmt; soccdpt_op_depth_tail and soccdpt_op_seg_tail are new);
+ *   7 (occupancy evaluation: soccdpt_occ_pack, soccdpt_occ_points_scratch_bytes / _count / _write and soccdpt_occ_iou_counts are new; nothing
+ *     that existed changed). */
+#define SOCCDPT_ABI_VERSION 7
 
 /* backbone ids: model/loader.py:65-77 (model_type switch), model/blocks.py:59-78 */
 #define SOCCDPT_BACKBONE_SWIN2T16_256 0 /* dpt_swin2_tiny_256 */
@@ -272,6 +274,38 @@ int soccdpt_occ_expand(void* handle, const uint32_t* dev_bits, int B, float* dev
 int soccdpt_occ_zero(void* handle, int B, float* dev_occ, void* stream);
 int soccdpt_occ_set(void* handle, const uint32_t* dev_bits, int B, float* dev_occ, void* stream);
 size_t soccdpt_occ_words(void* handle);
+
+/* ---- occupancy evaluation: consumers of the packed grid (csrc/occ_eval.hip).  No handle: stateless, like soccdpt_metrics_*; the grid
+ * extents, the class count C (1..8) and occupancy_shape are arguments.  Bit layout as above: cell n = row-major index of [g0][g1][g2][C],
+ * class n % C, bit n & 31 of word n >> 5, nwords = (ncell + 31) / 32 words per row; bits at or beyond ncell in a row's last word are written
+ * as 0 by soccdpt_occ_pack and ignored by the readers.  `rows` grids are processed by one call (ground-truth grids are per frame).
+ *
+ * soccdpt_occ_pack: dense [rows][ncell] of f32, u8 (torch.bool / uint8) or i32 (point counts) -> bits [rows][nwords]; a bit is set where
+ *   (float)v >= threshold, or (float)v > threshold with strict != 0 (utils/__init__.py:550 and datasets/bdd_helper.py:340 list with >=,
+ *   bdd_helper.py:357 thresholds the grid with >).  NaN compares false.
+ * soccdpt_occ_points_count: bits [rows][nwords] -> counts[rows][C] (set bits per row and class), total[0] = N (their sum); leaves the write
+ *   offsets in `scratch` (soccdpt_occ_points_scratch_bytes(rows, ncell, C) bytes).  counts / total may be NULL.
+ * soccdpt_occ_points_write: after _count on the same bits and scratch: points [min(N, capacity)][4] f64 rows (x, y, z, class_id) in the order of
+ *   occupancy_grid_to_points (utils/__init__.py:532-568): row after row, inside a row class after class, inside a class ascending cell index
+ *   (np.argwhere order); x = (double)(float)((double)i / grid[0] * (double)occupancy_shape[0]), likewise y, z (bit-equal to numpy's
+ *   (indices / grid_size * occupancy_shape).astype(np.float32) with an f32 occupancy_shape).  Only list rows below `capacity` are written, so a
+ *   caller either reads N back after _count and allocates exactly (two-call form) or passes a capacity of its own and reads N from `total`
+ *   later (no host synchronisation).  dev_class_colors [C][3] u8 and dev_colors [min(N, capacity)][3] u8 are both NULL or both given:
+ *   dev_colors[p] = dev_class_colors[class of row p] (semantic_pc_to_colors_and_pc, utils/__init__.py:571-595).  Deterministic: no atomics.
+ * soccdpt_occ_iou_counts: pred [pred_rows][nwords], gt [rows][nwords] (pred_rows == rows, or 1: one predicted grid against every gt row, the
+ *   model's grid being the union over the batch) -> counts [rows][C][4] u64 = {|pred & gt|, |pred | gt|, |pred|, |gt|} per class. */
+#define SOCCDPT_OCC_F32 0
+#define SOCCDPT_OCC_U8 1
+#define SOCCDPT_OCC_I32 2
+int soccdpt_occ_pack(const void* dev_dense, int dtype, int rows, size_t ncell, float threshold, int strict, uint32_t* dev_bits, void* stream);
+size_t soccdpt_occ_points_scratch_bytes(int rows, size_t ncell, int C);
+int soccdpt_occ_points_count(const uint32_t* dev_bits, int rows, size_t ncell, int C, void* dev_scratch, size_t scratch_bytes, int64_t* dev_counts,
+                             int64_t* dev_total, void* stream);
+int soccdpt_occ_points_write(const uint32_t* dev_bits, int rows, const int32_t* grid, int C, const float* occupancy_shape, const void* dev_scratch,
+                             size_t scratch_bytes, size_t capacity, double* dev_points, const uint8_t* dev_class_colors, uint8_t* dev_colors,
+                             void* stream);
+int soccdpt_occ_iou_counts(const uint32_t* dev_pred_bits, int pred_rows, const uint32_t* dev_gt_bits, int rows, size_t ncell, int C,
+                           uint64_t* dev_counts, void* stream);
 
 /* Number of kernel launches issued by the last soccdpt_network call (diagnostics). */
 int soccdpt_last_launch_count(void* handle);

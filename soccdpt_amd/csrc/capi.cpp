@@ -9,6 +9,7 @@
 #include "calibrate.h"
 #include "train.h"
 #include "kernels.h"
+#include "occ_eval.h"
 
 using namespace soccdpt;
 
@@ -400,6 +401,40 @@ int soccdpt_metrics_iou(const float* dev_pred, const float* dev_gt, int B, int C
     std::string err;
     if (!dev_pred || !dev_gt || !dev_out || !dev_scratch) return fail(nullptr, "soccdpt_metrics_iou: null argument");
     if (launch_iou_metrics(dev_pred, dev_gt, B, C, npix, dev_out, dev_scratch, (hipStream_t)stream, err)) return fail(nullptr, err);
+    return 0;
+}
+
+int soccdpt_occ_pack(const void* dev_dense, int dtype, int rows, size_t ncell, float threshold, int strict, uint32_t* dev_bits, void* stream) {
+    std::string err;
+    if (launch_occ_pack(dev_dense, dtype, rows, ncell, threshold, strict, dev_bits, (hipStream_t)stream, err)) return fail(nullptr, "soccdpt_" + err);
+    return 0;
+}
+
+size_t soccdpt_occ_points_scratch_bytes(int rows, size_t ncell, int C) { return occ_points_scratch_bytes(rows, ncell, C); }
+
+int soccdpt_occ_points_count(const uint32_t* dev_bits, int rows, size_t ncell, int C, void* dev_scratch, size_t scratch_bytes, int64_t* dev_counts,
+                             int64_t* dev_total, void* stream) {
+    std::string err;
+    if (launch_occ_points_count(dev_bits, rows, ncell, C, dev_scratch, scratch_bytes, dev_counts, dev_total, (hipStream_t)stream, err))
+        return fail(nullptr, "soccdpt_" + err);
+    return 0;
+}
+
+int soccdpt_occ_points_write(const uint32_t* dev_bits, int rows, const int32_t* grid, int C, const float* occupancy_shape, const void* dev_scratch,
+                             size_t scratch_bytes, size_t capacity, double* dev_points, const uint8_t* dev_class_colors, uint8_t* dev_colors,
+                             void* stream) {
+    std::string err;
+    if (launch_occ_points_write(dev_bits, rows, grid, C, occupancy_shape, dev_scratch, scratch_bytes, capacity, dev_points, dev_class_colors, dev_colors,
+                                (hipStream_t)stream, err))
+        return fail(nullptr, "soccdpt_" + err);
+    return 0;
+}
+
+int soccdpt_occ_iou_counts(const uint32_t* dev_pred_bits, int pred_rows, const uint32_t* dev_gt_bits, int rows, size_t ncell, int C,
+                           uint64_t* dev_counts, void* stream) {
+    std::string err;
+    if (launch_occ_iou_counts(dev_pred_bits, pred_rows, dev_gt_bits, rows, ncell, C, dev_counts, (hipStream_t)stream, err))
+        return fail(nullptr, "soccdpt_" + err);
     return 0;
 }
 

@@ -15,7 +15,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SOCCDPT_LIB_PATH") or os.path.join(_HERE, "libsoccdpt_hip.so")   # override: A/B of two builds in one GPU call (tools/ab_bench.sh)
 
-ABI_VERSION = 6
+ABI_VERSION = 7
 BACKBONE_IDS = {"swin2t16_256": 0, "swin2b24_384": 1, "vitb_rn50_384": 2}
 PREC_BF16 = 0
 PREC_F32 = 1
@@ -182,6 +182,16 @@ def load_library() -> ctypes.CDLL:
     L.soccdpt_occ_expand.restype = ci
     L.soccdpt_occ_words.argtypes = [vp]
     L.soccdpt_occ_words.restype = cs
+    L.soccdpt_occ_pack.argtypes = [vp, ci, ci, cs, ctypes.c_float, ci, vp, vp]
+    L.soccdpt_occ_pack.restype = ci
+    L.soccdpt_occ_points_scratch_bytes.argtypes = [ci, cs, ci]
+    L.soccdpt_occ_points_scratch_bytes.restype = cs
+    L.soccdpt_occ_points_count.argtypes = [vp, ci, cs, ci, vp, cs, vp, vp, vp]
+    L.soccdpt_occ_points_count.restype = ci
+    L.soccdpt_occ_points_write.argtypes = [vp, ci, ctypes.POINTER(ctypes.c_int32), ci, ctypes.POINTER(ctypes.c_float), vp, cs, cs, vp, vp, vp, vp]
+    L.soccdpt_occ_points_write.restype = ci
+    L.soccdpt_occ_iou_counts.argtypes = [vp, ci, vp, ci, cs, ci, vp, vp]
+    L.soccdpt_occ_iou_counts.restype = ci
     L.soccdpt_last_launch_count.argtypes = [vp]
     L.soccdpt_last_launch_count.restype = ci
     L.soccdpt_launch_counter.argtypes = []

@@ -169,6 +169,17 @@ class SOccDPT(BaseModel):
         # (/root/reference/SOccDPT/model/SOccDPT.py:449-455); a caller that only reads it saves (B - 1) x 25 MB of stores per step.
         return occ.expand(B, -1, -1, -1, -1) if self.share_occupancy_rows else occ
 
+    def occupancy_points(self, class_2_color=None):
+        """The last forward's occupancy grid as the reference's point list (utils/__init__.py:532-568 occupancy_grid_to_points on occupancy[0]):
+        float64 [N,4] rows (x, y, z, class_id) in metres, class-major, straight from the packed bits `last_occ_bits` -- no dense grid is read,
+        so it works the same with share_occupancy_rows=True and under occ_exchange.  With class_2_color also the [N,3] u8 colours."""
+        bits = getattr(self, "last_occ_bits", None)
+        if bits is None:
+            raise RuntimeError("occupancy_points() needs a forward of a model built with compute_occ=True first")
+        from ..utils.occupancy import occupancy_bits_to_points
+        res = occupancy_bits_to_points(bits, self.grid_size, self.scale, num_classes=self.num_classes, class_2_color=class_2_color)
+        return res.points if class_2_color is None else (res.points, res.colors)
+
 
 class SOccDPT_V3(SOccDPT):
     def __init__(self, sigmoid=True, load_depth: str = DEPTH_l39icv3q, **kwargs):

@@ -39,6 +39,8 @@ def build_parser() -> argparse.ArgumentParser:
     parser.add_argument("-ld", "--load_depth", default=None, help="Which depth checkpoint to load")
     parser.add_argument("-ls", "--load_seg", default=None, help="Which seg checkpoint to load")
     parser.add_argument("--camera_intrinsics_yaml", default=None, help="calibration file (default: the synthetic 1920x1080 camera of SURVEY.md 8d)")
+    parser.add_argument("--occupancy", action="store_true", help="also evaluate the semantic occupancy grid on the GPU: 3-D IoU against the ground-truth "
+                        "grid of OccupancyProcessor and the mean length of the occupancy point list (prints IOU_3D / OCC_POINTS)")
     return parser
 
 
@@ -72,6 +74,9 @@ def main(args) -> dict:
     num_classes = 3
     calib = args.camera_intrinsics_yaml or write_synth_calib(os.path.join(tempfile.mkdtemp(), "calib.yaml"))
     model_kwargs = dict(num_classes=num_classes, camera_intrinsics_yaml=calib)
+    occupancy = bool(getattr(args, "occupancy", False))
+    if occupancy:
+        model_kwargs.update(compute_occ=True, share_occupancy_rows=True)
     if args.version == 1:
         model_kwargs["load_depth"] = args.load_depth
         model_kwargs["load_seg"] = args.load_seg
@@ -123,8 +128,32 @@ def main(args) -> dict:
     print(f"A1: {a1:.4f}")
     print(f"A2: {a2:.4f}")
     print(f"A3: {a3:.4f}")
+    result = dict(fps=fps, iou=iou, abs_rel=abs_rel, sq_rel=sq_rel, rmse=rmse, rmse_log=rmse_log, a1=a1, a2=a2, a3=a3)
+    if occupancy:
+        result.update(evaluate_occupancy_set(net, dataset, device))
+        print(f"IOU_3D: {result['iou_3D']:.4f}")
+        print(f"OCC_POINTS: {result['occ_points']:.1f}")
     print("=" * 20)
-    return dict(fps=fps, iou=iou, abs_rel=abs_rel, sq_rel=sq_rel, rmse=rmse, rmse_log=rmse_log, a1=a1, a2=a2, a3=a3)
+    return result
+
+
+def evaluate_occupancy_set(net, dataset, device, point_count_threshold: float = 10.0) -> dict:
+    """Mean 3-D IoU of the model's occupancy grid (packed bits of each forward) against the ground-truth grid OccupancyProcessor builds from the
+    sample's (y_disp, argmax y_seg), and the mean length of the model's occupancy point list -- everything on the GPU."""
+    from ..utils.gt_occupancy import OccupancyProcessor
+    from ..utils.occupancy import occupancy_iou
+    proc = OccupancyProcessor(intrinsic_matrix=net.intrinsic_matrix, height=net.height, width=net.width, grid_size=net.grid_size, scale=net.scale, shift=net.shift,
+                              pc_scale=net.pc_scale, pc_shift=net.pc_shift, point_count_threshold=point_count_threshold, num_classes=net.num_classes,
+                              correction_angle=net.correction_angle)
+    ious, lengths = [], []
+    for batch in dataset:
+        x, y_disp, y_seg = batch[0], batch[3], batch[-1]
+        x = x.to(device=device, dtype=torch.float32)
+        gt = proc.process(y_disp.to(device=device, dtype=torch.float32), y_seg.to(device).argmax(dim=1), want_points=False, want_depth=False)
+        net(x)
+        ious.append(occupancy_iou(net.last_occ_bits, gt["occupancy_grid"], num_classes=net.num_classes)["iou_3D"])
+        lengths.append(net.occupancy_points().shape[0])
+    return dict(iou_3D=float(torch.cat(ious).mean().item()), occ_points=float(np.mean(lengths)))
 
 
 if __name__ == "__main__":

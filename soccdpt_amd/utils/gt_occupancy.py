@@ -4,7 +4,9 @@ numpy on the host (2 M points, ~0.5 s per 1080p frame); here a batch of disparit
 becomes depth, the rotated point cloud and the thresholded counting grid in two launches (csrc/gt_occ.hip).
 
 What stays on the host, outside this boundary: decoding images, `rgb_seg_to_class` (colour -> class id LUT, :10-25) and the
-colourised point cloud / `occupancy_points` list used for visualisation (:320-345, :491-521)."""
+colourised point cloud used for visualisation (:491-521).  The `occupancy_points` list of transform_points_to_occupancy_grid_vect (:339-355)
+is available on request (`want_occupancy_points`, csrc/occ_eval.hip); the un-rotation / un-shift / un-scale that process_frame applies to it
+afterwards for drawing (:500-528, numpy matmuls on the host) is not."""
 from __future__ import annotations
 
 import ctypes
@@ -36,9 +38,13 @@ class OccupancyProcessor:
         Rc = np.array([[math.cos(c), -math.sin(c), 0], [math.sin(c), math.cos(c), 0], [0, 0, 1]])
         self._rot = np.concatenate([Ra.T.reshape(-1), Rb.T.reshape(-1), Rc.T.reshape(-1)]).astype(np.float64)
 
-    def process(self, disparity: torch.Tensor, seg_class: torch.Tensor, want_points: bool = True, want_depth: bool = True) -> Dict[str, Optional[torch.Tensor]]:
+    def process(self, disparity: torch.Tensor, seg_class: torch.Tensor, want_points: bool = True, want_depth: bool = True,
+                want_occupancy_points: bool = False) -> Dict[str, Optional[torch.Tensor]]:
         """disparity [B,H,W] (or [H,W]) float, seg_class same shape integer class ids, both cuda ->
-        depth [B,H,W] f32, points [B,H*W,3] f64, occupancy_grid [B,g0,g1,g2,C] bool, counts [B,g0,g1,g2,C] int32."""
+        depth [B,H,W] f32, points [B,H*W,3] f64, occupancy_grid [B,g0,g1,g2,C] bool, counts [B,g0,g1,g2,C] int32.
+        want_occupancy_points adds `occupancy_points`: a list of B float64 [N_b,4] tensors (x, y, z, class_id), the value
+        transform_points_to_occupancy_grid_vect returns under that key (cells with counts >= point_count_threshold, class-major; bdd_helper.py:339-355),
+        built on the GPU from `counts`.  process_frame's later un-rotate / un-shift / un-scale of that list (:500-528, drawing only) is out of scope."""
         assert disparity.is_cuda, "the HIP path needs cuda tensors (no CPU fallback)"
         if disparity.dim() == 2:
             disparity, seg_class = disparity.unsqueeze(0), seg_class.unsqueeze(0)
@@ -62,4 +68,10 @@ class OccupancyProcessor:
                                         _ptr(counts), _ptr(occ), _stream_ptr(dev))
         if rc != 0:
             raise RuntimeError("soccdpt_gt_occupancy failed: " + L.soccdpt_last_error(None).decode())
-        return dict(depth=depth, points=pts, occupancy_grid=occ.bool(), counts=counts)
+        out = dict(depth=depth, points=pts, occupancy_grid=occ.bool(), counts=counts)
+        if want_occupancy_points:
+            from .occupancy import occupancy_bits_to_points, pack_occupancy
+            bits = pack_occupancy(counts, self.point_count_threshold, strict=False)           # the list uses >=, the grid above >
+            res = occupancy_bits_to_points(bits, g, self.scale, num_classes=self.num_classes, rows=B)
+            out["occupancy_points"] = list(torch.split(res.points, res.counts.sum(dim=1).tolist()))
+        return out
