@@ -150,7 +150,7 @@ struct Handle {
         float drop_path = 0.f;    // were called in between (the reuse_xt staged operands and the DropPath scales belong to the forward)
     } train_key;
     float train_drop_path = 0.f;   // soccdpt_train_set_drop_path: timm drop_path_rate of the Swin-V2 encoder in train mode (0 = off)
-    int train_amp = 0;        // soccdpt_train_set_amp: 16-bit MFMA operands for the gradient GEMMs (f32 accumulate, f32 weights / activations / gradients): 1 bf16, 2 fp16
+    int train_amp = 0;        // soccdpt_train_set_amp: operand format of the gradient GEMMs (f32 accumulate, f32 weights / activations / gradients): 0 f32, 1 bf16, 2 fp16, 3 x3 split-fp16 (train.h OpFmt)
     hipGraph_t graph = nullptr;
     hipGraphExec_t graph_exec = nullptr;
     hipStream_t graph_stream = nullptr;  // capture/replay stream (the caller's may be the legacy null stream, which cannot capture)

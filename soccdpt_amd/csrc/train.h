@@ -1,4 +1,5 @@
-// Launchers of train.hip (backward / train-mode forward kernels, exact f32) and the training entry points of train_step.cpp.
+// Launchers of train.hip (backward / train-mode forward kernels; the staging launchers write the operand format they are given) and the training
+// entry points of train_step.cpp.
 #pragma once
 #include <vector>
 #include "internal.h"
@@ -6,9 +7,16 @@
 
 namespace soccdpt {
 
+// Format of a gradient GEMM's staged operands.  The values are soccdpt_train_set_amp's codes: Handle::train_amp converts with a cast.
+enum class OpFmt : int { F32 = 0, BF16 = 1, F16 = 2, X3 = 3 };   // exact f32, bf16, IEEE fp16, x3 split-fp16 pairs (half16.h: 4 bytes per element)
+constexpr bool op_is16(OpFmt f) { return f == OpFmt::BF16 || f == OpFmt::F16; }
+constexpr size_t op_size(OpFmt f) { return op_is16(f) ? 2 : 4; }                                      // bytes per element
+constexpr int op_cvt_hf(OpFmt f) { return f == OpFmt::X3 ? 3 : f == OpFmt::F16 ? 5 : 0; }             // launch_cvt_bf16's `hf` (kernels.h); F32 has no conversion
+constexpr int op_igemm_f16(OpFmt f) { return f == OpFmt::F16 ? 1 : 0; }                                // IgemmDesc::f16
+
 // Every dgrad weight operand of one backward pass staged by a handful of launches instead of one per layer (round 4: 81 launches, 0.7 ms per bf16-amp step).
-// kind 0: [R][C] -> [C][R] (tr_transpose / tr_transpose16 with Rp = R); kind 1: conv weight [R = N][C][3][3] -> tr_conv_w_dgrad's layout.  Same
-// element conversions as the single forms (fmt: -1 f32, 0 bf16, 1 / 2 fp16, 3 x3), so the staged copies are bit-identical to theirs.
+// kind 0: [R][C] -> [C][R] (tr_transpose with Rp = R); kind 1: conv weight [R = N][C][3][3] -> tr_conv_w_dgrad's layout.  Same element
+// conversions as the single forms, so the staged copies are bit-identical to theirs.
 struct TrBatchEntry {
     const float* src;
     void* dst;
@@ -19,22 +27,17 @@ struct TrBatchTable {
     TrBatchEntry e[kTrBatchMax];
     int n;
 };
-int tr_weight_batch(const TrBatchTable& t, int total_tiles, int fmt, hipStream_t st, std::string& err);
-int tr_transpose(const float* in, float* out, int R, int C, int Rp, hipStream_t st, std::string& err);
-int tr_transpose16(const float* in, uint16_t* out, int R, int C, int Rp, int f16, hipStream_t st, std::string& err);
-int tr_im2colT(const float* halo, float* out, int B, int H, int W, int C, size_t Mp, hipStream_t st, std::string& err);
-int tr_im2colT16(const float* halo, uint16_t* out, int B, int H, int W, int C, size_t Mp, int f16, hipStream_t st, std::string& err);
-int tr_dy_halo_T(const float* dy, void* out, int out16, int B, int r, int N, int margin, int ld, hipStream_t st, std::string& err, int rpp = 0);
+int tr_weight_batch(const TrBatchTable& t, int total_tiles, OpFmt fmt, hipStream_t st, std::string& err);
+int tr_transpose(const float* in, void* out, OpFmt fmt, int R, int C, int Rp, hipStream_t st, std::string& err);
+int tr_im2colT(const float* halo, void* out, OpFmt fmt, int B, int H, int W, int C, size_t Mp, hipStream_t st, std::string& err);
+int tr_dy_halo_T(const float* dy, void* out, OpFmt fmt, int B, int r, int N, int margin, int ld, hipStream_t st, std::string& err, int rpp = 0);
 int tr_x_halo_T_x3(const float* halo, void* out, int B, int r, int C, int col0, int ld, int rpp, hipStream_t st, std::string& err);
-int tr_wgrad_permute9(const float* in, float* out, int N, int C, hipStream_t st, std::string& err);
-int tr_conv_w_dgrad(const float* w, float* out, int N, int C, hipStream_t st, std::string& err);
-int tr_conv_w_dgrad16(const float* w, uint16_t* out, int N, int C, int f16, hipStream_t st, std::string& err);
+int tr_conv_w_dgrad(const float* w, void* out, OpFmt fmt, int N, int C, hipStream_t st, std::string& err);
 int tr_wgrad_permute(const float* in, float* out, int N, int C, hipStream_t st, std::string& err);
 int tr_to_halo(const float* in, float* out, int B, int H, int W, int C, hipStream_t st, std::string& err);
-int tr_to_halo_full(const float* in, void* out, int B, int H, int W, int C, int fmt, hipStream_t st, std::string& err);   // whole image incl. a zero border
-int tr_to_halo16(const float* in, uint16_t* out, int B, int H, int W, int C, int f16, hipStream_t st, std::string& err);
-int tr_from_halo(const float* halo, float* out, int B, int H, int W, int C, int accumulate, hipStream_t st, std::string& err);
-int tr_cvt16_pair(const float* in0, uint16_t* out0, size_t n0, const float* in1, uint16_t* out1, size_t n1, int f16, hipStream_t st, std::string& err);   // f32 -> bf16 / IEEE fp16 of two tensors, one launch
+int tr_to_halo_full(const float* in, void* out, OpFmt fmt, int B, int H, int W, int C, hipStream_t st, std::string& err);   // whole image incl. a zero border
+// f32 -> bf16 / IEEE fp16 / x3 of two tensors, one launch.  Element counts: multiples of 4 (x3: of 16).
+int tr_cvt_pair(const float* in0, void* out0, size_t n0, const float* in1, void* out1, size_t n1, OpFmt fmt, hipStream_t st, std::string& err);
 int tr_colsum(const float* a, const float* b, float* out, float* scratch, size_t M, int N, int accumulate, hipStream_t st, std::string& err);
 int tr_colsum2(const float* a, const float* b, float* out_ab, float* out_a, float* scratch, size_t M, int N, hipStream_t st, std::string& err);   // sum a*b and sum a in one pass
 int tr_axpy(float* y, const float* x, size_t n, hipStream_t st, std::string& err);
@@ -48,7 +51,6 @@ int tr_bn_relu_dropout_fwd(const float* x, const float* stats, const float* gamm
 int tr_bn_relu_dropout_bwd_pre(const float* dout, const float* out, const uint8_t* keep, float* dz, size_t n, float p, hipStream_t st, std::string& err);
 int tr_bn_bwd(const float* dz, const float* x, const float* stats, const float* gamma, const float* dbeta, const float* dgamma, float* dx, size_t M, int C, hipStream_t st, std::string& err);
 int tr_bn_xhat(const float* x, const float* stats, float* xh, size_t M, int C, hipStream_t st, std::string& err);
-int tr_smallk_fwd(const float* x, const float* w, const float* bias, float* out, size_t M, int C, int K, hipStream_t st, std::string& err);
 int tr_smallk_dgrad(const float* dl, const float* w, float* dx, size_t M, int C, int K, hipStream_t st, std::string& err);
 int tr_smallk_wgrad(const float* dl, const float* x, float* dw, float* scratch, size_t M, int C, int K, hipStream_t st, std::string& err);
 int tr_seg_act_bwd(const float* dseg, const float* seg, float* dup, int B, int K, int S, int sigmoid, hipStream_t st, std::string& err);
@@ -60,10 +62,9 @@ int tr_pad_cols(const float* in, float* out, int N, int cin, int cout, hipStream
 int tr_attention_bwd(const float* qkv, const float* attn_out, const float* dO, const float* table, const float* scale, float* dS, float* rowstat, float* dscale_part, float* part, float* dqkv, int B, int res, int ws, int shift, int heads, hipStream_t st, std::string& err);
 // MFMA form of tr_attention_bwd (train_attn.hip): no `part` scratch; rowstat holds {m + ln l, delta}; dscale_part has tr_attention_bwd_mfma_slots(ws) per (window, head)
 int tr_attention_bwd_mfma(const float* qkv, const float* attn_out, const float* dO, const float* table, const float* scale, float* dS, float* rowstat,
-                          float* dscale_part, float* dqkv, int B, int res, int ws, int shift, int heads, hipStream_t st, std::string& err, int op = 0);
+                          float* dscale_part, float* dqkv, int B, int res, int ws, int shift, int heads, hipStream_t st, std::string& err, OpFmt fmt);   // fmt: F32, BF16 or F16 products
 int tr_attention_bwd_mfma_slots(int ws);
-int tr_cvt_x3_pair(const float* in0, void* out0, size_t n0, const float* in1, void* out1, size_t n1, hipStream_t st, std::string& err);   // two f32 -> x3 conversions, one launch
-// Weight gradient from operands as stored (train_wgrad_tn.hip): out[Nout][taps * C] = sum_k A[k][n] B[k + shift(tap)][c], 16-bit operands
+// Weight gradient from operands as stored (train_wgrad_tn.hip): out[Nout][taps * C] = sum_k A[k][n] B[k + shift(tap)][c], 16-bit or x3 operands
 bool tr_wgrad_tn_ok(size_t K, int Nout, int C, int taps);
 // Deferred reduction of the weight-gradient partials (round 6): every tr_wgrad_tn call used to be followed by its own tn_reduce launch -- 74 launches of ~14 us per
 // bf16-amp step whose work is a few hundred KB each.  With a TnDefer the partials of successive calls stay in an arena (bump allocation, flushed when full) and ONE
@@ -76,7 +77,7 @@ struct TnDefer {
     std::vector<TnPending> pend;
 };
 int tn_flush(TnDefer& d, hipStream_t st, std::string& err);
-int tr_wgrad_tn(const uint16_t* A, long ldA, const uint16_t* B, long ldB, size_t K, int Nout, int C, int taps, int rp, int f16, float* part, size_t part_floats,
+int tr_wgrad_tn(const void* A, long ldA, const void* B, long ldB, size_t K, int Nout, int C, int taps, int rp, OpFmt fmt, float* part, size_t part_floats,
                 float* out, hipStream_t st, std::string& err, float* bias_out = nullptr, TnDefer* defer = nullptr, int perm_C = 0);
 int tr_attn_param_grads(float* dS, const float* dscale_part, const float* table, const float* ls, const float* w0, const float* b0, const float* w2, float* dtable, float* dt, float* hid, float* dls, float* dw0, float* db0, float* dw2, int nwin, int ws, int pws, int heads, hipStream_t st, std::string& err, int dscale_slots = 0);
 int tr_drop_path_fill(float* out, int B, float p, unsigned seed, unsigned stream_id, hipStream_t st, std::string& err);
@@ -84,7 +85,28 @@ int tr_scale_rows(const float* in, float* out, const float* scale, size_t M, int
 int tr_unscale_check(float* g, size_t n, float inv_scale, int* found, hipStream_t st, std::string& err);
 int tr_qv_bias_grad(const float* dqkv_bias, float* dq, float* dv, int C, hipStream_t st, std::string& err);
 
-// train_step.cpp: SOccDPT_V3 training step (model/SOccDPT.py:660-685 in train mode + autograd), SOCCDPT_PREC_F32 only
+// train_hybrid.hip: ViT-hybrid encoder (ResNetV2 stem and stages, ViT-B blocks, readout)
+int th_gn_bwd(const float* dout, const float* x, const float* stats, const float* gamma, const float* beta, float* dx, float* dgamma, float* dbeta, float* scratch, int B,
+              int HW, int C, int cpg, int relu, hipStream_t st, std::string& err);
+int th_ws_bwd(const float* dwh, const float* wh, const float* w, float* dw, int Cout, int Cin, int k, int Kpad, float eps, hipStream_t st, std::string& err);
+int th_conv_w_dgrad_tap(const float* wt, float* out, int N, int C, hipStream_t st, std::string& err);
+int th_im2colT_gen(const float* halo, float* out, int B, int Hi, int Ho, int C, int stride, int pad, size_t Mp, hipStream_t st, std::string& err);
+int th_col2im(const float* dcol, float* dx, int B, int Hi, int Ho, int C, int stride, int pad, int accumulate, hipStream_t st, std::string& err);
+int th_stride_gather(const float* in, float* out, int B, int Hi, int Ho, int C, int stride, hipStream_t st, std::string& err);
+int th_stride_scatter_add(const float* dg, float* dx, int B, int Hi, int Ho, int C, int stride, hipStream_t st, std::string& err);
+int th_maxpool_bwd(const float* dpool, const float* raw, const float* stats, const float* gamma, const float* beta, uint8_t* idx, float* dA, int B, int Hi, int C, int cpg,
+                   hipStream_t st, std::string& err);
+int th_readout_cat(const float* tok, float* cat, int B, int NT, int E, hipStream_t st, std::string& err);
+int th_readout_cat_bwd(const float* dcat, float* dtok, int B, int NT, int E, int accumulate, hipStream_t st, std::string& err);
+int th_tokens_to_patches(const float* dtok, float* dpatch, int B, int NT, int E, hipStream_t st, std::string& err);
+size_t th_vit_attention_part_floats(int B, int N, int heads);
+int th_vit_attention_fwd(const float* qkv, float* out, float* rowstat, float* part, int B, int N, int heads, hipStream_t st, std::string& err);
+int th_vit_attention_bwd(const float* qkv, const float* O, const float* dO, const float* rowstat, float* part, float* dqkv, int B, int N, int heads, hipStream_t st,
+                         std::string& err);
+// train_attn.hip: MFMA form of th_vit_attention_bwd without its `part` scratch; fmt: F32, BF16 or F16 products
+int th_vit_attention_bwd_mfma(const float* qkv, const float* O, const float* dO, float* rowstat, float* dqkv, int B, int N, int heads, hipStream_t st, std::string& err, OpFmt fmt);
+
+// train_step.cpp: SOccDPT_V3 training step (model/SOccDPT.py:660-685 in train mode + autograd) on SOCCDPT_PREC_F32 handles; arithmetic by soccdpt_train_set_amp (OpFmt)
 size_t train_workspace_bytes(Handle& h, int B);
 int train_backward_encoder(Handle& h, int B, const float* const* d_feat, void* ws, size_t ws_bytes, hipStream_t st, std::string& err);
 int train_workspace_tensor(Handle& h, int B, const char* name, size_t* byte_offset, size_t* elems);

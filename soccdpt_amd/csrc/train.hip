@@ -19,7 +19,7 @@ namespace {
 
 constexpr float LN100 = 4.605170185988092f;
 
-// staging kernels write f32 or, in the mixed-precision mode (SOCCDPT train amp: bf16 MFMA operands for the gradient GEMMs), bf16
+// staging kernels write the operand format of their gradient GEMM (train.h OpFmt): one output element type per format
 template <typename OT> __device__ __forceinline__ OT cvt_out(float v);
 template <> __device__ __forceinline__ float cvt_out<float>(float v) { return v; }
 template <> __device__ __forceinline__ uint16_t cvt_out<uint16_t>(float v) { return f2h<false>(v); }
@@ -125,15 +125,6 @@ __global__ __launch_bounds__(256) void x_halo_T_kernel(const float* __restrict__
         if (c < C && k < ld) store_out<OT>(out, (size_t)c * ld + k, t[tx][i]);
     }
 }
-// dW slabs [9][N][C] -> parameter layout [N][C][3][3]
-__global__ void wgrad_permute9_kernel(const float* __restrict__ in, float* __restrict__ out, int N, int C) {
-    const size_t n = (size_t)N * C * 9;
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-        const int tap = (int)(i % 9);
-        const size_t r = i / 9;    // n * C + c
-        out[i] = in[(size_t)tap * N * C + r];
-    }
-}
 
 // W [N][C][3][3] -> Wd [C][2-ky][2-kx][N] (tap-major, flipped): Wt operand of the 3x3 dgrad (a convolution of dY with the rotated filter)
 template <typename OT>
@@ -235,19 +226,6 @@ __global__ void to_halo_full8_kernel(const float* __restrict__ in, OT* __restric
 #pragma unroll
             for (int k = 0; k < 8; ++k) out[o + k] = cvt_out<OT>(f[k]);
         }
-    }
-}
-// out[i] (+)= halo interior
-__global__ void from_halo_kernel(const float* __restrict__ halo, float* __restrict__ out, int B, int H, int W, int C, int accumulate) {
-    const size_t n = (size_t)B * H * W * C;
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-        const int c = (int)(i % C);
-        size_t r = i / C;
-        const int x = (int)(r % W);
-        r /= W;
-        const int y = (int)(r % H), b = (int)(r / H);
-        const float v = halo[(((size_t)b * (H + 2) + y + 1) * (W + 2) + x + 1) * C + c];
-        out[i] = accumulate ? out[i] + v : v;
     }
 }
 
@@ -589,19 +567,7 @@ __global__ void bn_xhat_kernel(const float* __restrict__ x, const float* __restr
     }
 }
 
-// Conv2d(C, K, 1) with tiny K (seg head: 3 classes): forward logits[m][k] = x[m][:] . w[k][:] + b[k]; backward dx[m][c] = sum_k dl[m][k] w[k][c]
-__global__ __launch_bounds__(256) void smallk_fwd_kernel(const float* __restrict__ x, const float* __restrict__ w, const float* __restrict__ bias, float* __restrict__ out,
-                                                         size_t M, int C, int K) {
-    const int lane = threadIdx.x & 63;
-    const size_t row = (size_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (row >= M) return;
-    for (int k = 0; k < K; ++k) {
-        float s = 0.f;
-        for (int c = lane; c < C; c += 64) s += x[row * C + c] * w[(size_t)k * C + c];
-        for (int o = 1; o < 64; o <<= 1) s += __shfl_xor(s, o);
-        if (lane == 0) out[row * K + k] = s + (bias ? bias[k] : 0.f);
-    }
-}
+// Conv2d(C, K, 1) with tiny K (seg head: 3 classes), logits[m][k] = x[m][:] . w[k][:] + b[k]: backward dx[m][c] = sum_k dl[m][k] w[k][c]
 __global__ void smallk_dgrad_kernel(const float* __restrict__ dl, const float* __restrict__ w, float* __restrict__ dx, size_t M, int C, int K) {
     const size_t n = M * C;
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
@@ -1220,42 +1186,39 @@ inline unsigned gs_blocks(size_t n) {
 
 #define TK(name) return check_launch(name, err)
 
-int tr_weight_batch(const TrBatchTable& t, int total_tiles, int fmt, hipStream_t st, std::string& err) {
+// The one format dispatch of the staging launchers: calls fn with a value of the kernels' output element type for `fmt`
+template <typename Fn>
+static int with_fmt(OpFmt fmt, const char* who, std::string& err, Fn fn) {
+    switch (fmt) {
+        case OpFmt::F32: fn(float{}); break;
+        case OpFmt::BF16: fn(uint16_t{}); break;
+        case OpFmt::F16: fn(f16raw{}); break;
+        case OpFmt::X3: fn(x3raw{}); break;
+        default: err = std::string(who) + ": unknown operand format"; return 1;
+    }
+    return check_launch(who, err);
+}
+
+int tr_weight_batch(const TrBatchTable& t, int total_tiles, OpFmt fmt, hipStream_t st, std::string& err) {
     if (t.n < 1 || t.n > kTrBatchMax || total_tiles < 1) { err = "weight_batch: bad table"; return 1; }
-    if (fmt == 3) SOCCDPT_LAUNCH(weight_batch_kernel<x3raw>, dim3(total_tiles), dim3(256), 0, st, t);
-    else if (fmt == 1 || fmt == 2) SOCCDPT_LAUNCH(weight_batch_kernel<f16raw>, dim3(total_tiles), dim3(256), 0, st, t);
-    else if (fmt == 0) SOCCDPT_LAUNCH(weight_batch_kernel<uint16_t>, dim3(total_tiles), dim3(256), 0, st, t);
-    else SOCCDPT_LAUNCH(weight_batch_kernel<float>, dim3(total_tiles), dim3(256), 0, st, t);
-    TK("weight_batch");
+    return with_fmt(fmt, "weight_batch", err, [&](auto o) { SOCCDPT_LAUNCH(weight_batch_kernel<decltype(o)>, dim3(total_tiles), dim3(256), 0, st, t); });
 }
-int tr_transpose(const float* in, float* out, int R, int C, int Rp, hipStream_t st, std::string& err) {
-    SOCCDPT_LAUNCH(transpose_kernel<float>, dim3((C + 31) / 32, (Rp + 31) / 32), dim3(256), 0, st, in, out, R, C, Rp);
-    TK("transpose");
+int tr_transpose(const float* in, void* out, OpFmt fmt, int R, int C, int Rp, hipStream_t st, std::string& err) {
+    return with_fmt(fmt, "transpose", err, [&](auto o) {
+        SOCCDPT_LAUNCH(transpose_kernel<decltype(o)>, dim3((C + 31) / 32, (Rp + 31) / 32), dim3(256), 0, st, in, static_cast<decltype(o)*>(out), R, C, Rp);
+    });
 }
-int tr_transpose16(const float* in, uint16_t* out, int R, int C, int Rp, int f16, hipStream_t st, std::string& err) {
-    if (f16 == 3) SOCCDPT_LAUNCH(transpose_kernel<x3raw>, dim3((C + 31) / 32, (Rp + 31) / 32), dim3(256), 0, st, in, reinterpret_cast<x3raw*>(out), R, C, Rp);   // x3: 4 bytes per element
-    else if (f16) SOCCDPT_LAUNCH(transpose_kernel<f16raw>, dim3((C + 31) / 32, (Rp + 31) / 32), dim3(256), 0, st, in, reinterpret_cast<f16raw*>(out), R, C, Rp);
-    else SOCCDPT_LAUNCH(transpose_kernel<uint16_t>, dim3((C + 31) / 32, (Rp + 31) / 32), dim3(256), 0, st, in, out, R, C, Rp);
-    TK("transpose16");
+int tr_im2colT(const float* halo, void* out, OpFmt fmt, int B, int H, int W, int C, size_t Mp, hipStream_t st, std::string& err) {
+    return with_fmt(fmt, "im2colT", err, [&](auto o) {
+        SOCCDPT_LAUNCH(im2colT_kernel<decltype(o)>, dim3((C + 31) / 32, (unsigned)((Mp + 31) / 32), 9), dim3(256), 0, st, halo, static_cast<decltype(o)*>(out), B, H, W, C, Mp);
+    });
 }
-int tr_im2colT(const float* halo, float* out, int B, int H, int W, int C, size_t Mp, hipStream_t st, std::string& err) {
-    SOCCDPT_LAUNCH(im2colT_kernel<float>, dim3((C + 31) / 32, (unsigned)((Mp + 31) / 32), 9), dim3(256), 0, st, halo, out, B, H, W, C, Mp);
-    TK("im2colT");
-}
-int tr_im2colT16(const float* halo, uint16_t* out, int B, int H, int W, int C, size_t Mp, int f16, hipStream_t st, std::string& err) {
-    if (f16 == 3) SOCCDPT_LAUNCH(im2colT_kernel<x3raw>, dim3((C + 31) / 32, (unsigned)((Mp + 31) / 32), 9), dim3(256), 0, st, halo, reinterpret_cast<x3raw*>(out), B, H, W, C, Mp);
-    else if (f16) SOCCDPT_LAUNCH(im2colT_kernel<f16raw>, dim3((C + 31) / 32, (unsigned)((Mp + 31) / 32), 9), dim3(256), 0, st, halo, reinterpret_cast<f16raw*>(out), B, H, W, C, Mp);
-    else SOCCDPT_LAUNCH(im2colT_kernel<uint16_t>, dim3((C + 31) / 32, (unsigned)((Mp + 31) / 32), 9), dim3(256), 0, st, halo, out, B, H, W, C, Mp);
-    TK("im2colT16");
-}
-int tr_dy_halo_T(const float* dy, void* out, int out16, int B, int r, int N, int margin, int ld, hipStream_t st, std::string& err, int rpp) {
+int tr_dy_halo_T(const float* dy, void* out, OpFmt fmt, int B, int r, int N, int margin, int ld, hipStream_t st, std::string& err, int rpp) {
     const dim3 grid((N + 31) / 32, (ld + 31) / 32);
     if (rpp <= 0) rpp = r + 2;
-    if (out16 == 3) SOCCDPT_LAUNCH(dy_halo_T_kernel<x3raw>, grid, dim3(256), 0, st, dy, static_cast<x3raw*>(out), B, r, N, margin, ld, rpp);
-    else if (out16 == 2) SOCCDPT_LAUNCH(dy_halo_T_kernel<f16raw>, grid, dim3(256), 0, st, dy, static_cast<f16raw*>(out), B, r, N, margin, ld, rpp);
-    else if (out16) SOCCDPT_LAUNCH(dy_halo_T_kernel<uint16_t>, grid, dim3(256), 0, st, dy, static_cast<uint16_t*>(out), B, r, N, margin, ld, rpp);
-    else SOCCDPT_LAUNCH(dy_halo_T_kernel<float>, grid, dim3(256), 0, st, dy, static_cast<float*>(out), B, r, N, margin, ld, rpp);
-    TK("dy_halo_T");
+    return with_fmt(fmt, "dy_halo_T", err, [&](auto o) {
+        SOCCDPT_LAUNCH(dy_halo_T_kernel<decltype(o)>, grid, dim3(256), 0, st, dy, static_cast<decltype(o)*>(out), B, r, N, margin, ld, rpp);
+    });
 }
 // x3 only: the pitched transposed halo image of the activation (x_halo_T_kernel)
 int tr_x_halo_T_x3(const float* halo, void* out, int B, int r, int C, int col0, int ld, int rpp, hipStream_t st, std::string& err) {
@@ -1263,47 +1226,24 @@ int tr_x_halo_T_x3(const float* halo, void* out, int B, int r, int C, int col0, 
     SOCCDPT_LAUNCH(x_halo_T_kernel<x3raw>, grid, dim3(256), 0, st, halo, static_cast<x3raw*>(out), B, r, C, col0, ld, rpp);
     TK("x_halo_T_x3");
 }
-int tr_wgrad_permute9(const float* in, float* out, int N, int C, hipStream_t st, std::string& err) {
-    SOCCDPT_LAUNCH(wgrad_permute9_kernel, dim3(gs_blocks((size_t)N * C * 9)), dim3(256), 0, st, in, out, N, C);
-    TK("wgrad_permute9");
-}
-int tr_conv_w_dgrad(const float* w, float* out, int N, int C, hipStream_t st, std::string& err) {
-    SOCCDPT_LAUNCH(conv_w_dgrad_kernel<float>, dim3(gs_blocks((size_t)N * C * 9)), dim3(256), 0, st, w, out, N, C);
-    TK("conv_w_dgrad");
-}
-int tr_conv_w_dgrad16(const float* w, uint16_t* out, int N, int C, int f16, hipStream_t st, std::string& err) {
-    if (f16 == 3) SOCCDPT_LAUNCH(conv_w_dgrad_kernel<x3raw>, dim3(gs_blocks((size_t)N * C * 9)), dim3(256), 0, st, w, reinterpret_cast<x3raw*>(out), N, C);
-    else if (f16) SOCCDPT_LAUNCH(conv_w_dgrad_kernel<f16raw>, dim3(gs_blocks((size_t)N * C * 9)), dim3(256), 0, st, w, reinterpret_cast<f16raw*>(out), N, C);
-    else SOCCDPT_LAUNCH(conv_w_dgrad_kernel<uint16_t>, dim3(gs_blocks((size_t)N * C * 9)), dim3(256), 0, st, w, out, N, C);
-    TK("conv_w_dgrad16");
+int tr_conv_w_dgrad(const float* w, void* out, OpFmt fmt, int N, int C, hipStream_t st, std::string& err) {
+    return with_fmt(fmt, "conv_w_dgrad", err, [&](auto o) {
+        SOCCDPT_LAUNCH(conv_w_dgrad_kernel<decltype(o)>, dim3(gs_blocks((size_t)N * C * 9)), dim3(256), 0, st, w, static_cast<decltype(o)*>(out), N, C);
+    });
 }
 int tr_wgrad_permute(const float* in, float* out, int N, int C, hipStream_t st, std::string& err) {
     SOCCDPT_LAUNCH(wgrad_permute_kernel, dim3(gs_blocks((size_t)N * C * 9)), dim3(256), 0, st, in, out, N, C);
     TK("wgrad_permute");
 }
-int tr_to_halo_full(const float* in, void* out, int B, int H, int W, int C, int fmt, hipStream_t st, std::string& err) {
-    // fmt: 0 f32, 1 bf16, 2 fp16, 3 x3.  Writes the border too (zeros): no memset needed.  C % 8 == 0.
+// Writes the border too (zeros): no memset needed.  C % 8 == 0.
+int tr_to_halo_full(const float* in, void* out, OpFmt fmt, int B, int H, int W, int C, hipStream_t st, std::string& err) {
     if (C % 8) { err = "tr_to_halo_full: C must be a multiple of 8"; return 1; }
     const dim3 g(gs_blocks((size_t)B * (H + 2) * (W + 2) * (C / 8))), b(256);
-    if (fmt == 0) SOCCDPT_LAUNCH(to_halo_full8_kernel<float>, g, b, 0, st, in, static_cast<float*>(out), B, H, W, C);
-    else if (fmt == 1) SOCCDPT_LAUNCH(to_halo_full8_kernel<uint16_t>, g, b, 0, st, in, static_cast<uint16_t*>(out), B, H, W, C);
-    else if (fmt == 2) SOCCDPT_LAUNCH(to_halo_full8_kernel<f16raw>, g, b, 0, st, in, static_cast<f16raw*>(out), B, H, W, C);
-    else SOCCDPT_LAUNCH(to_halo_full8_kernel<x3raw>, g, b, 0, st, in, static_cast<x3raw*>(out), B, H, W, C);
-    return check_launch("to_halo_full", err);
+    return with_fmt(fmt, "to_halo_full", err, [&](auto o) { SOCCDPT_LAUNCH(to_halo_full8_kernel<decltype(o)>, g, b, 0, st, in, static_cast<decltype(o)*>(out), B, H, W, C); });
 }
 int tr_to_halo(const float* in, float* out, int B, int H, int W, int C, hipStream_t st, std::string& err) {
     SOCCDPT_LAUNCH(to_halo_kernel<float>, dim3(gs_blocks((size_t)B * H * W * C)), dim3(256), 0, st, in, out, B, H, W, C);
     TK("to_halo");
-}
-int tr_to_halo16(const float* in, uint16_t* out, int B, int H, int W, int C, int f16, hipStream_t st, std::string& err) {
-    if (f16 == 3) SOCCDPT_LAUNCH(to_halo_kernel<x3raw>, dim3(gs_blocks((size_t)B * H * W * C)), dim3(256), 0, st, in, reinterpret_cast<x3raw*>(out), B, H, W, C);
-    else if (f16) SOCCDPT_LAUNCH(to_halo_kernel<f16raw>, dim3(gs_blocks((size_t)B * H * W * C)), dim3(256), 0, st, in, reinterpret_cast<f16raw*>(out), B, H, W, C);
-    else SOCCDPT_LAUNCH(to_halo_kernel<uint16_t>, dim3(gs_blocks((size_t)B * H * W * C)), dim3(256), 0, st, in, out, B, H, W, C);
-    TK("to_halo16");
-}
-int tr_from_halo(const float* halo, float* out, int B, int H, int W, int C, int accumulate, hipStream_t st, std::string& err) {
-    SOCCDPT_LAUNCH(from_halo_kernel, dim3(gs_blocks((size_t)B * H * W * C)), dim3(256), 0, st, halo, out, B, H, W, C, accumulate);
-    TK("from_halo");
 }
 // scratch: up to 65536 + N floats
 int tr_colsum(const float* a, const float* b, float* out, float* scratch, size_t M, int N, int accumulate, hipStream_t st, std::string& err) {
@@ -1325,21 +1265,19 @@ int tr_colsum2(const float* a, const float* b, float* out_ab, float* out_a, floa
     SOCCDPT_LAUNCH(colsum_final_kernel, dim3((2 * N + 63) / 64), dim3(1024), 0, st, scratch, out_ab, out_a, N, 2 * N, chunks, 0);
     TK("colsum2");
 }
-int tr_cvt_x3_pair(const float* in0, void* out0, size_t n0, const float* in1, void* out1, size_t n1, hipStream_t st, std::string& err) {
-    if ((n0 | n1) % 16) { err = "cvt_x3_pair: x3 tensors are multiples of 16 elements"; return 1; }
+// in1 may be null (n1 = 0).  The x3 kernel and the 16-bit kernel keep their own alignment rules.
+int tr_cvt_pair(const float* in0, void* out0, size_t n0, const float* in1, void* out1, size_t n1, OpFmt fmt, hipStream_t st, std::string& err) {
+    if (fmt != OpFmt::X3 && !op_is16(fmt)) { err = "cvt_pair: the operand format must be bf16, fp16 or x3"; return 1; }
+    if (fmt == OpFmt::X3 && (n0 | n1) % 16) { err = "cvt_pair: x3 tensors are multiples of 16 elements"; return 1; }
+    if ((n0 | n1) % 4) { err = "cvt_pair: element counts must be multiples of 4"; return 1; }
     size_t blocks = ((n0 + n1) / 4 + 255) / 256;
     if (blocks > 2048) blocks = 2048;
-    SOCCDPT_LAUNCH(cvt_x3_pair_kernel, dim3((unsigned)blocks), dim3(256), 0, st, in0, out0, n0, in1, out1, n1);
-    TK("cvt_x3_pair");
-}
-// mode: 0 bf16, 1 fp16 (IEEE, no clamp); in1 may be null (n1 = 0)
-int tr_cvt16_pair(const float* in0, uint16_t* out0, size_t n0, const float* in1, uint16_t* out1, size_t n1, int f16, hipStream_t st, std::string& err) {
-    if ((n0 | n1) % 4) { err = "cvt16_pair: element counts must be multiples of 4"; return 1; }
-    size_t blocks = ((n0 + n1) / 4 + 255) / 256;
-    if (blocks > 2048) blocks = 2048;
-    if (f16) SOCCDPT_LAUNCH(cvt16_pair_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, st, in0, out0, n0, in1, out1, n1);
-    else SOCCDPT_LAUNCH(cvt16_pair_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, st, in0, out0, n0, in1, out1, n1);
-    TK("cvt16_pair");
+    const dim3 g((unsigned)blocks), b(256);
+    uint16_t *const h0 = static_cast<uint16_t*>(out0), *const h1 = static_cast<uint16_t*>(out1);
+    if (fmt == OpFmt::X3) SOCCDPT_LAUNCH(cvt_x3_pair_kernel, g, b, 0, st, in0, out0, n0, in1, out1, n1);
+    else if (fmt == OpFmt::F16) SOCCDPT_LAUNCH(cvt16_pair_kernel<true>, g, b, 0, st, in0, h0, n0, in1, h1, n1);
+    else SOCCDPT_LAUNCH(cvt16_pair_kernel<false>, g, b, 0, st, in0, h0, n0, in1, h1, n1);
+    TK("cvt_pair");
 }
 int tr_axpy(float* y, const float* x, size_t n, hipStream_t st, std::string& err) {
     SOCCDPT_LAUNCH(axpy_kernel, dim3(gs_blocks(n)), dim3(256), 0, st, y, x, n);
@@ -1394,10 +1332,6 @@ int tr_bn_bwd(const float* dz, const float* x, const float* stats, const float* 
 int tr_bn_xhat(const float* x, const float* stats, float* xh, size_t M, int C, hipStream_t st, std::string& err) {
     SOCCDPT_LAUNCH(bn_xhat_kernel, dim3(gs_blocks(M * C)), dim3(256), 0, st, x, stats, xh, M, C);
     TK("bn_xhat");
-}
-int tr_smallk_fwd(const float* x, const float* w, const float* bias, float* out, size_t M, int C, int K, hipStream_t st, std::string& err) {
-    SOCCDPT_LAUNCH(smallk_fwd_kernel, dim3((unsigned)((M + 3) / 4)), dim3(256), 0, st, x, w, bias, out, M, C, K);
-    TK("smallk_fwd");
 }
 int tr_smallk_dgrad(const float* dl, const float* w, float* dx, size_t M, int C, int K, hipStream_t st, std::string& err) {
     SOCCDPT_LAUNCH(smallk_dgrad_kernel, dim3(gs_blocks(M * C)), dim3(256), 0, st, dl, w, dx, M, C, K);

@@ -657,13 +657,13 @@ __global__ __launch_bounds__(256) void vit_attn_bwd_mfma_kernel(const float* __r
 
 template <int WS>
 int launch_ws(const float* qkv, const float* attn_out, const float* dO, const float* table, const float* scale, float* dS, float* rowstat, float* dscale_part,
-              float* dqkv, int B, int res, int shift, int heads, hipStream_t st, int op) {
+              float* dqkv, int B, int res, int shift, int heads, hipStream_t st, OpFmt fmt) {
     constexpr int N = WS * WS, NT = (N + 31) / 32, NOB = (NT + 3) / 4;
     const int nw = res / WS;
     const unsigned blocks = (unsigned)(B * nw * nw * heads * NOB);
 #define ATTN_BWD(P, O) SOCCDPT_LAUNCH((attn_bwd_mfma_kernel<WS, P, O>), dim3(blocks), dim3(256), 0, st, qkv, dO, attn_out, table, scale, rowstat, dS, dscale_part, dqkv, res, shift, heads)
-    if (op == 1) { ATTN_BWD(0, 1); ATTN_BWD(1, 1); }
-    else if (op == 2) { ATTN_BWD(0, 2); ATTN_BWD(1, 2); }
+    if (fmt == OpFmt::BF16) { ATTN_BWD(0, 1); ATTN_BWD(1, 1); }
+    else if (fmt == OpFmt::F16) { ATTN_BWD(0, 2); ATTN_BWD(1, 2); }
     else { ATTN_BWD(0, 0); ATTN_BWD(1, 0); }
 #undef ATTN_BWD
     return 0;
@@ -681,13 +681,14 @@ int tr_attention_bwd_mfma_slots(int ws) {
 // Same contract as tr_attention_bwd (train.hip) without its `part` scratch: dqkv [B*res*res][3C] receives dq | dk | dv, dS [nwin][heads][N][N],
 // rowstat [nwin][heads][N][2] = {m + ln l, delta}, dscale_part [nwin][heads][tr_attention_bwd_mfma_slots(ws)].
 int tr_attention_bwd_mfma(const float* qkv, const float* attn_out, const float* dO, const float* table, const float* scale, float* dS, float* rowstat,
-                          float* dscale_part, float* dqkv, int B, int res, int ws, int shift, int heads, hipStream_t st, std::string& err, int op) {
+                          float* dscale_part, float* dqkv, int B, int res, int ws, int shift, int heads, hipStream_t st, std::string& err, OpFmt fmt) {
+    if (fmt == OpFmt::X3) { err = "attention_bwd_mfma: products are f32, bf16 or fp16"; return 1; }
     if (res % ws) { err = "attention_bwd_mfma: res must be a multiple of the window size"; return 1; }
     switch (ws) {
-        case 8: launch_ws<8>(qkv, attn_out, dO, table, scale, dS, rowstat, dscale_part, dqkv, B, res, shift, heads, st, op); break;
-        case 16: launch_ws<16>(qkv, attn_out, dO, table, scale, dS, rowstat, dscale_part, dqkv, B, res, shift, heads, st, op); break;
-        case 12: launch_ws<12>(qkv, attn_out, dO, table, scale, dS, rowstat, dscale_part, dqkv, B, res, shift, heads, st, op); break;
-        case 24: launch_ws<24>(qkv, attn_out, dO, table, scale, dS, rowstat, dscale_part, dqkv, B, res, shift, heads, st, op); break;
+        case 8: launch_ws<8>(qkv, attn_out, dO, table, scale, dS, rowstat, dscale_part, dqkv, B, res, shift, heads, st, fmt); break;
+        case 16: launch_ws<16>(qkv, attn_out, dO, table, scale, dS, rowstat, dscale_part, dqkv, B, res, shift, heads, st, fmt); break;
+        case 12: launch_ws<12>(qkv, attn_out, dO, table, scale, dS, rowstat, dscale_part, dqkv, B, res, shift, heads, st, fmt); break;
+        case 24: launch_ws<24>(qkv, attn_out, dO, table, scale, dS, rowstat, dscale_part, dqkv, B, res, shift, heads, st, fmt); break;
         default: err = "attention_bwd_mfma: no instantiation for this window size"; return 1;
     }
     const hipError_t e = hipGetLastError();
@@ -697,12 +698,13 @@ int tr_attention_bwd_mfma(const float* qkv, const float* attn_out, const float* 
 
 
 // ViT form: qkv [B*N][3E], O / dO [B*N][E], rowstat B * heads * N * 2 floats of scratch, dqkv [B*N][3E]
-int th_vit_attention_bwd_mfma(const float* qkv, const float* O, const float* dO, float* rowstat, float* dqkv, int B, int N, int heads, hipStream_t st, std::string& err, int op) {
+int th_vit_attention_bwd_mfma(const float* qkv, const float* O, const float* dO, float* rowstat, float* dqkv, int B, int N, int heads, hipStream_t st, std::string& err, OpFmt fmt) {
+    if (fmt == OpFmt::X3) { err = "vit_attention_bwd_mfma: products are f32, bf16 or fp16"; return 1; }
     const int NT = (N + 31) / 32, NOB = (NT + 3) / 4;
     const unsigned blocks = (unsigned)(B * heads * NOB);
 #define VIT_BWD(P, OPV) SOCCDPT_LAUNCH((vit_attn_bwd_mfma_kernel<P, OPV>), dim3(blocks), dim3(256), 0, st, qkv, dO, O, rowstat, dqkv, N, heads)
-    if (op == 1) { VIT_BWD(0, 1); VIT_BWD(1, 1); }
-    else if (op == 2) { VIT_BWD(0, 2); VIT_BWD(1, 2); }
+    if (fmt == OpFmt::BF16) { VIT_BWD(0, 1); VIT_BWD(1, 1); }
+    else if (fmt == OpFmt::F16) { VIT_BWD(0, 2); VIT_BWD(1, 2); }
     else { VIT_BWD(0, 0); VIT_BWD(1, 0); }
 #undef VIT_BWD
     const hipError_t e = hipGetLastError();

@@ -4,6 +4,7 @@
 // from the saved raw convolution output), weight-standardisation backward, strided / 'SAME' convolution plumbing (generalised im2col^T,
 // col2im as a gather), max-pool backward, the ProjectReadout concatenation, global softmax attention backward.
 #include "kernels.h"
+#include "train.h"
 
 namespace soccdpt {
 namespace {

@@ -7,27 +7,6 @@
 #include "train_internal.h"
 
 namespace soccdpt {
-
-// train_hybrid.hip
-int th_gn_bwd(const float* dout, const float* x, const float* stats, const float* gamma, const float* beta, float* dx, float* dgamma, float* dbeta, float* scratch, int B,
-              int HW, int C, int cpg, int relu, hipStream_t st, std::string& err);
-int th_ws_bwd(const float* dwh, const float* wh, const float* w, float* dw, int Cout, int Cin, int k, int Kpad, float eps, hipStream_t st, std::string& err);
-int th_conv_w_dgrad_tap(const float* wt, float* out, int N, int C, hipStream_t st, std::string& err);
-int th_im2colT_gen(const float* halo, float* out, int B, int Hi, int Ho, int C, int stride, int pad, size_t Mp, hipStream_t st, std::string& err);
-int th_col2im(const float* dcol, float* dx, int B, int Hi, int Ho, int C, int stride, int pad, int accumulate, hipStream_t st, std::string& err);
-int th_stride_gather(const float* in, float* out, int B, int Hi, int Ho, int C, int stride, hipStream_t st, std::string& err);
-int th_stride_scatter_add(const float* dg, float* dx, int B, int Hi, int Ho, int C, int stride, hipStream_t st, std::string& err);
-int th_maxpool_bwd(const float* dpool, const float* raw, const float* stats, const float* gamma, const float* beta, uint8_t* idx, float* dA, int B, int Hi, int C, int cpg,
-                   hipStream_t st, std::string& err);
-int th_readout_cat(const float* tok, float* cat, int B, int NT, int E, hipStream_t st, std::string& err);
-int th_readout_cat_bwd(const float* dcat, float* dtok, int B, int NT, int E, int accumulate, hipStream_t st, std::string& err);
-int th_tokens_to_patches(const float* dtok, float* dpatch, int B, int NT, int E, hipStream_t st, std::string& err);
-size_t th_vit_attention_part_floats(int B, int N, int heads);
-int th_vit_attention_fwd(const float* qkv, float* out, float* rowstat, float* part, int B, int N, int heads, hipStream_t st, std::string& err);
-int th_vit_attention_bwd_mfma(const float* qkv, const float* O, const float* dO, float* rowstat, float* dqkv, int B, int N, int heads, hipStream_t st, std::string& err, int op);   // train_attn.hip (op: 0 exact f32, 1 bf16, 2 fp16 products)
-int th_vit_attention_bwd(const float* qkv, const float* O, const float* dO, const float* rowstat, float* part, float* dqkv, int B, int N, int heads, hipStream_t st,
-                         std::string& err);
-
 namespace trn {
 namespace {
 
@@ -67,30 +46,29 @@ int conv_gen_bwd(Ctx& c, const float* dY, const float* Xhalo, const float* Wtap,
         // gradient from the operands as stored in halo pixel order (train_wgrad_tn.hip) -- the path the decoder convolutions take in conv3_bwd, with the
         // tap-major standardised weights of this encoder on both ends.  SOCCDPT_WGRAD_TRANSPOSE=1 keeps the f32 path below.
         static const bool tn_off = getenv("SOCCDPT_WGRAD_TRANSPOSE") != nullptr;
-        const int amp = c.h.train_amp;
+        const OpFmt fmt = amp_fmt(c);
         const int rp = Ho + 2;
         const size_t Kh = (size_t)B * rp * rp, Kp = (Kh + 63) / 64 * 64, mrg = (size_t)rp + 1;
-        if (!tn_off && (amp == 1 || amp == 2) && stride == 1 && pad == 1 && Hi == Ho && N % 128 == 0 && C % 128 == 0 && tr_wgrad_tn_ok(Kp, N, C, 9)) {
-            const int F16 = amp == 2 ? 1 : 0, cvt = F16 ? 5 : 0;
-            uint16_t* h16 = reinterpret_cast<uint16_t*>(T.S_halo);
-            TRY(tr_to_halo_full(dY, h16, B, Ho, Ho, N, 1 + F16, c.st, c.err));
+        if (!tn_off && op_is16(fmt) && stride == 1 && pad == 1 && Hi == Ho && N % 128 == 0 && C % 128 == 0 && tr_wgrad_tn_ok(Kp, N, C, 9)) {
+            const size_t es = op_size(fmt);
+            char* const hS = reinterpret_cast<char*>(T.S_halo);
+            TRY(tr_to_halo_full(dY, hS, fmt, B, Ho, Ho, N, c.st, c.err));
             if (dX_out) {
-                uint16_t* w16 = reinterpret_cast<uint16_t*>(T.S_wt);
                 TRY(th_conv_w_dgrad_tap(Wtap, T.S_dw, N, C, c.st, c.err));                         // [C][9][N] f32, rotated
-                TRY(launch_cvt_bf16(T.S_dw, w16, (size_t)C * 9 * N, cvt, c.st, c.err));
+                TRY(cvt_op(c, T.S_dw, T.S_wt, (size_t)C * 9 * N, fmt));
                 IgemmDesc d;
-                d.X = h16; d.Wt = w16; d.M = (int)Mo; d.N = C; d.Cin = N; d.taps = 9; d.H = Ho; d.W = Ho; d.out_f32 = dX_out;
-                TRY(gemm16(c, d));
+                d.X = hS; d.Wt = T.S_wt; d.M = (int)Mo; d.N = C; d.Cin = N; d.taps = 9; d.H = Ho; d.W = Ho; d.out_f32 = dX_out;
+                TRY(gemm(c, d, fmt));
             }
             if (dWtap_out) {
-                uint16_t* xb = reinterpret_cast<uint16_t*>(T.S_T2);
-                hipError_t e = Kp > Kh ? hipMemsetAsync(h16 + Kh * N, 0, (Kp - Kh) * N * 2, c.st) : hipSuccess;
-                if (e == hipSuccess) e = hipMemsetAsync(xb, 0, mrg * C * 2, c.st);
-                if (e == hipSuccess) e = hipMemsetAsync(xb + (mrg + Kh) * C, 0, (Kp - Kh + mrg) * C * 2, c.st);
+                char* const xS = reinterpret_cast<char*>(T.S_T2);
+                hipError_t e = Kp > Kh ? hipMemsetAsync(hS + Kh * N * es, 0, (Kp - Kh) * N * es, c.st) : hipSuccess;
+                if (e == hipSuccess) e = hipMemsetAsync(xS, 0, mrg * C * es, c.st);
+                if (e == hipSuccess) e = hipMemsetAsync(xS + (mrg + Kh) * C * es, 0, (Kp - Kh + mrg) * C * es, c.st);
                 if (e != hipSuccess) { c.err = std::string("conv_gen_bwd memset: ") + hipGetErrorString(e); return 1; }
-                TRY(launch_cvt_bf16(Xhalo, xb + mrg * C, Kh * C, cvt, c.st, c.err));
+                TRY(cvt_op(c, Xhalo, xS + mrg * C * es, Kh * C, fmt));
                 c.T.xt_tn_src = nullptr;   // S_T2 no longer holds conv3_bwd's staged image
-                TRY(tr_wgrad_tn(h16, N, xb + mrg * C, C, Kp, N, C, 9, rp, F16, T.sk_part, kTrainSkPartFloats, dWtap_out, c.st, c.err));
+                TRY(tr_wgrad_tn(hS, N, xS + mrg * C * es, C, Kp, N, C, 9, rp, fmt, T.sk_part, kTrainSkPartFloats, dWtap_out, c.st, c.err));
             }
             if (db) TRY(tr_colsum(dY, nullptr, db, T.S_col, Mo, N, 0, c.st, c.err));
             return 0;
@@ -107,7 +85,7 @@ int conv_gen_bwd(Ctx& c, const float* dY, const float* Xhalo, const float* Wtap,
             d.X = T.S_halo; d.Wt = T.S_wt; d.M = (int)Mo; d.N = C; d.Cin = N; d.taps = 9; d.H = Ho; d.W = Ho; d.out_f32 = dX_out;
             TRY(gemm(c, d));
         } else {
-            TRY(tr_transpose(Wtap, T.S_wt, N, 9 * C, N, c.st, c.err));   // [9C][N]
+            TRY(tr_transpose(Wtap, T.S_wt, OpFmt::F32, N, 9 * C, N, c.st, c.err));   // [9C][N]
             IgemmDesc d;
             d.X = dY; d.Wt = T.S_wt; d.M = (int)Mo; d.N = 9 * C; d.Cin = N; d.ldx = N; d.out_f32 = T.S_T2;   // dcol [Mo][9][C]
             TRY(gemm(c, d));
@@ -116,11 +94,11 @@ int conv_gen_bwd(Ctx& c, const float* dY, const float* Xhalo, const float* Wtap,
     }
     if (dWtap_out) {
         const int Mp = (int)((Mo + 31) / 32 * 32);
-        TRY(tr_transpose(dY, T.S_T1, (int)Mo, N, Mp, c.st, c.err));
+        TRY(tr_transpose(dY, T.S_T1, OpFmt::F32, (int)Mo, N, Mp, c.st, c.err));
         TRY(th_im2colT_gen(Xhalo, T.S_T2, B, Hi, Ho, C, stride, pad, (size_t)Mp, c.st, c.err));
         IgemmDesc d;
         d.X = T.S_T1; d.Wt = T.S_T2; d.M = N; d.N = 9 * C; d.Cin = Mp; d.ldx = Mp; d.out_f32 = dWtap_out;
-        TRY(gemm_wgrad(c, d, false));   // f32 staging (the strided / weight-standardised convolutions do not take the amp path)
+        TRY(gemm_wgrad(c, d, OpFmt::F32));   // f32 staging (the strided / weight-standardised convolutions do not take the amp path)
     }
     if (db) TRY(tr_colsum(dY, nullptr, db, T.S_col, Mo, N, 0, c.st, c.err));
     return 0;
@@ -407,8 +385,8 @@ int hy_backward(Ctx& c) {
         if (attn_valu) TRY(th_vit_attention_bwd(v.qkv, v.attn, G[0], v.rowstat, Y.attn_part, G[4], B, NT, a.vit_heads, st, err));
         else {
             static const bool attn_f32 = getenv("SOCCDPT_ATTN_BWD_F32") != nullptr;   // A/B: keep the exact products in the amp modes too
-            const int attn_op = (!attn_f32 && (c.h.train_amp == 1 || c.h.train_amp == 2)) ? c.h.train_amp : 0;
-            TRY(th_vit_attention_bwd_mfma(v.qkv, v.attn, G[0], v.rowstat, G[4], B, NT, a.vit_heads, st, err, attn_op));
+            const OpFmt attn_fmt = !attn_f32 && op_is16(amp_fmt(c)) ? amp_fmt(c) : OpFmt::F32;
+            TRY(th_vit_attention_bwd_mfma(v.qkv, v.attn, G[0], v.rowstat, G[4], B, NT, a.vit_heads, st, err, attn_fmt));
         }
         TRY(linear_bwd(c, G[4], v.ln1, c.W(k + "attn.qkv.weight"), Mt, 3 * E, E, G[1], nullptr, c.Gd(k + "attn.qkv.weight"), c.Gd(k + "attn.qkv.bias")));
         TRY(ln_bwd(c, v.xin, c.W(k + "norm1.weight"), G[1], G[0], G[3], Mt, E, c.Gd(k + "norm1.weight"), c.Gd(k + "norm1.bias"), kLnEps));

@@ -115,13 +115,12 @@ struct Ctx {
 
 #define TRY(call) do { if (call) return 1; } while (0)
 
-#define TRY(call) do { if (call) return 1; } while (0)
-
-int gemm(Ctx& c, IgemmDesc d, bool x3 = false);
-// a GEMM of the train-mode FORWARD: exact f32, or -- train amp mode 3 -- its operands converted to x3 into scratch first (outputs stay f32)
+inline OpFmt amp_fmt(const Ctx& c) { return static_cast<OpFmt>(c.h.train_amp); }   // the operand format soccdpt_train_set_amp selected
+int gemm(Ctx& c, IgemmDesc d, OpFmt fmt = OpFmt::F32);   // operands of format fmt, f32 outputs
+// a GEMM of the train-mode FORWARD: exact f32, or -- any train amp mode -- its operands converted to x3 into scratch first (outputs stay f32)
 int gemm_fwd(Ctx& c, IgemmDesc d, size_t x_elems, size_t w_elems);
-int gemm16(Ctx& c, IgemmDesc d);   // 16-bit operands of the amp mode (bf16 / fp16), f32 outputs
-int gemm_wgrad(Ctx& c, IgemmDesc d, bool bf16_operands, bool x3 = false);   // operands as written by the caller's staging kernels
+int gemm_wgrad(Ctx& c, IgemmDesc d, OpFmt fmt);   // operands as written by the caller's staging kernels
+int cvt_op(Ctx& c, const float* in, void* out, size_t n, OpFmt fmt);   // f32 -> bf16 / fp16 / x3 (launch_cvt_bf16)
 int copy_d2d(Ctx& c, void* dst, const void* src, size_t bytes, const char* what);
 // Transposed (Linear / 1x1) or rotated tap-major (3x3) copies of every regularly shaped bound weight in the amp mode's operand format, for the dgrad GEMMs of
 // this backward pass: two or three launches instead of one per layer.  linear_bwd / conv3_bwd use a staged copy when they find one (staged_wt) and stage their

@@ -155,11 +155,13 @@ void carve(const Handle& h, int B, TArena& ar, Tape& T) {
     T.S_cpb = ar.f(a.hybrid ? 64 : (size_t)2 * (2 * a.window - 1) * (2 * a.window - 1) * 512);
 }
 
-// x3: the operands are x3 split-fp16 tensors (train amp mode 3: three fp16 MFMAs per product, f32-grade results; same tile set and
-// split-K decisions as the exact-f32 GEMMs)
-int gemm(Ctx& c, IgemmDesc d, bool x3) {
-    d.f32 = x3 ? 0 : 1;
-    d.x3 = x3 ? 1 : 0;
+// A GEMM over operands of format fmt (f32 outputs).  X3: three fp16 MFMAs per product, f32-grade results; same tile set and split-K decisions
+// as the exact-f32 GEMMs.  BF16 / F16: the igemm's own 16-bit tiles.
+int gemm(Ctx& c, IgemmDesc d, OpFmt fmt) {
+    d.f32 = fmt == OpFmt::F32 ? 1 : 0;
+    d.x3 = fmt == OpFmt::X3 ? 1 : 0;
+    d.f16 = op_igemm_f16(fmt);
+    if (op_is16(fmt)) return launch_igemm(d, c.st, c.err);
     // Small grids with a long K (coarse decoder levels, stage-3 Linear layers, their dgrads): split K like the weight-gradient GEMMs do
     const long tiles = (long)((d.M + 63) / 64) * ((d.N + 63) / 64);
     const long nk = (long)d.taps * d.Cin / 32;
@@ -174,29 +176,33 @@ int gemm(Ctx& c, IgemmDesc d, bool x3) {
     return launch_igemm(d, c.st, c.err);
 }
 
+int cvt_op(Ctx& c, const float* in, void* out, size_t n, OpFmt fmt) {
+    if (fmt == OpFmt::F32) { c.err = "cvt_op: f32 operands are used as stored"; return 1; }
+    return launch_cvt_bf16(in, static_cast<bf16_t*>(out), n, op_cvt_hf(fmt), c.st, c.err);   // fp16: IEEE conversion, an overflow of the scaled gradient becomes inf
+}
+
 // Forward GEMM.  With any train amp mode (the 16-bit modes too: their forward stays f32-grade, so the ReLU masks are those of the f32 step) the operands -- f32 tape tensors and f32 (tap-major) weights -- are converted to the x3 split-fp16
 // format into backward scratch (S_T2 / S_wt, idle during the forward) and the product runs as three fp16 MFMAs per k-step; everything the launch
 // writes stays f32 (out_f32, and out_op as an f32 tensor: out_op_f32), so the tape and the backward are unchanged.  x_elems / w_elems: elements of
 // the X buffer (a halo image counts its border) and of the weight matrix.
 int gemm_fwd(Ctx& c, IgemmDesc d, size_t x_elems, size_t w_elems) {
-    const bool x3 = c.h.train_amp != 0 && d.Cin % 32 == 0 && (d.taps == 9 || d.ldx % 16 == 0) && x_elems % 16 == 0 && w_elems % 16 == 0 && !d.ln_g &&
+    const bool x3 = amp_fmt(c) != OpFmt::F32 && d.Cin % 32 == 0 && (d.taps == 9 || d.ldx % 16 == 0) && x_elems % 16 == 0 && w_elems % 16 == 0 && !d.ln_g &&
                     !d.grp_rows && !d.gather1 && d.stride == 1 && d.pad == 1 && d.in_halo == 1;
     if (!x3) return gemm(c, d);
-    uint16_t* xs = reinterpret_cast<uint16_t*>(c.T.S_T2);
-    uint16_t* wsx = reinterpret_cast<uint16_t*>(c.T.S_wt);
-    TRY(tr_cvt_x3_pair(static_cast<const float*>(d.X), xs, x_elems, static_cast<const float*>(d.Wt), wsx, w_elems, c.st, c.err));
-    d.X = xs; d.Wt = wsx; d.out_op_f32 = 1;
-    return gemm(c, d, true);
+    TRY(tr_cvt_pair(static_cast<const float*>(d.X), c.T.S_T2, x_elems, static_cast<const float*>(d.Wt), c.T.S_wt, w_elems, OpFmt::X3, c.st, c.err));
+    d.X = c.T.S_T2; d.Wt = c.T.S_wt; d.out_op_f32 = 1;
+    return gemm(c, d, OpFmt::X3);
 }
 
 // Weight-gradient GEMM over TRANSPOSED operands: few output tiles, K = pixels.  Split K so that about two workgroups per CU exist; the partial tiles are
 // summed in split order -- by a second launch (sk_defer) for the big tiles and for >= 4 splits, by the last workgroup to arrive otherwise: deterministic
-// either way.  amp: bf16 / fp16 operands (K padded to 128 by the caller).
-int gemm_wgrad(Ctx& c, IgemmDesc d, bool bf16_operands, bool x3) {
-    const bool amp = bf16_operands;   // the CALLER says what its staging kernels wrote (amp applies per GEMM: shapes that do not fit stay f32)
-    d.f32 = (amp || x3) ? 0 : 1;
+// either way.  fmt: what the CALLER's staging kernels wrote (the amp mode applies per GEMM: shapes that do not fit stay f32); 16-bit operands have K padded
+// to 128 by the caller.
+int gemm_wgrad(Ctx& c, IgemmDesc d, OpFmt fmt) {
+    const bool amp = op_is16(fmt), x3 = fmt == OpFmt::X3;
+    d.f32 = fmt == OpFmt::F32 ? 1 : 0;
     d.x3 = x3 ? 1 : 0;
-    d.f16 = c.h.train_amp == 2 ? 1 : 0;   // 16-bit format of the amp mode: bf16 (1) or fp16 with the caller's loss scaling (2)
+    d.f16 = op_igemm_f16(fmt);
     // Tiles.  Default for the wide layers (M, N multiples of 128, >= 8 tiles): the 8-wave 128 x 128 tile -- these launches are L2 -> LDS fill bound and it
     // carries 64 FLOP per staged byte (16-bit) against 21 for 32 x 64 -- with the DEFERRED reduction (igemm.h sk_defer).  Rounds 2 and early 3 measured
     // the big tiles slower (f32 4 waves 51.2 vs 45.2 ms, x3 37.5 vs 36.6 ms per step): that was the last-arriver reduction, one workgroup walking 14
@@ -226,13 +232,6 @@ int gemm_wgrad(Ctx& c, IgemmDesc d, bool bf16_operands, bool x3) {
     return launch_igemm(d, c.st, c.err);
 }
 
-// amp: a backward GEMM with bf16 operands (f32 accumulate, f32 outputs)
-int gemm16(Ctx& c, IgemmDesc d) {
-    d.f32 = 0;
-    d.f16 = c.h.train_amp == 2 ? 1 : 0;
-    return launch_igemm(d, c.st, c.err);
-}
-
 int copy_d2d(Ctx& c, void* dst, const void* src, size_t bytes, const char* what) {
     hipError_t e = hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, c.st);
     if (e != hipSuccess) { c.err = std::string(what) + ": " + hipGetErrorString(e); return 1; }
@@ -256,8 +255,7 @@ int stage_weights(Ctx& c) {
     Tape& T = c.T;
     T.wt_by_ptr.clear();
     if (off || !T.WT) return 0;
-    const int amp = c.h.train_amp;
-    const int fmt = amp == 3 ? 3 : amp == 2 ? 1 : amp == 1 ? 0 : -1;
+    const OpFmt fmt = amp_fmt(c);
     TrBatchTable t;
     t.n = 0;
     int tiles = 0;
@@ -292,102 +290,52 @@ const void* staged_wt(const Ctx& c, const float* W) {
 // y = x W^T + b backward.  dY [M][N], X [M][K], W [N][K].  dX_out = dY W (+ dX_res); dW = dY^T X; db = colsum(dY).
 int linear_bwd(Ctx& c, const float* dY, const float* X, const float* W, size_t M, int N, int K, float* dX_out, const float* dX_res, float* dW, float* db) {
     Tape& T = c.T;
-    const bool x3 = c.h.train_amp == 3 && N % 32 == 0 && K % 32 == 0 && K > 32;              // x3 split-fp16 operands (f32-grade, 4 bytes per element)
-    const bool amp = (c.h.train_amp == 1 || c.h.train_amp == 2) && N % 32 == 0 && K % 4 == 0 && K > 32;   // mixed precision: 16-bit operands for the two gradient GEMMs
-    const int F16 = c.h.train_amp == 2 ? 1 : 0;
-    // Both operand conversions of the layer in ONE launch when the weight gradient takes its operands as stored (wgrad_tn): dY for the two gradient
-    // GEMMs, X for the weight gradient (round 5; two launches of a scalar kernel per layer before)
-    const bool tn16 = amp && dW && wgrad_tn_on() && tr_wgrad_tn_ok((M + 63) / 64 * 64, N, K, 1) && (M * N) % 4 == 0 && (M * K) % 4 == 0;
-    const bool tn3 = x3 && dW && wgrad_tn_on() && tr_wgrad_tn_ok((M + 63) / 64 * 64, N, K, 1);
-    bool staged = false;   // S_T1 holds dY and S_T2 holds X in the launch format
+    // The operand format of the layer's two gradient GEMMs: the amp mode's where the shapes permit it (x3: f32-grade, 4 bytes per element), exact f32 otherwise
+    const OpFmt mode = amp_fmt(c);
+    const bool fits = mode == OpFmt::X3 ? N % 32 == 0 && K % 32 == 0 && K > 32 : N % 32 == 0 && K % 4 == 0 && K > 32;
+    const OpFmt fmt = fits ? mode : OpFmt::F32;
+    const size_t es = op_size(fmt);
+    // Weight gradient from the operands as stored (train_wgrad_tn.hip): no transposes.  Token counts that are not a k-tile multiple (577-token ViT
+    // sequences) get zero rows appended to both operands (zero bytes are x3 zeros too).
+    const size_t Mtn = (M + 63) / 64 * 64;
+    const bool tn = fmt != OpFmt::F32 && dW && wgrad_tn_on() && tr_wgrad_tn_ok(Mtn, N, K, 1);
+    // Both operand conversions of the layer in ONE launch then: dY for the two gradient GEMMs, X for the weight gradient (round 5; two launches of a
+    // scalar kernel per layer before)
+    const bool pair = tn && (fmt == OpFmt::X3 || ((M * N) % 4 == 0 && (M * K) % 4 == 0));
+    char* const yS = reinterpret_cast<char*>(T.S_T1);   // dY and X in the launch format
+    char* const xS = reinterpret_cast<char*>(T.S_T2);
     // a gradient written into scratch (standardised ResNetV2 kernels, the padded patch embedding) is read by its caller's next launch: summed at once; parameter gradients wait for the batched sum
     TnDefer* const df = c.may_defer(dW, bias_in_wgrad() ? db : nullptr) ? &c.tn : nullptr;   // (the qkv bias gradient, e.g., goes through scratch into q_bias / v_bias)
-    if (tn16) { TRY(tr_cvt16_pair(dY, reinterpret_cast<uint16_t*>(T.S_T1), M * N, X, reinterpret_cast<uint16_t*>(T.S_T2), M * K, F16, c.st, c.err)); staged = true; }
-    else if (tn3) { TRY(tr_cvt_x3_pair(dY, T.S_T1, M * N, X, T.S_T2, M * K, c.st, c.err)); staged = true; }
+    if (pair) TRY(tr_cvt_pair(dY, yS, M * N, X, xS, M * K, fmt, c.st, c.err));
     if (dX_out) {
         IgemmDesc d;
         d.M = (int)M; d.N = K; d.Cin = N; d.ldx = N; d.res1 = dX_res; d.out_f32 = dX_out;
-        if (x3) {
-            const void* w3 = staged_wt(c, W);
-            uint16_t* a3 = reinterpret_cast<uint16_t*>(T.S_T1);
-            if (!w3) { TRY(tr_transpose16(W, reinterpret_cast<uint16_t*>(T.S_wt), N, K, N, 3, c.st, c.err)); w3 = T.S_wt; }
-            if (!staged) TRY(launch_cvt_bf16(dY, a3, M * N, 3, c.st, c.err));
-            d.X = a3; d.Wt = w3;
-            TRY(gemm(c, d, true));
-        } else if (amp) {
-            const void* w16 = staged_wt(c, W);
-            uint16_t* a16 = reinterpret_cast<uint16_t*>(T.S_T1);
-            if (!w16) { TRY(tr_transpose16(W, reinterpret_cast<uint16_t*>(T.S_wt), N, K, N, F16, c.st, c.err)); w16 = T.S_wt; }
-            if (!staged) TRY(launch_cvt_bf16(dY, a16, M * N, F16 ? 5 : 0, c.st, c.err));   // fp16: IEEE conversion, an overflow of the scaled gradient becomes inf
-            d.X = a16; d.Wt = w16;
-            TRY(gemm16(c, d));
-        } else {
-            const void* wt = staged_wt(c, W);
-            if (!wt) { TRY(tr_transpose(W, T.S_wt, N, K, N, c.st, c.err)); wt = T.S_wt; }   // [K][N]
-            d.X = dY; d.Wt = wt;
-            TRY(gemm(c, d));
-        }
+        d.Wt = staged_wt(c, W);
+        if (!d.Wt) { TRY(tr_transpose(W, T.S_wt, fmt, N, K, N, c.st, c.err)); d.Wt = T.S_wt; }   // [K][N]
+        if (fmt != OpFmt::F32 && !pair) TRY(cvt_op(c, dY, yS, M * N, fmt));
+        d.X = fmt == OpFmt::F32 ? static_cast<const void*>(dY) : yS;
+        TRY(gemm(c, d, fmt));
     }
-    if (dW) {
-        IgemmDesc d;
-        d.M = N; d.N = K; d.out_f32 = dW;
-        if (x3 && wgrad_tn_on() && tr_wgrad_tn_ok((M + 63) / 64 * 64, N, K, 1)) {
-            // x3 operands as stored (train_wgrad_tn.hip: wgrad_tn_x3_kernel); zero bytes are x3 zeros
-            char* a3 = reinterpret_cast<char*>(T.S_T1);
-            char* x3p = reinterpret_cast<char*>(T.S_T2);
-            const size_t Mp = (M + 63) / 64 * 64;
-            if (!staged) {
-                if (!dX_out) TRY(launch_cvt_bf16(dY, reinterpret_cast<uint16_t*>(a3), M * N, 3, c.st, c.err));
-                TRY(launch_cvt_bf16(X, reinterpret_cast<uint16_t*>(x3p), M * K, 3, c.st, c.err));
-            }
-            if (Mp > M) {
-                hipError_t e = hipMemsetAsync(a3 + M * N * 4, 0, (Mp - M) * N * 4, c.st);
-                if (e == hipSuccess) e = hipMemsetAsync(x3p + M * K * 4, 0, (Mp - M) * K * 4, c.st);
-                if (e != hipSuccess) { c.err = std::string("linear_bwd memset: ") + hipGetErrorString(e); return 1; }
-            }
-            // (the bias gradient = column sums of dY rides in the same launch: one more MFMA per fragment against ones, train_wgrad_tn.hip)
-            TRY(tr_wgrad_tn(reinterpret_cast<uint16_t*>(a3), N, reinterpret_cast<uint16_t*>(x3p), K, Mp, N, K, 1, 0, 3, T.sk_part, kTrainSkPartFloats, dW, c.st, c.err, bias_in_wgrad() ? db : nullptr, df));
-            if (db && !bias_in_wgrad()) TRY(tr_colsum(dY, nullptr, db, T.S_col, M, N, 0, c.st, c.err));
-            return 0;
-        } else if (x3) {
-            const int Mp = (int)((M + 31) / 32 * 32);
-            uint16_t* y3 = reinterpret_cast<uint16_t*>(T.S_T1);
-            uint16_t* x3p = reinterpret_cast<uint16_t*>(T.S_T2);
-            TRY(tr_transpose16(dY, y3, (int)M, N, Mp, 3, c.st, c.err));
-            TRY(tr_transpose16(X, x3p, (int)M, K, Mp, 3, c.st, c.err));
-            d.X = y3; d.Wt = x3p; d.Cin = Mp; d.ldx = Mp;
-        } else if (amp && wgrad_tn_on() && tr_wgrad_tn_ok((M + 63) / 64 * 64, N, K, 1)) {
-            // operands as stored (train_wgrad_tn.hip): dY in 16 bit is what the dgrad launch above already staged; X needs one conversion, no transposes.
-            // Token counts that are not a k-tile multiple (577-token ViT sequences) get zero rows appended to both operands.
-            uint16_t* a16 = reinterpret_cast<uint16_t*>(T.S_T1);
-            uint16_t* x16 = reinterpret_cast<uint16_t*>(T.S_T2);
-            const size_t Mp = (M + 63) / 64 * 64;
-            if (!staged) {
-                if (!dX_out) TRY(launch_cvt_bf16(dY, a16, M * N, F16 ? 5 : 0, c.st, c.err));
-                TRY(launch_cvt_bf16(X, x16, M * K, F16 ? 5 : 0, c.st, c.err));
-            }
-            if (Mp > M) {
-                hipError_t e = hipMemsetAsync(a16 + M * N, 0, (Mp - M) * N * 2, c.st);
-                if (e == hipSuccess) e = hipMemsetAsync(x16 + M * K, 0, (Mp - M) * K * 2, c.st);
-                if (e != hipSuccess) { c.err = std::string("linear_bwd memset: ") + hipGetErrorString(e); return 1; }
-            }
-            TRY(tr_wgrad_tn(a16, N, x16, K, Mp, N, K, 1, 0, F16, T.sk_part, kTrainSkPartFloats, dW, c.st, c.err, bias_in_wgrad() ? db : nullptr, df));
-            if (db && !bias_in_wgrad()) TRY(tr_colsum(dY, nullptr, db, T.S_col, M, N, 0, c.st, c.err));
-            return 0;
-        } else if (amp) {
-            const int Mp = (int)((M + 127) / 128 * 128);
-            uint16_t* y16 = reinterpret_cast<uint16_t*>(T.S_T1);
-            uint16_t* x16 = reinterpret_cast<uint16_t*>(T.S_T2);
-            TRY(tr_transpose16(dY, y16, (int)M, N, Mp, F16, c.st, c.err));
-            TRY(tr_transpose16(X, x16, (int)M, K, Mp, F16, c.st, c.err));
-            d.X = y16; d.Wt = x16; d.Cin = Mp; d.ldx = Mp;
-        } else {
-            const int Mp = (int)((M + 31) / 32 * 32);                    // k-tile multiple; the padding rows are zero
-            TRY(tr_transpose(dY, T.S_T1, (int)M, N, Mp, c.st, c.err));   // [N][Mp]
-            TRY(tr_transpose(X, T.S_T2, (int)M, K, Mp, c.st, c.err));    // [K][Mp]
-            d.X = T.S_T1; d.Wt = T.S_T2; d.Cin = Mp; d.ldx = Mp;
+    if (dW && tn) {
+        if (!pair) {   // dY in the launch format is what the dgrad launch above already staged
+            if (!dX_out) TRY(cvt_op(c, dY, yS, M * N, fmt));
+            TRY(cvt_op(c, X, xS, M * K, fmt));
         }
-        TRY(gemm_wgrad(c, d, amp, x3));
+        if (Mtn > M) {
+            hipError_t e = hipMemsetAsync(yS + M * N * es, 0, (Mtn - M) * N * es, c.st);
+            if (e == hipSuccess) e = hipMemsetAsync(xS + M * K * es, 0, (Mtn - M) * K * es, c.st);
+            if (e != hipSuccess) { c.err = std::string("linear_bwd memset: ") + hipGetErrorString(e); return 1; }
+        }
+        // (the bias gradient = column sums of dY rides in the same launch: one more MFMA per fragment against ones, train_wgrad_tn.hip)
+        TRY(tr_wgrad_tn(yS, N, xS, K, Mtn, N, K, 1, 0, fmt, T.sk_part, kTrainSkPartFloats, dW, c.st, c.err, bias_in_wgrad() ? db : nullptr, df));
+        if (bias_in_wgrad()) db = nullptr;
+    } else if (dW) {
+        const int Mp = (int)(op_is16(fmt) ? (M + 127) / 128 * 128 : (M + 31) / 32 * 32);   // k-tile multiple; the padding rows are zero
+        TRY(tr_transpose(dY, yS, fmt, (int)M, N, Mp, c.st, c.err));   // [N][Mp]
+        TRY(tr_transpose(X, xS, fmt, (int)M, K, Mp, c.st, c.err));    // [K][Mp]
+        IgemmDesc d;
+        d.X = yS; d.Wt = xS; d.M = N; d.N = K; d.Cin = Mp; d.ldx = Mp; d.out_f32 = dW;
+        TRY(gemm_wgrad(c, d, fmt));
     }
     if (db) TRY(tr_colsum(dY, nullptr, db, T.S_col, M, N, 0, c.st, c.err));
     return 0;
@@ -399,149 +347,105 @@ int conv3_bwd(Ctx& c, const float* dY, const float* Xhalo, const float* W, int r
     Tape& T = c.T;
     const int B = c.B;
     const size_t M = (size_t)B * r * r;
-    const bool x3 = c.h.train_amp == 3 && N % 32 == 0 && C % 32 == 0;
-    const bool amp = (c.h.train_amp == 1 || c.h.train_amp == 2) && N % 32 == 0 && C % 32 == 0;
-    const int F16 = c.h.train_amp == 2 ? 1 : 0;
+    const OpFmt fmt = N % 32 == 0 && C % 32 == 0 ? amp_fmt(c) : OpFmt::F32;   // the amp mode's operand format where the shapes permit it
+    const bool x3 = fmt == OpFmt::X3, amp = op_is16(fmt);
+    const size_t es = op_size(fmt);
+    char* const yS = reinterpret_cast<char*>(T.S_T1);
+    char* const xS = reinterpret_cast<char*>(T.S_T2);
+    char* const hS = reinterpret_cast<char*>(T.S_halo);
     if (dX_out) {
-        const bool full = N % 8 == 0;   // the staging kernel writes the zero border itself; otherwise clear the buffer first
-        if (!full) {
-            const size_t hb = (size_t)B * (r + 2) * (r + 2) * N * (amp ? 2 : 4);
-            hipError_t e = hipMemsetAsync(T.S_halo, 0, hb, c.st);
+        if (N % 8 == 0) TRY(tr_to_halo_full(dY, hS, fmt, B, r, r, N, c.st, c.err));   // writes the zero border itself
+        else {                                                                         // (f32 only: the other formats have N % 32 == 0) clear the buffer first
+            hipError_t e = hipMemsetAsync(hS, 0, (size_t)B * (r + 2) * (r + 2) * N * es, c.st);
             if (e != hipSuccess) { c.err = std::string("conv3_bwd memset: ") + hipGetErrorString(e); return 1; }
+            TRY(tr_to_halo(dY, T.S_halo, B, r, r, N, c.st, c.err));
         }
         IgemmDesc d;
         d.M = (int)M; d.N = C; d.Cin = N; d.taps = 9; d.H = r; d.W = r; d.res1 = dX_res; d.out_f32 = dX_out;
-        if (x3) {
-            uint16_t* h3 = reinterpret_cast<uint16_t*>(T.S_halo);
-            const void* w3 = staged_wt(c, W);
-            TRY(tr_to_halo_full(dY, h3, B, r, r, N, 3, c.st, c.err));
-            if (!w3) { TRY(tr_conv_w_dgrad16(W, reinterpret_cast<uint16_t*>(T.S_wt), N, C, 3, c.st, c.err)); w3 = T.S_wt; }
-            d.X = h3; d.Wt = w3;
-            TRY(gemm(c, d, true));
-        } else if (amp) {
-            uint16_t* h16 = reinterpret_cast<uint16_t*>(T.S_halo);
-            const void* w16 = staged_wt(c, W);
-            TRY(tr_to_halo_full(dY, h16, B, r, r, N, 1 + F16, c.st, c.err));
-            if (!w16) { TRY(tr_conv_w_dgrad16(W, reinterpret_cast<uint16_t*>(T.S_wt), N, C, F16, c.st, c.err)); w16 = T.S_wt; }
-            d.X = h16; d.Wt = w16;
-            TRY(gemm16(c, d));
-        } else {
-            if (full) TRY(tr_to_halo_full(dY, T.S_halo, B, r, r, N, 0, c.st, c.err));
-            else TRY(tr_to_halo(dY, T.S_halo, B, r, r, N, c.st, c.err));
-            const void* wt = staged_wt(c, W);
-            if (!wt) { TRY(tr_conv_w_dgrad(W, T.S_wt, N, C, c.st, c.err)); wt = T.S_wt; }   // [C][9][N], rotated
-            d.X = T.S_halo; d.Wt = wt;
-            TRY(gemm(c, d));
-        }
+        d.X = hS; d.Wt = staged_wt(c, W);
+        if (!d.Wt) { TRY(tr_conv_w_dgrad(W, T.S_wt, fmt, N, C, c.st, c.err)); d.Wt = T.S_wt; }   // [C][9][N], rotated
+        TRY(gemm(c, d, fmt));
     }
-    if (dW && (amp || x3) && wgrad_tn_on() && tr_wgrad_tn_ok((size_t)((size_t)B * (r + 2) * (r + 2) + 63) / 64 * 64, N, C, 9)) {
-        // Operands as stored, in halo pixel order (train_wgrad_tn.hip): A = dY as the zero-bordered 16-bit image the dgrad launch staged, B = the input's halo image
-        // converted to 16 bit; tap (ky, kx) reads B (ky - 1)(r + 2) + (kx - 1) rows further on.  K is padded to a k-tile with zero rows of A; B gets
+    if (dW && fmt != OpFmt::F32 && wgrad_tn_on() && tr_wgrad_tn_ok((size_t)((size_t)B * (r + 2) * (r + 2) + 63) / 64 * 64, N, C, 9)) {
+        // Operands as stored, in halo pixel order (train_wgrad_tn.hip): A = dY as the zero-bordered image the dgrad launch staged, B = the input's halo image
+        // converted to the operand format; tap (ky, kx) reads B (ky - 1)(r + 2) + (kx - 1) rows further on.  K is padded to a k-tile with zero rows of A; B gets
         // zero margins of r + 3 rows on both sides (border pixels of A are zero, but 0 * NaN is not).
         const int rp = r + 2;
         const size_t Kh = (size_t)B * rp * rp, Kp = (Kh + 63) / 64 * 64, mrg = (size_t)rp + 1;
-        const size_t es = x3 ? 4 : 2;                              // bytes per operand element
-        const int fmt = x3 ? 3 : 1 + F16, cvt = x3 ? 3 : (F16 ? 5 : 0);
-        char* h16 = reinterpret_cast<char*>(T.S_halo);
-        char* xb = reinterpret_cast<char*>(T.S_T2);
-        if (!dX_out) TRY(tr_to_halo_full(dY, h16, B, r, r, N, fmt, c.st, c.err));
-        hipError_t e = Kp > Kh ? hipMemsetAsync(h16 + Kh * N * es, 0, (Kp - Kh) * N * es, c.st) : hipSuccess;
+        if (!dX_out) TRY(tr_to_halo_full(dY, hS, fmt, B, r, r, N, c.st, c.err));
+        hipError_t e = Kp > Kh ? hipMemsetAsync(hS + Kh * N * es, 0, (Kp - Kh) * N * es, c.st) : hipSuccess;
         if (!reuse_xt || T.xt_tn_src != Xhalo) {
             T.xt_tn_src = Xhalo;
-            if (e == hipSuccess) e = hipMemsetAsync(xb, 0, mrg * C * es, c.st);
-            if (e == hipSuccess) e = hipMemsetAsync(xb + (mrg + Kh) * C * es, 0, (Kp - Kh + mrg) * C * es, c.st);
-            if (e == hipSuccess) TRY(launch_cvt_bf16(Xhalo, reinterpret_cast<uint16_t*>(xb + mrg * C * es), Kh * C, cvt, c.st, c.err));
+            if (e == hipSuccess) e = hipMemsetAsync(xS, 0, mrg * C * es, c.st);
+            if (e == hipSuccess) e = hipMemsetAsync(xS + (mrg + Kh) * C * es, 0, (Kp - Kh + mrg) * C * es, c.st);
+            if (e == hipSuccess) TRY(cvt_op(c, Xhalo, xS + mrg * C * es, Kh * C, fmt));
         }
         if (e != hipSuccess) { c.err = std::string("conv3_bwd memset: ") + hipGetErrorString(e); return 1; }
-        if (C % 4 == 0 && c.may_defer(dW, bias_in_wgrad() ? db : nullptr)) {   // deferred: the batched sum writes the parameter layout itself
-            TRY(tr_wgrad_tn(reinterpret_cast<uint16_t*>(h16), N, reinterpret_cast<uint16_t*>(xb + mrg * C * es), C, Kp, N, C, 9, rp, x3 ? 3 : F16, T.sk_part, kTrainSkPartFloats,
-                            dW, c.st, c.err, bias_in_wgrad() ? db : nullptr, &c.tn, C));
+        float* const bias = bias_in_wgrad() ? db : nullptr;   // dY in halo order: its zero border adds nothing to the column sums
+        if (C % 4 == 0 && c.may_defer(dW, bias)) {            // deferred: the batched sum writes the parameter layout itself
+            TRY(tr_wgrad_tn(hS, N, xS + mrg * C * es, C, Kp, N, C, 9, rp, fmt, T.sk_part, kTrainSkPartFloats, dW, c.st, c.err, bias, &c.tn, C));
         } else {
-        TRY(tr_wgrad_tn(reinterpret_cast<uint16_t*>(h16), N, reinterpret_cast<uint16_t*>(xb + mrg * C * es), C, Kp, N, C, 9, rp, x3 ? 3 : F16, T.sk_part, kTrainSkPartFloats,
-                        T.S_dw, c.st, c.err, bias_in_wgrad() ? db : nullptr));   // dY in halo order: its zero border adds nothing to the column sums
-        TRY(tr_wgrad_permute(T.S_dw, dW, N, C, c.st, c.err));
+            TRY(tr_wgrad_tn(hS, N, xS + mrg * C * es, C, Kp, N, C, 9, rp, fmt, T.sk_part, kTrainSkPartFloats, T.S_dw, c.st, c.err, bias));
+            TRY(tr_wgrad_permute(T.S_dw, dW, N, C, c.st, c.err));
         }
         if (bias_in_wgrad()) db = nullptr;
     } else if (dW && x3 && C % 64 == 0) {
-        // x3, no im2col: like the f32 form below, but an x3 tensor is cut in 8-element units, so the views must start at multiples of 16 elements:
+        // x3 only, no im2col: like the shifted views below, but an x3 tensor is cut in 8-element units, so the views must start at multiples of 16 elements:
         // the pixel order pads every halo row to rpp = roundup(r + 2, 16) pixels (vertical taps = +- rpp) and the horizontal taps read three copies
         // of the transposed image pre-shifted by -1 / 0 / +1 pixel (x_halo_T_kernel).  9 views of 3 copies instead of a 9-fold im2col^T.
         const int rp = r + 2, rpp = (rp + 15) / 16 * 16, Mh = B * rp * rpp, margin = rpp + 16;
         const int ld = (2 * margin + Mh + 31) / 32 * 32;
         const size_t head = (size_t)rpp + 16;                        // zeroed elements in front of and behind each copy (the +- rpp views)
         const size_t copy_elems = (size_t)C * ld + 2 * head;
-        char* yT = reinterpret_cast<char*>(T.S_T1);
-        char* xT = reinterpret_cast<char*>(T.S_T2);
-        TRY(tr_dy_halo_T(dY, yT, 3, B, r, N, margin, ld, c.st, c.err, rpp));
+        TRY(tr_dy_halo_T(dY, yS, fmt, B, r, N, margin, ld, c.st, c.err, rpp));
         if (!reuse_xt || T.xt_tn_src) {
             T.xt_tn_src = nullptr;
             for (int kx = 0; kx < 3; ++kx) {
-                char* base = xT + (size_t)kx * copy_elems * 4;
-                hipError_t e = hipMemsetAsync(base, 0, head * 4, c.st);
-                if (e == hipSuccess) e = hipMemsetAsync(base + (head + (size_t)C * ld) * 4, 0, head * 4, c.st);
+                char* base = xS + (size_t)kx * copy_elems * es;
+                hipError_t e = hipMemsetAsync(base, 0, head * es, c.st);
+                if (e == hipSuccess) e = hipMemsetAsync(base + (head + (size_t)C * ld) * es, 0, head * es, c.st);
                 if (e != hipSuccess) { c.err = std::string("conv3_bwd memset: ") + hipGetErrorString(e); return 1; }
-                TRY(tr_x_halo_T_x3(Xhalo, base + head * 4, B, r, C, margin - (kx - 1), ld, rpp, c.st, c.err));
+                TRY(tr_x_halo_T_x3(Xhalo, base + head * es, B, r, C, margin - (kx - 1), ld, rpp, c.st, c.err));
             }
         }
         IgemmDesc d;
-        d.X = yT; d.Wt = xT; d.M = N; d.N = 9 * C; d.Cin = ld; d.ldx = ld; d.out_f32 = T.S_dw;
+        d.X = yS; d.Wt = xS; d.M = N; d.N = 9 * C; d.Cin = ld; d.ldx = ld; d.out_f32 = T.S_dw;
         d.wt_grp_rows = C; d.wt_rp = rpp; d.wt_base = (int)head; d.wt_kx = (int)copy_elems;
-        TRY(gemm_wgrad(c, d, false, true));
+        TRY(gemm_wgrad(c, d, fmt));
         TRY(tr_wgrad_permute(T.S_dw, dW, N, C, c.st, c.err));
     } else if (dW && (C % 64 != 0 || x3)) {   // (layer1_rn of tiny_256, C = 96: a weight tile would straddle two taps) explicit im2col^T
+        const int Mp = (int)(amp ? (M + 127) / 128 * 128 : (M + 31) / 32 * 32);
+        TRY(tr_transpose(dY, yS, fmt, (int)M, N, Mp, c.st, c.err));             // [N][Mp]
+        TRY(tr_im2colT(Xhalo, xS, fmt, B, r, r, C, (size_t)Mp, c.st, c.err));   // [9C][Mp]
         IgemmDesc d;
-        d.M = N; d.N = 9 * C; d.out_f32 = T.S_dw;
-        if (x3) {
-            const int Mp = (int)((M + 31) / 32 * 32);
-            uint16_t* y3 = reinterpret_cast<uint16_t*>(T.S_T1);
-            uint16_t* x3p = reinterpret_cast<uint16_t*>(T.S_T2);
-            TRY(tr_transpose16(dY, y3, (int)M, N, Mp, 3, c.st, c.err));
-            TRY(tr_im2colT16(Xhalo, x3p, B, r, r, C, (size_t)Mp, 3, c.st, c.err));
-            d.X = y3; d.Wt = x3p; d.Cin = Mp; d.ldx = Mp;
-        } else if (amp) {
-            const int Mp = (int)((M + 127) / 128 * 128);
-            uint16_t* y16 = reinterpret_cast<uint16_t*>(T.S_T1);
-            uint16_t* x16 = reinterpret_cast<uint16_t*>(T.S_T2);
-            TRY(tr_transpose16(dY, y16, (int)M, N, Mp, F16, c.st, c.err));
-            TRY(tr_im2colT16(Xhalo, x16, B, r, r, C, (size_t)Mp, F16, c.st, c.err));
-            d.X = y16; d.Wt = x16; d.Cin = Mp; d.ldx = Mp;
-        } else {
-            const int Mp = (int)((M + 31) / 32 * 32);
-            TRY(tr_transpose(dY, T.S_T1, (int)M, N, Mp, c.st, c.err));             // [N][Mp]
-            TRY(tr_im2colT(Xhalo, T.S_T2, B, r, r, C, (size_t)Mp, c.st, c.err));   // [9C][Mp]
-            d.X = T.S_T1; d.Wt = T.S_T2; d.Cin = Mp; d.ldx = Mp;
-        }
-        TRY(gemm_wgrad(c, d, amp, x3));
+        d.X = yS; d.Wt = xS; d.M = N; d.N = 9 * C; d.Cin = Mp; d.ldx = Mp; d.out_f32 = T.S_dw;
+        TRY(gemm_wgrad(c, d, fmt));
         TRY(tr_wgrad_permute(T.S_dw, dW, N, C, c.st, c.err));
     } else if (dW) {
-        // No im2col: both operands transposed in halo pixel order, tap (ky, kx) = the plain GEMM over a shifted view of the ONE transposed halo
+        // f32 and 16-bit, no im2col: both operands transposed in halo pixel order, tap (ky, kx) = the plain GEMM over a shifted view of the ONE transposed halo
         // image (train.hip: dy_halo_T_kernel).  Margins of r + 3 zero columns on both sides of every row absorb the shifts.
         const int rp = r + 2, Mh = B * rp * rp, margin = r + 3;
         const int ld = (2 * margin + Mh + 127) / 128 * 128;
-        const size_t esz = amp ? 2 : 4;
-        char* yT = reinterpret_cast<char*>(T.S_T1);
-        char* xT = reinterpret_cast<char*>(T.S_T2);            // amp: two copies, shifted by 0 / 1 element, so that every tap's base stays 4-byte aligned
         const size_t head = (size_t)(margin + 13) / 8 * 8;     // zeroed elements in FRONT of each copy: the most negative shift reads base - (r + 4)
-        const size_t copy_bytes = ((size_t)(C + 1) * ld + 64 + head) * esz;
-        xT += head * esz;
-        TRY(tr_dy_halo_T(dY, yT, amp ? 1 + F16 : 0, B, r, N, margin, ld, c.st, c.err));
+        const size_t copy_bytes = ((size_t)(C + 1) * ld + 64 + head) * es;
+        char* const xT = xS + head * es;                       // 16-bit only: two copies, shifted by 0 / 1 element, so that every tap's base stays 4-byte aligned
+        TRY(tr_dy_halo_T(dY, yS, fmt, B, r, N, margin, ld, c.st, c.err));
         if (!reuse_xt || T.xt_tn_src) {
             T.xt_tn_src = nullptr;
             for (int cp = 0; cp < (amp ? 2 : 1); ++cp) {
                 char* base = xT + cp * copy_bytes;
                 // headroom + the first row's left margin; every other gap is the zero tail of a row (tr_transpose pads rows up to ld)
-                hipError_t e = hipMemsetAsync(base - head * esz, 0, (head + margin) * esz, c.st);
+                hipError_t e = hipMemsetAsync(base - head * es, 0, (head + margin) * es, c.st);
                 if (e != hipSuccess) { c.err = std::string("conv3_bwd memset: ") + hipGetErrorString(e); return 1; }
-                if (amp) TRY(tr_transpose16(Xhalo, reinterpret_cast<uint16_t*>(base) + margin - cp, Mh, C, ld, F16, c.st, c.err));
-                else TRY(tr_transpose(Xhalo, reinterpret_cast<float*>(base) + margin, Mh, C, ld, c.st, c.err));
+                TRY(tr_transpose(Xhalo, base + (margin - cp) * es, fmt, Mh, C, ld, c.st, c.err));
             }
         }
         {   // ONE GEMM: M = N out-channels, N = 9 groups of C rows of the weight operand (one shifted view per tap), K = ld halo-order pixels
             IgemmDesc d;
-            d.X = yT; d.Wt = xT - head * esz; d.M = N; d.N = 9 * C; d.Cin = ld; d.ldx = ld; d.out_f32 = T.S_dw;
+            d.X = yS; d.Wt = xS; d.M = N; d.N = 9 * C; d.Cin = ld; d.ldx = ld; d.out_f32 = T.S_dw;
             d.wt_grp_rows = C; d.wt_rp = rp; d.wt_base = (int)head;
-            d.wt_odd = amp ? (int)(copy_bytes / esz) - 1 : 0;   // amp: taps with kx != 1 read copy 1 (x[k + 1] at k) so that every base stays 4-byte aligned
-            TRY(gemm_wgrad(c, d, amp));
+            d.wt_odd = amp ? (int)(copy_bytes / es) - 1 : 0;   // 16-bit: taps with kx != 1 read copy 1 (x[k + 1] at k) so that every base stays 4-byte aligned
+            TRY(gemm_wgrad(c, d, fmt));
         }
         TRY(tr_wgrad_permute(T.S_dw, dW, N, C, c.st, c.err));
     }
@@ -876,9 +780,9 @@ static int encoder_backward(Ctx& c) {
             static const bool attn_valu = getenv("SOCCDPT_ATTN_BWD_VALU") != nullptr;
             // amp modes: the four products of the attention backward on 16-bit MFMAs too (autocast semantics); SOCCDPT_ATTN_BWD_F32=1 keeps them exact (A/B)
             static const bool attn_f32 = getenv("SOCCDPT_ATTN_BWD_F32") != nullptr;
-            const int attn_op = (!attn_f32 && (c.h.train_amp == 1 || c.h.train_amp == 2)) ? c.h.train_amp : 0;
+            const OpFmt attn_fmt = !attn_f32 && op_is16(amp_fmt(c)) ? amp_fmt(c) : OpFmt::F32;
             const int dslots = attn_valu ? 0 : tr_attention_bwd_mfma_slots(wsz);
-            if (dslots) TRY(tr_attention_bwd_mfma(b.qkv, b.attn, G[2], b.table, b.scale, T.dS, T.rowstat, T.dscale_part, G[4], B, res, wsz, a.shift(s, j), H, st, err, attn_op));
+            if (dslots) TRY(tr_attention_bwd_mfma(b.qkv, b.attn, G[2], b.table, b.scale, T.dS, T.rowstat, T.dscale_part, G[4], B, res, wsz, a.shift(s, j), H, st, err, attn_fmt));
             else TRY(tr_attention_bwd(b.qkv, b.attn, G[2], b.table, b.scale, T.dS, T.rowstat, T.dscale_part, T.attn_part, G[4], B, res, wsz, a.shift(s, j), H, st, err));
             {
                 float* dls = c.Gd(k + "attn.logit_scale");

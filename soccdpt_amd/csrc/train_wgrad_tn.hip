@@ -359,16 +359,17 @@ bool tr_wgrad_tn_ok(size_t K, int Nout, int C, int taps) {
     return taps == 1 && Nout % 32 == 0 && C % 32 == 0;         // edge tiles are masked (the operands are over-read by up to 127 columns: callers keep them inside scratch)
 }
 
-// out [Nout][taps * C] f32 (tap-major for taps == 9).  A = dY [K][ldA] and B = X [K][ldB] are 16-bit (bf16, or fp16 when f16 == 1) or x3 tensors (f16 == 3); for taps == 9 both are
+// out [Nout][taps * C] f32 (tap-major for taps == 9).  A = dY [K][ldA] and B = X [K][ldB] are bf16, fp16 or x3 tensors (fmt); for taps == 9 both are
 // in halo pixel order with pitch rp and B must be readable (finite) from row -(rp + 1) to row K + rp: zero margins.  part: at least
 // splits * Nout * taps * C floats.  Returns the number of splits used through *splits_out.
-int tr_wgrad_tn(const uint16_t* A, long ldA, const uint16_t* B, long ldB, size_t K, int Nout, int C, int taps, int rp, int f16, float* part, size_t part_floats,
+int tr_wgrad_tn(const void* A, long ldA, const void* B, long ldB, size_t K, int Nout, int C, int taps, int rp, OpFmt fmt, float* part, size_t part_floats,
                 float* out, hipStream_t st, std::string& err, float* bias_out, TnDefer* defer, int perm_C) {
     if (!tr_wgrad_tn_ok(K, Nout, C, taps)) { err = "wgrad_tn: unsupported shape"; return 1; }
-    const bool x3 = f16 == 3;   // x3 operands: 4 bytes per element, rows start at multiples of 16 elements, 32-row k-tiles
+    if (fmt == OpFmt::F32) { err = "wgrad_tn: the operand format must be bf16, fp16 or x3"; return 1; }
+    const bool x3 = fmt == OpFmt::X3;   // x3 operands: 4 bytes per element, rows start at multiples of 16 elements, 32-row k-tiles
     if (x3 ? ((ldA & 15) || (ldB & 15)) : ((ldA & 7) || (ldB & 7))) { err = "wgrad_tn: row strides must be multiples of 8 (x3: 16) elements"; return 1; }
     TnArgs a;
-    a.A = A; a.B = B; a.ldA = ldA; a.ldB = ldB; a.K = (int)K; a.Nout = Nout; a.C = C; a.taps = taps; a.Ncols = taps * C; a.rp = rp; a.part = part;
+    a.A = static_cast<const uint16_t*>(A); a.B = static_cast<const uint16_t*>(B); a.ldA = ldA; a.ldB = ldB; a.K = (int)K; a.Nout = Nout; a.C = C; a.taps = taps; a.Ncols = taps * C; a.rp = rp; a.part = part;
     const long tiles = (long)((Nout + 127) / 128) * ((a.Ncols + 127) / 128), nk = (long)K / (x3 ? 32 : 64);
     static const long target = getenv("SOCCDPT_TN_TILES") ? atol(getenv("SOCCDPT_TN_TILES")) : 512;
     long S = target / tiles > 0 ? target / tiles : 1;   // one round of two workgroups per CU
@@ -393,7 +394,7 @@ int tr_wgrad_tn(const uint16_t* A, long ldA, const uint16_t* B, long ldB, size_t
     const dim3 grid((unsigned)(tiles * S)), block(512);
     const size_t lds = 2 * 2 * 64 * 256;
     if (x3) SOCCDPT_LAUNCH(wgrad_tn_x3_kernel, grid, block, lds, st, a);
-    else if (f16) SOCCDPT_LAUNCH(wgrad_tn_kernel<true>, grid, block, lds, st, a);
+    else if (fmt == OpFmt::F16) SOCCDPT_LAUNCH(wgrad_tn_kernel<true>, grid, block, lds, st, a);
     else SOCCDPT_LAUNCH(wgrad_tn_kernel<false>, grid, block, lds, st, a);
     const size_t n4 = (size_t)Nout * a.Ncols / 4;
     if (defer) {
