@@ -36,8 +36,10 @@ extern "C" {
  *     soccdpt_op_window_attention_qkv are new);
  *   6 (soccdpt_igemm_args gained the fused-epilogue fields res2_h .. halo_fmt; soccdpt_op_depth_tail and soccdpt_op_seg_tail are new);
  *   7 (occupancy evaluation: soccdpt_occ_pack, soccdpt_occ_points_scratch_bytes / _count / _write and soccdpt_occ_iou_counts are new; nothing
- *     that existed changed). */
-#define SOCCDPT_ABI_VERSION 7
+ *     that existed changed);
+ *   8 (per-frame occupancy grids: soccdpt_voxelise_frames, soccdpt_occ_expand_frames and soccdpt_forward_frames are new; nothing that existed
+ *     changed, soccdpt_config keeps its size). */
+#define SOCCDPT_ABI_VERSION 8
 
 /* backbone ids: model/loader.py:65-77 (model_type switch), model/blocks.py:59-78 */
 #define SOCCDPT_BACKBONE_SWIN2T16_256 0 /* dpt_swin2_tiny_256 */
@@ -274,6 +276,32 @@ int soccdpt_occ_expand(void* handle, const uint32_t* dev_bits, int B, float* dev
 int soccdpt_occ_zero(void* handle, int B, float* dev_occ, void* stream);
 int soccdpt_occ_set(void* handle, const uint32_t* dev_bits, int B, float* dev_occ, void* stream);
 size_t soccdpt_occ_words(void* handle);
+
+/* ---- per-frame occupancy grids (csrc/occ_frames.hip) ----
+ * soccdpt_forward / soccdpt_project mark ONE grid per call: the union over the frames of the batch, which soccdpt_occ_expand copies into every batch
+ * row -- the reference's points_to_occupancy_grid writes into [:, i, j, k, c] (model/SOccDPT.py:449-455).  These entry points give row b the grid of
+ * frame b ALONE, bit-identical to what the reference computes when handed that one frame as a batch of one.  Bit layout of a row as everywhere
+ * else in this header: cell n = row-major index of [gx][gy][gz][C], bit n & 31 of word n >> 5, soccdpt_occ_words() words per row, rows contiguous.
+ * The OR of the rows equals the union grid of soccdpt_project on the same inputs.  Integer ORs only: deterministic.
+ *
+ * soccdpt_voxelise_frames: dev_inv_up [B,Hc,Wc] is the clamped camera-resolution inverse depth soccdpt_project / soccdpt_forward wrote for these
+ *   frames, dev_seg [B,C,in_h,in_w] the class probabilities at NETWORK resolution (nearest-sampled here, as there).  Per camera pixel the float32
+ *   sequence of the fused kernel is redone from 1 / inv_up on (back-projection, the 3-pixel pc_scale / pc_shift quirk, the three rotations, the
+ *   finite test, the voxel index, 0 < i, j, k < grid), and class c of the voxel is set in row b iff the sampled probability != 0.
+ *   ORs into dev_frame_bits [B][soccdpt_occ_words()] (all B rows cleared first when clear_bits != 0).
+ * soccdpt_occ_expand_frames: dev_frame_bits [B][words] -> dev_occ [B,gx,gy,gz,C] f32 (exactly 0.0 / 1.0), row b from row b.
+ * soccdpt_forward_frames: soccdpt_forward with per-frame rows: network -> projection -> soccdpt_voxelise_frames on the network's class maps ->
+ *   soccdpt_occ_expand_frames.  dev_frame_bits [B][words] and dev_inv_up are required (non-NULL; the voxelisation reads the inverse depth back);
+ *   dev_occ, when given, receives the per-frame rows; dev_occ_bits, when given, receives the union of the rows (one soccdpt_occ_or over
+ *   dev_frame_bits), word for word what soccdpt_forward writes there.  Needs compute_occ.  THIS CALL ALWAYS RUNS EAGERLY: with soccdpt_set_graph
+ *   on it neither captures nor replays (and leaves a graph soccdpt_forward / soccdpt_network captured untouched).
+ * Errors (non-zero, soccdpt_last_error): NULL inputs, B <= 0, num_classes != 3, a too-small workspace. */
+int soccdpt_voxelise_frames(void* handle, const float* dev_inv_up, const float* dev_seg, int B, int in_h, int in_w,
+                            uint32_t* dev_frame_bits, int clear_bits, void* stream);
+int soccdpt_occ_expand_frames(void* handle, const uint32_t* dev_frame_bits, int B, float* dev_occ, void* stream);
+int soccdpt_forward_frames(void* handle, const float* dev_x, int B, float* dev_inv_up, float* dev_seg_up, float* dev_points,
+                           float* dev_occ, uint32_t* dev_occ_bits, uint32_t* dev_frame_bits, void* dev_workspace, size_t workspace_bytes,
+                           void* stream);
 
 /* ---- occupancy evaluation: consumers of the packed grid (csrc/occ_eval.hip).  No handle: stateless, like soccdpt_metrics_*; the grid
  * extents, the class count C (1..8) and occupancy_shape are arguments.  Bit layout as above: cell n = row-major index of [g0][g1][g2][C],

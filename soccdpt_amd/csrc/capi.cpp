@@ -383,6 +383,76 @@ int soccdpt_forward(void* handle, const float* dev_x, int B, float* dev_inv_up, 
     return rc;
 }
 
+// algorithmic HBM bytes of the per-frame voxelisation: the inverse depth and the class maps once, the rows' clear
+static double voxelise_frames_bytes(const soccdpt_config& c, int B, int h, int w) {
+    return (double)B * ((double)c.cam_width * c.cam_height * 4.0 + (double)h * w * 4.0 * c.num_classes + occ_cells(c) * 0.125);
+}
+
+int soccdpt_voxelise_frames(void* handle, const float* dev_inv_up, const float* dev_seg, int B, int in_h, int in_w, uint32_t* dev_frame_bits,
+                            int clear_bits, void* stream) {
+    Handle* h = static_cast<Handle*>(handle);
+    if (!h) return 1;
+    if (!dev_inv_up || !dev_seg || !dev_frame_bits) return fail(h, "soccdpt_voxelise_frames: null argument");
+    if (B <= 0 || in_h <= 0 || in_w <= 0) return fail(h, "soccdpt_voxelise_frames: empty input");
+    ProfScope ps(h->prof, "voxelise_frames", 0.0, voxelise_frames_bytes(h->cfg, B, in_h, in_w), (hipStream_t)stream);
+    return launch_voxelise_frames(h->cfg, dev_inv_up, dev_seg, B, in_h, in_w, dev_frame_bits, clear_bits, (hipStream_t)stream, h->err);
+}
+
+int soccdpt_occ_expand_frames(void* handle, const uint32_t* dev_frame_bits, int B, float* dev_occ, void* stream) {
+    Handle* h = static_cast<Handle*>(handle);
+    if (!h) return 1;
+    if (!dev_frame_bits || !dev_occ) return fail(h, "soccdpt_occ_expand_frames: null argument");
+    if (B <= 0) return fail(h, "soccdpt_occ_expand_frames: empty batch");
+    ProfScope ps(h->prof, "occ_expand_frames", 0.0, occ_cells(h->cfg) * (4.0 + 0.125) * B, (hipStream_t)stream);
+    return launch_occ_expand_frames(h->cfg, dev_frame_bits, B, dev_occ, (hipStream_t)stream, h->err);
+}
+
+int soccdpt_forward_frames(void* handle, const float* dev_x, int B, float* dev_inv_up, float* dev_seg_up, float* dev_points, float* dev_occ,
+                           uint32_t* dev_occ_bits, uint32_t* dev_frame_bits, void* dev_workspace, size_t workspace_bytes, void* stream) {
+    Handle* h = static_cast<Handle*>(handle);
+    if (!h) return 1;
+    if (B <= 0) return fail(h, "soccdpt_forward_frames: empty batch");
+    if (!dev_x || !dev_workspace) return fail(h, "soccdpt_forward_frames: null argument");
+    if (!h->cfg.compute_occ) return fail(h, "soccdpt_forward_frames: the handle was created without compute_occ");
+    if (!dev_inv_up) return fail(h, "soccdpt_forward_frames: dev_inv_up is required (the per-frame voxelisation reads the inverse depth back)");
+    if (!dev_frame_bits) return fail(h, "soccdpt_forward_frames: dev_frame_bits is required");
+    const int S = h->img;
+    // the network outputs live at the head of the workspace (as in soccdpt_forward)
+    float* inv = static_cast<float*>(dev_workspace);
+    float* seg = inv + (size_t)B * S * S;
+    const size_t head = (size_t)B * S * S * (1 + h->cfg.num_classes) * sizeof(float);
+    if (workspace_bytes < head) return fail(h, "soccdpt_forward_frames: workspace too small");
+    hipStream_t st = (hipStream_t)stream;
+    // always eager: the per-frame passes read this call's outputs, and a captured network graph is keyed on soccdpt_forward's pointers
+    const bool graph_was = h->use_graph;
+    h->use_graph = false;
+    int rc = model_network(*h, dev_x, B, inv, seg, dev_workspace, workspace_bytes, st, h->err);
+    h->use_graph = graph_was;
+    if (rc) return rc;
+    {   // the union comes from the frame rows below, so the fused kernel skips its own marking
+        ProfScope ps(h->prof, "project_voxelise", 0.0, project_bytes(h->cfg, B, S, S, dev_inv_up, dev_seg_up, dev_points), st);
+        rc = launch_project(h->cfg, inv, seg, B, S, S, dev_inv_up, dev_seg_up, dev_points, nullptr, 0, st, h->err);
+    }
+    if (rc) return rc;
+    {
+        ProfScope ps(h->prof, "voxelise_frames", 0.0, voxelise_frames_bytes(h->cfg, B, S, S), st);
+        rc = launch_voxelise_frames(h->cfg, dev_inv_up, seg, B, S, S, dev_frame_bits, 1, st, h->err);
+    }
+    if (rc) return rc;
+    if (dev_occ_bits) {
+        const size_t wbytes = soccdpt_occ_words(h) * sizeof(uint32_t);
+        if (hipMemsetAsync(dev_occ_bits, 0, wbytes, st) != hipSuccess) return fail(h, "soccdpt_forward_frames: clearing dev_occ_bits failed");
+        ProfScope ps(h->prof, "occ_or", 0.0, occ_cells(h->cfg) * 0.125 * (B + 2), st);
+        rc = launch_occ_or(h->cfg, dev_occ_bits, dev_frame_bits, B, st, h->err);
+        if (rc) return rc;
+    }
+    if (dev_occ) {
+        ProfScope ps(h->prof, "occ_expand_frames", 0.0, occ_cells(h->cfg) * (4.0 + 0.125) * B, st);
+        rc = launch_occ_expand_frames(h->cfg, dev_frame_bits, B, dev_occ, st, h->err);
+    }
+    return rc;
+}
+
 int soccdpt_last_launch_count(void* handle) { return static_cast<Handle*>(handle)->launches; }
 unsigned long long soccdpt_launch_counter(void) { return soccdpt::launch_counter(); }
 

@@ -183,4 +183,9 @@ int launch_occ_zero(const soccdpt_config& cfg, int B, float* occ, hipStream_t st
 int launch_occ_set(const soccdpt_config& cfg, const uint32_t* bits, int B, float* occ, hipStream_t stream, std::string& err);
 int launch_occ_or(const soccdpt_config& cfg, uint32_t* dst, const uint32_t* src, int nsets, hipStream_t stream, std::string& err);
 
+// occ_frames.hip: per-frame grids (row b = frame b alone) from the camera-resolution inverse depth soccdpt_project wrote
+int launch_voxelise_frames(const soccdpt_config& cfg, const float* inv_up, const float* seg, int B, int in_h, int in_w, uint32_t* frame_bits,
+                           int clear_bits, hipStream_t stream, std::string& err);
+int launch_occ_expand_frames(const soccdpt_config& cfg, const uint32_t* frame_bits, int B, float* occ, hipStream_t stream, std::string& err);
+
 }  // namespace soccdpt

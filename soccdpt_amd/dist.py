@@ -6,6 +6,10 @@ written to every batch row (/root/reference/SOccDPT/model/SOccDPT.py:449-455).  
 its own frames into a bit-packed grid (786,432 B for 256x256x32x3) and the ranks exchange only those
 packed grids: one RCCL all-gather (backend "nccl" is RCCL on ROCm) followed by a local OR-reduce kernel and
 the bits->f32 expansion.  The dense 25 MB f32 grids never cross xGMI.
+
+A model built with occupancy_per_frame=True keeps its per-frame grids RANK-LOCAL: row b of the occupancy a rank returns (and of
+net.last_occ_frame_bits) is the grid of that rank's frame b alone and is never exchanged.  Only the union (net.last_occ_bits) goes through
+the exchange, exactly as in union mode; no collective changes.
 """
 from __future__ import annotations
 

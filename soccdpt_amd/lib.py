@@ -15,7 +15,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SOCCDPT_LIB_PATH") or os.path.join(_HERE, "libsoccdpt_hip.so")   # override: A/B of two builds in one GPU call (tools/ab_bench.sh)
 
-ABI_VERSION = 7
+ABI_VERSION = 8
 BACKBONE_IDS = {"swin2t16_256": 0, "swin2b24_384": 1, "vitb_rn50_384": 2}
 PREC_BF16 = 0
 PREC_F32 = 1
@@ -182,6 +182,12 @@ def load_library() -> ctypes.CDLL:
     L.soccdpt_occ_expand.restype = ci
     L.soccdpt_occ_words.argtypes = [vp]
     L.soccdpt_occ_words.restype = cs
+    L.soccdpt_voxelise_frames.argtypes = [vp, vp, vp, ci, ci, ci, vp, ci, vp]
+    L.soccdpt_voxelise_frames.restype = ci
+    L.soccdpt_occ_expand_frames.argtypes = [vp, vp, ci, vp, vp]
+    L.soccdpt_occ_expand_frames.restype = ci
+    L.soccdpt_forward_frames.argtypes = [vp, vp, ci, vp, vp, vp, vp, vp, vp, vp, cs, vp]
+    L.soccdpt_forward_frames.restype = ci
     L.soccdpt_occ_pack.argtypes = [vp, ci, ci, cs, ctypes.c_float, ci, vp, vp]
     L.soccdpt_occ_pack.restype = ci
     L.soccdpt_occ_points_scratch_bytes.argtypes = [ci, cs, ci]
@@ -530,6 +536,34 @@ class Engine:
         with torch.cuda.device(self.device):
             self._check(self.L.soccdpt_occ_expand(self._h, _ptr(bits), B, _ptr(occ), _stream_ptr(self.device)),
                         "soccdpt_occ_expand")
+
+    # ---- per-frame occupancy grids (include/soccdpt_hip.h: soccdpt_voxelise_frames / soccdpt_occ_expand_frames / soccdpt_forward_frames) ----
+    def voxelise_frames(self, inv_up: torch.Tensor, seg: torch.Tensor, frame_bits: torch.Tensor, clear_bits: bool = True):
+        """inv_up [B,Hc,Wc] (the clamped inverse depth `project` wrote) + seg [B,C,h,w] at network resolution -> frame_bits [B, occ_words()] int32:
+        row b is the grid of frame b alone (ORed into the buffer; cleared first with clear_bits)."""
+        B, h, w = seg.shape[0], seg.shape[2], seg.shape[3]
+        assert tuple(inv_up.shape) == (B, self.cfg.cam_height, self.cfg.cam_width) and inv_up.dtype == torch.float32 and seg.dtype == torch.float32
+        assert frame_bits.dtype == torch.int32 and frame_bits.numel() == B * self.occ_words()
+        with torch.cuda.device(self.device):
+            self._check(self.L.soccdpt_voxelise_frames(self._h, _ptr(inv_up), _ptr(seg), B, h, w, _ptr(frame_bits), 1 if clear_bits else 0,
+                                                       _stream_ptr(self.device)), "soccdpt_voxelise_frames")
+
+    def occ_expand_frames(self, frame_bits: torch.Tensor, B: int, occ: torch.Tensor):
+        """frame_bits [B, occ_words()] -> occ [B,g0,g1,g2,C] f32, row b from row b."""
+        assert frame_bits.dtype == torch.int32 and frame_bits.numel() == B * self.occ_words() and occ.dtype == torch.float32
+        with torch.cuda.device(self.device):
+            self._check(self.L.soccdpt_occ_expand_frames(self._h, _ptr(frame_bits), B, _ptr(occ), _stream_ptr(self.device)),
+                        "soccdpt_occ_expand_frames")
+
+    def forward_frames(self, x: torch.Tensor, inv_up, seg_up, points, occ, occ_bits, frame_bits):
+        """`forward` with per-frame occupancy rows: occ (optional) and frame_bits [B, occ_words()] hold frame b's grid in row b, occ_bits (optional)
+        the union as `forward` writes it.  Always eager (no hipGraph replay)."""
+        B = x.shape[0]
+        ws = self.workspace(B)
+        with torch.cuda.device(self.device):
+            self._check(self.L.soccdpt_forward_frames(self._h, _ptr(x), B, _ptr(inv_up), _ptr(seg_up), _ptr(points), _ptr(occ), _ptr(occ_bits),
+                                                      _ptr(frame_bits), ws.data_ptr(), ws.numel(), _stream_ptr(self.device)),
+                        "soccdpt_forward_frames")
 
     def occ_zero(self, B: int, occ: torch.Tensor):
         with torch.cuda.device(self.device):

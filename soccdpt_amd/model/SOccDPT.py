@@ -39,10 +39,16 @@ class SOccDPT(BaseModel):
                  camera_intrinsics_yaml=DEFAULT_CALIB, point_compute_method="torch",
                  grid_size=(256, 256, 32), scale=(2.0, 2.0, 0.666), shift=(0.0, 0.0, 0.0),
                  pc_scale=(10000.0, 50000.0, 800.0), pc_shift=(55.0, -20.0, 15.0), correction_angle=(7.0, 0, 0),
-                 compute_occ=False, precision: int = PREC_MIXED, streams: int = 1, graph: bool = False, share_occupancy_rows: bool = False, **kwargs):
+                 compute_occ=False, precision: int = PREC_MIXED, streams: int = 1, graph: bool = False, share_occupancy_rows: bool = False,
+                 occupancy_per_frame: bool = False, **kwargs):
         super().__init__()
         self.compute_occ = compute_occ
         self.share_occupancy_rows = bool(share_occupancy_rows)   # occupancy returned as a stride-0 expand of one row (read-only callers)
+        # opt-in: row b of the occupancy output is the grid of frame b ALONE (what the reference computes for that frame as a batch of one) instead
+        # of the union over the batch in every row; the packed rows are kept in last_occ_frame_bits, last_occ_bits stays the union
+        self.occupancy_per_frame = bool(occupancy_per_frame)
+        assert not (self.occupancy_per_frame and self.share_occupancy_rows), \
+            "occupancy_per_frame gives every batch row its own grid; share_occupancy_rows returns one shared row: choose one"
         self.grid_size = grid_size
         self.scale = scale
         self.shift = shift
@@ -142,11 +148,37 @@ class SOccDPT(BaseModel):
         seg_up = torch.empty((B, C, Hc, Wc), device=dev)
         points = torch.empty((B, Hc, Wc, 3), device=dev)
         occ = None
+        if self.compute_occ and self.occupancy_per_frame:
+            eng.project(inv, seg, inv_up, seg_up, points, None)   # the union comes from the frame rows
+            occ = self._frames_occupancy(eng, inv_up, seg)
+            return self._shape_outputs(inv_up, seg_up, points, occ)
         bits = torch.empty((eng.occ_words(),), dtype=torch.int32, device=dev) if self.compute_occ else None
         eng.project(inv, seg, inv_up, seg_up, points, bits, clear_bits=True)
         if self.compute_occ:
             occ = self._finish_occupancy(eng, bits, B)
         return self._shape_outputs(inv_up, seg_up, points, occ)
+
+    def _frames_occupancy(self, eng: Engine, inv_up: torch.Tensor, seg: torch.Tensor):
+        """occupancy_per_frame: one grid per frame from the projection's clamped inverse depth and the network-resolution class maps
+        (soccdpt_voxelise_frames), dense rows from their own bits, the union of the rows as last_occ_bits."""
+        B = inv_up.shape[0]
+        g = self.grid_size
+        frame_bits = torch.empty((B, eng.occ_words()), dtype=torch.int32, device=inv_up.device)
+        eng.voxelise_frames(inv_up, seg, frame_bits, clear_bits=True)
+        union = torch.zeros((eng.occ_words(),), dtype=torch.int32, device=inv_up.device)
+        eng.occ_or(union, frame_bits, B)
+        occ = torch.empty((B, g[0], g[1], g[2], self.num_classes), device=inv_up.device)
+        eng.occ_expand_frames(frame_bits, B, occ)
+        self._publish_frame_bits(eng, frame_bits, union)
+        return occ
+
+    def _publish_frame_bits(self, eng: Engine, frame_bits: torch.Tensor, union: torch.Tensor):
+        # multi-GPU: the per-frame rows are rank-local and stay here; only the union goes through the exchange, as in union mode
+        ex = self.occ_exchange
+        if ex is not None:
+            union = ex.finish(eng, union, ex.start(union)) if hasattr(ex, "start") else ex(eng, union)
+        self.last_occ_frame_bits = frame_bits
+        self.last_occ_bits = union
 
     def _finish_occupancy(self, eng: Engine, bits: torch.Tensor, B: int):
         g = self.grid_size
@@ -165,15 +197,23 @@ class SOccDPT(BaseModel):
                 bits = ex(eng, bits)
             eng.occ_expand(bits, rows, occ)
         self.last_occ_bits = bits
+        self.last_occ_frame_bits = None
         # opt-in: ONE dense row viewed B times (stride 0).  The reference writes the same union grid into every batch row
         # (/root/reference/SOccDPT/model/SOccDPT.py:449-455); a caller that only reads it saves (B - 1) x 25 MB of stores per step.
         return occ.expand(B, -1, -1, -1, -1) if self.share_occupancy_rows else occ
 
-    def occupancy_points(self, class_2_color=None):
+    def occupancy_points(self, class_2_color=None, frame=None):
         """The last forward's occupancy grid as the reference's point list (utils/__init__.py:532-568 occupancy_grid_to_points on occupancy[0]):
         float64 [N,4] rows (x, y, z, class_id) in metres, class-major, straight from the packed bits `last_occ_bits` -- no dense grid is read,
-        so it works the same with share_occupancy_rows=True and under occ_exchange.  With class_2_color also the [N,3] u8 colours."""
-        bits = getattr(self, "last_occ_bits", None)
+        so it works the same with share_occupancy_rows=True and under occ_exchange.  With class_2_color also the [N,3] u8 colours.
+        frame=None lists the union grid; frame=b (a model built with occupancy_per_frame=True) lists frame b's own grid from `last_occ_frame_bits`."""
+        if frame is not None:
+            rows = getattr(self, "last_occ_frame_bits", None)
+            if not self.occupancy_per_frame or rows is None:
+                raise RuntimeError("occupancy_points(frame=...) needs a forward of a model built with compute_occ=True and occupancy_per_frame=True")
+            bits = rows[int(frame)]
+        else:
+            bits = getattr(self, "last_occ_bits", None)
         if bits is None:
             raise RuntimeError("occupancy_points() needs a forward of a model built with compute_occ=True first")
         from ..utils.occupancy import occupancy_bits_to_points
@@ -278,6 +318,14 @@ class SOccDPT_V3(SOccDPT):
         points = torch.empty((B, Hc, Wc, 3), device=dev)
         occ = None
         bits = None
+        if self.compute_occ and self.occupancy_per_frame:
+            g = self.grid_size
+            occ = torch.empty((B, g[0], g[1], g[2], C), device=dev)
+            bits = torch.empty((eng.occ_words(),), dtype=torch.int32, device=dev)
+            frame_bits = torch.empty((B, eng.occ_words()), dtype=torch.int32, device=dev)
+            eng.forward_frames(xin, inv_up, seg_up, points, occ, bits, frame_bits)
+            self._publish_frame_bits(eng, frame_bits, bits)
+            return self._shape_outputs(inv_up, seg_up, points, occ)
         if self.compute_occ:
             bits = torch.empty((eng.occ_words(),), dtype=torch.int32, device=dev)
             if self.occ_exchange is None and not self.share_occupancy_rows:
@@ -287,6 +335,7 @@ class SOccDPT_V3(SOccDPT):
         if self.compute_occ and occ is None:
             occ = self._finish_occupancy(eng, bits, B)
         self.last_occ_bits = bits
+        self.last_occ_frame_bits = None
         return self._shape_outputs(inv_up, seg_up, points, occ)
 
     def _forward_train(self, x: torch.Tensor):
@@ -476,12 +525,13 @@ class _TrainForward(torch.autograd.Function):
         inv_up = torch.empty((B, Hc, Wc), device=dev)
         seg_up = torch.empty((B, C, Hc, Wc), device=dev)
         points = torch.empty((B, Hc, Wc, 3), device=dev)
-        bits = torch.empty((eng.occ_words(),), dtype=torch.int32, device=dev) if net.compute_occ else None
+        per_frame = net.compute_occ and net.occupancy_per_frame
+        bits = torch.empty((eng.occ_words(),), dtype=torch.int32, device=dev) if (net.compute_occ and not per_frame) else None
         eng.project(inv, seg, inv_up, seg_up, points, bits, clear_bits=True)
         ctx.net, ctx.generation, ctx.hw = net, net._train_generation, (inv.shape[1], inv.shape[2])
         ctx.save_for_backward(inv_up)
         if net.compute_occ:
-            occ = net._finish_occupancy(eng, bits, B)
+            occ = net._frames_occupancy(eng, inv_up, seg) if per_frame else net._finish_occupancy(eng, bits, B)
             ctx.mark_non_differentiable(occ)
             return inv_up, seg_up, points, occ
         return inv_up, seg_up, points

@@ -41,6 +41,9 @@ def build_parser() -> argparse.ArgumentParser:
     parser.add_argument("--camera_intrinsics_yaml", default=None, help="calibration file (default: the synthetic 1920x1080 camera of SURVEY.md 8d)")
     parser.add_argument("--occupancy", action="store_true", help="also evaluate the semantic occupancy grid on the GPU: 3-D IoU against the ground-truth "
                         "grid of OccupancyProcessor and the mean length of the occupancy point list (prints IOU_3D / OCC_POINTS)")
+    parser.add_argument("--occupancy-per-frame", dest="occupancy_per_frame", action="store_true", help="implies --occupancy, with the model built with "
+                        "occupancy_per_frame=True: every frame's own grid (not the union over the batch) is scored against that frame's ground truth, "
+                        "and OCC_POINTS is the mean point-list length per frame")
     return parser
 
 
@@ -74,8 +77,11 @@ def main(args) -> dict:
     num_classes = 3
     calib = args.camera_intrinsics_yaml or write_synth_calib(os.path.join(tempfile.mkdtemp(), "calib.yaml"))
     model_kwargs = dict(num_classes=num_classes, camera_intrinsics_yaml=calib)
-    occupancy = bool(getattr(args, "occupancy", False))
-    if occupancy:
+    per_frame = bool(getattr(args, "occupancy_per_frame", False))
+    occupancy = bool(getattr(args, "occupancy", False)) or per_frame
+    if per_frame:
+        model_kwargs.update(compute_occ=True, occupancy_per_frame=True)
+    elif occupancy:
         model_kwargs.update(compute_occ=True, share_occupancy_rows=True)
     if args.version == 1:
         model_kwargs["load_depth"] = args.load_depth
@@ -139,7 +145,9 @@ def main(args) -> dict:
 
 def evaluate_occupancy_set(net, dataset, device, point_count_threshold: float = 10.0) -> dict:
     """Mean 3-D IoU of the model's occupancy grid (packed bits of each forward) against the ground-truth grid OccupancyProcessor builds from the
-    sample's (y_disp, argmax y_seg), and the mean length of the model's occupancy point list -- everything on the GPU."""
+    sample's (y_disp, argmax y_seg), and the mean length of the model's occupancy point list -- everything on the GPU.  A model built with
+    occupancy_per_frame=True is scored row by row: frame b's own grid (net.last_occ_frame_bits[b]) against ground-truth row b, and the list length
+    is the mean over the frames; otherwise the one union grid of each forward is scored against every ground-truth row of its batch."""
     from ..utils.gt_occupancy import OccupancyProcessor
     from ..utils.occupancy import occupancy_iou
     proc = OccupancyProcessor(intrinsic_matrix=net.intrinsic_matrix, height=net.height, width=net.width, grid_size=net.grid_size, scale=net.scale, shift=net.shift,
@@ -151,8 +159,13 @@ def evaluate_occupancy_set(net, dataset, device, point_count_threshold: float = 
         x = x.to(device=device, dtype=torch.float32)
         gt = proc.process(y_disp.to(device=device, dtype=torch.float32), y_seg.to(device).argmax(dim=1), want_points=False, want_depth=False)
         net(x)
-        ious.append(occupancy_iou(net.last_occ_bits, gt["occupancy_grid"], num_classes=net.num_classes)["iou_3D"])
-        lengths.append(net.occupancy_points().shape[0])
+        if getattr(net, "occupancy_per_frame", False):
+            rows = net.last_occ_frame_bits
+            ious.append(occupancy_iou(rows, gt["occupancy_grid"], num_classes=net.num_classes)["iou_3D"])
+            lengths.extend(net.occupancy_points(frame=b).shape[0] for b in range(rows.shape[0]))
+        else:
+            ious.append(occupancy_iou(net.last_occ_bits, gt["occupancy_grid"], num_classes=net.num_classes)["iou_3D"])
+            lengths.append(net.occupancy_points().shape[0])
     return dict(iou_3D=float(torch.cat(ious).mean().item()), occ_points=float(np.mean(lengths)))
 
 
