@@ -26,16 +26,75 @@ unsigned long long& launch_counter() {
 }
 }  // namespace soccdpt
 
-// algorithmic HBM bytes of the projection kernel: inputs once + every requested output once
-static double project_bytes(const soccdpt_config& c, int B, int h, int w, const void* inv_up, const void* seg_up, const void* points) {
-    const double px = (double)c.cam_width * c.cam_height * B;
-    return (double)B * h * w * 4.0 * (1 + c.num_classes) + px * 4.0 * ((inv_up ? 1 : 0) + (seg_up ? c.num_classes : 0) + (points ? 3 : 0));
-}
 static double occ_cells(const soccdpt_config& c) { return (double)c.grid[0] * c.grid[1] * c.grid[2] * c.num_classes; }
 
 static int fail(Handle* h, const std::string& msg) {
     if (h) h->err = msg; else g_create_error = msg;
     return 1;
+}
+
+// ---- profiled launches: each profiler family's name and algorithmic HBM bytes exist here once; the stage-level entry points and the
+// two whole-forward entry points launch through them ----
+static int profiled_project(Handle* h, const float* inv, const float* seg, int B, int in_h, int in_w, float* inv_up, float* seg_up, float* points,
+                            uint32_t* occ_bits, int clear_bits, hipStream_t st) {
+    const soccdpt_config& c = h->cfg;
+    // inputs once + every requested output once
+    const double px = (double)c.cam_width * c.cam_height * B;
+    const double bytes = (double)B * in_h * in_w * 4.0 * (1 + c.num_classes) + px * 4.0 * ((inv_up ? 1 : 0) + (seg_up ? c.num_classes : 0) + (points ? 3 : 0));
+    ProfScope ps(h->prof, "project_voxelise", 0.0, bytes, st);
+    return launch_project(c, inv, seg, B, in_h, in_w, inv_up, seg_up, points, occ_bits, clear_bits, st, h->err);
+}
+static int profiled_occ_expand(Handle* h, const uint32_t* bits, int B, float* occ, hipStream_t st) {
+    ProfScope ps(h->prof, "occ_expand", 0.0, occ_cells(h->cfg) * (4.0 * B + 0.125), st);
+    return launch_occ_expand(h->cfg, bits, B, occ, st, h->err);
+}
+static int profiled_voxelise_frames(Handle* h, const float* inv_up, const float* seg, int B, int in_h, int in_w, uint32_t* frame_bits, int clear_bits,
+                                    hipStream_t st) {
+    const soccdpt_config& c = h->cfg;
+    // the inverse depth and the class maps once, the rows' clear
+    const double bytes = (double)B * ((double)c.cam_width * c.cam_height * 4.0 + (double)in_h * in_w * 4.0 * c.num_classes + occ_cells(c) * 0.125);
+    ProfScope ps(h->prof, "voxelise_frames", 0.0, bytes, st);
+    return launch_voxelise_frames(c, inv_up, seg, B, in_h, in_w, frame_bits, clear_bits, st, h->err);
+}
+static int profiled_occ_expand_frames(Handle* h, const uint32_t* frame_bits, int B, float* occ, hipStream_t st) {
+    ProfScope ps(h->prof, "occ_expand_frames", 0.0, occ_cells(h->cfg) * (4.0 + 0.125) * B, st);
+    return launch_occ_expand_frames(h->cfg, frame_bits, B, occ, st, h->err);
+}
+
+// Head of soccdpt_forward / soccdpt_forward_frames (`who`): the network outputs live at the head of the workspace -- model_network carves its scratch
+// behind the same head, so the halo images sit at the same place for every entry point -- and the network runs into them.
+static int network_at_head(Handle* h, const char* who, const float* dev_x, int B, void* dev_workspace, size_t workspace_bytes, hipStream_t st, float** inv,
+                           float** seg) {
+    const int S = h->img;
+    *inv = static_cast<float*>(dev_workspace);
+    *seg = *inv + (size_t)B * S * S;
+    const size_t head = (size_t)B * S * S * (1 + h->cfg.num_classes) * sizeof(float);
+    if (workspace_bytes < head) return fail(h, std::string(who) + ": workspace too small");
+    return model_network(*h, dev_x, B, *inv, *seg, dev_workspace, workspace_bytes, st, h->err);
+}
+
+// soccdpt_prepare found that the precision map in force does not describe the bound weights (or does again): put the map that does in place --
+// the shipped one, or x3 operands for every group -- void both caches, whose layout follows the formats, and prepare again.
+static int remap_and_prepare(Handle* h, bool shipped_map, void* dev_prepared, size_t prepared_bytes, hipStream_t st) {
+    if (shipped_map) model_prec_default(*h);
+    else for (const auto& g : model_prec_groups(*h)) h->prec_map[g] = 3;
+    h->ws_key = Handle::WsKey();
+    model_drop_graph(*h);
+    return model_prepare(*h, dev_prepared, prepared_bytes, st, h->err) ? 1 : 0;
+}
+
+// The backward passes of the training step (`who`) run with the amp / drop-path modes their forward latched: a setter called between forward
+// and backward takes effect at the next forward.
+template <class Run>
+static int train_backward_as_forward_ran(Handle* h, const char* who, int B, void* dev_workspace, Run&& run) {
+    if (h->train_key.ws != dev_workspace || h->train_key.B != B || !dev_workspace)
+        return fail(h, std::string(who) + ": no soccdpt_train_forward ran on this workspace with this batch size");
+    const int amp_now = h->train_amp;
+    const float dp_now = h->train_drop_path;
+    h->train_amp = h->train_key.amp; h->train_drop_path = h->train_key.drop_path;
+    const int rc = run();
+    h->train_amp = amp_now; h->train_drop_path = dp_now;
+    return rc;
 }
 
 extern "C" {
@@ -147,40 +206,31 @@ int soccdpt_prepare(void* handle, void* dev_prepared, size_t prepared_bytes, voi
     Handle* h = static_cast<Handle*>(handle);
     if (!h) return 1;
     if (model_prepare(*h, dev_prepared, prepared_bytes, (hipStream_t)stream, h->err)) return 1;
+    // the fingerprint kernels' 8 bytes of output: the arena's 256-byte tail is free
+    unsigned long long* tmp = reinterpret_cast<unsigned long long*>((reinterpret_cast<uintptr_t>(dev_prepared) + h->prepared_bytes - 8) & ~uintptr_t(7));
     if (h->cfg.precision == SOCCDPT_PREC_MIXED && h->prec_source == 1 && h->calib_fp_valid) {
         // A calibrated map is a statement about the weights it was derived on: other values under the same keys -- a rebind, or a
         // load_state_dict / optimizer step into the same storage -- void it.  Same four-tensor fingerprint as below; on a mismatch every group
         // goes back to x3 operands (source 3) until the caller calibrates again.
-        unsigned long long* tmp = reinterpret_cast<unsigned long long*>((reinterpret_cast<uintptr_t>(dev_prepared) + h->prepared_bytes - 8) & ~uintptr_t(7));
         unsigned long long fp = 0;
         const int rc = calib_fingerprint(*h, tmp, (hipStream_t)stream, &fp, h->err);
         if (rc < 0) return 1;
         if (rc > 0 || fp != h->calib_fp) {
             h->prec_source = 3;
             h->calib_fp_valid = false;
-            for (const auto& g : model_prec_groups(*h)) h->prec_map[g] = 3;
-            h->ws_key = Handle::WsKey();
-            model_drop_graph(*h);
-            if (model_prepare(*h, dev_prepared, prepared_bytes, (hipStream_t)stream, h->err)) return 1;
+            return remap_and_prepare(h, false, dev_prepared, prepared_bytes, (hipStream_t)stream);
         }
         return 0;
     }
     if (h->cfg.precision == SOCCDPT_PREC_MIXED && h->prec_source != 1 && h->prec_source != 2) {
-        // Is the shipped map running on the weights it was derived from?  (a fingerprint of four tensors; the arena's 256-byte tail is free.)
+        // Is the shipped map running on the weights it was derived from?  (a fingerprint of four tensors.)
         // On any other weights its within-tolerance claim is unverified -- measured in round 5: a second synthetic draw leaves the class logits at
         // 1.4e-3 under the shipped map -- so until soccdpt_prec_calibrate has run every group takes x3 operands (f32-grade, about 1.7x the step).
-        unsigned long long* tmp = reinterpret_cast<unsigned long long*>((reinterpret_cast<uintptr_t>(dev_prepared) + h->prepared_bytes - 8) & ~uintptr_t(7));
         const int same = calib_weights_are_the_shipped_draw(*h, tmp, (hipStream_t)stream, h->err);
         if (same < 0) return 1;
         const int was = h->prec_source;
         h->prec_source = same ? 0 : 3;
-        if (h->prec_source != was && (h->prec_source == 3 || was == 3)) {
-            if (same) model_prec_default(*h);
-            else for (const auto& g : model_prec_groups(*h)) h->prec_map[g] = 3;
-            h->ws_key = Handle::WsKey();
-            model_drop_graph(*h);
-            if (model_prepare(*h, dev_prepared, prepared_bytes, (hipStream_t)stream, h->err)) return 1;
-        }
+        if (h->prec_source != was && (h->prec_source == 3 || was == 3)) return remap_and_prepare(h, same != 0, dev_prepared, prepared_bytes, (hipStream_t)stream);
     }
     return 0;
 }
@@ -249,14 +299,9 @@ size_t soccdpt_train_workspace_bytes(void* handle, int B) { return handle && B >
 int soccdpt_train_backward_encoder(void* handle, int B, const float* const* dev_d_feat, void* dev_workspace, size_t workspace_bytes, void* stream) {
     Handle* h = static_cast<Handle*>(handle);
     if (!h) return 1;
-    if (h->train_key.ws != dev_workspace || h->train_key.B != B || !dev_workspace)
-        return fail(h, "soccdpt_train_backward_encoder: no soccdpt_train_forward ran on this workspace with this batch size");
-    const int amp_now = h->train_amp;
-    const float dp_now = h->train_drop_path;
-    h->train_amp = h->train_key.amp; h->train_drop_path = h->train_key.drop_path;
-    const int rc = train_backward_encoder(*h, B, dev_d_feat, dev_workspace, workspace_bytes, (hipStream_t)stream, h->err);
-    h->train_amp = amp_now; h->train_drop_path = dp_now;
-    return rc;
+    return train_backward_as_forward_ran(h, "soccdpt_train_backward_encoder", B, dev_workspace, [&] {
+        return train_backward_encoder(*h, B, dev_d_feat, dev_workspace, workspace_bytes, (hipStream_t)stream, h->err);
+    });
 }
 int soccdpt_train_workspace_tensor(void* handle, int B, const char* name, size_t* byte_offset, size_t* elems) {
     Handle* h = static_cast<Handle*>(handle);
@@ -280,15 +325,9 @@ int soccdpt_train_backward(void* handle, const float* dev_x, int B, const float*
     Handle* h = static_cast<Handle*>(handle);
     if (!h) return 1;
     if (!dev_d_inv || !dev_d_seg) return fail(h, "soccdpt_train_backward: null argument");
-    if (h->train_key.ws != dev_workspace || h->train_key.B != B || !dev_workspace)
-        return fail(h, "soccdpt_train_backward: no soccdpt_train_forward ran on this workspace with this batch size");
-    // the modes the forward ran with (a setter called between forward and backward takes effect at the next forward)
-    const int amp_now = h->train_amp;
-    const float dp_now = h->train_drop_path;
-    h->train_amp = h->train_key.amp; h->train_drop_path = h->train_key.drop_path;
-    const int rc = train_backward(*h, dev_x, B, dev_d_inv, dev_d_seg, dev_workspace, workspace_bytes, (hipStream_t)stream, h->err);
-    h->train_amp = amp_now; h->train_drop_path = dp_now;
-    return rc;
+    return train_backward_as_forward_ran(h, "soccdpt_train_backward", B, dev_workspace, [&] {
+        return train_backward(*h, dev_x, B, dev_d_inv, dev_d_seg, dev_workspace, workspace_bytes, (hipStream_t)stream, h->err);
+    });
 }
 
 int soccdpt_project(void* handle, const float* dev_inv, const float* dev_seg, int B, int in_h, int in_w, float* dev_inv_up,
@@ -296,9 +335,7 @@ int soccdpt_project(void* handle, const float* dev_inv, const float* dev_seg, in
     Handle* h = static_cast<Handle*>(handle);
     if (!h) return 1;
     if (!dev_inv || !dev_seg) return fail(h, "soccdpt_project: null input");
-    ProfScope ps(h->prof, "project_voxelise", 0.0, project_bytes(h->cfg, B, in_h, in_w, dev_inv_up, dev_seg_up, dev_points), (hipStream_t)stream);
-    return launch_project(h->cfg, dev_inv, dev_seg, B, in_h, in_w, dev_inv_up, dev_seg_up, dev_points, dev_occ_bits, clear_bits,
-                          (hipStream_t)stream, h->err);
+    return profiled_project(h, dev_inv, dev_seg, B, in_h, in_w, dev_inv_up, dev_seg_up, dev_points, dev_occ_bits, clear_bits, (hipStream_t)stream);
 }
 
 size_t soccdpt_occ_words(void* handle) {
@@ -334,8 +371,7 @@ int soccdpt_occ_expand(void* handle, const uint32_t* dev_bits, int B, float* dev
     Handle* h = static_cast<Handle*>(handle);
     if (!h) return 1;
     if (B <= 0) return fail(h, "soccdpt_occ_expand: empty batch");
-    ProfScope ps(h->prof, "occ_expand", 0.0, occ_cells(h->cfg) * (4.0 * B + 0.125), (hipStream_t)stream);
-    return launch_occ_expand(h->cfg, dev_bits, B, dev_occ, (hipStream_t)stream, h->err);
+    return profiled_occ_expand(h, dev_bits, B, dev_occ, (hipStream_t)stream);
 }
 
 int soccdpt_occ_zero(void* handle, int B, float* dev_occ, void* stream) {
@@ -360,32 +396,16 @@ int soccdpt_forward(void* handle, const float* dev_x, int B, float* dev_inv_up, 
     if (!h) return 1;
     if (B <= 0) return fail(h, "soccdpt_forward: empty batch");
     const int S = h->img;
-    // the network outputs live at the head of the workspace
-    float* inv = static_cast<float*>(dev_workspace);
-    float* seg = inv + (size_t)B * S * S;
-    const size_t head = (size_t)B * S * S * (1 + h->cfg.num_classes) * sizeof(float);
-    if (workspace_bytes < head) return fail(h, "soccdpt_forward: workspace too small");
-    // model_network carves its scratch behind the same head, so the halo images sit at the same place for every entry point
-    int rc = model_network(*h, dev_x, B, inv, seg, dev_workspace, workspace_bytes, (hipStream_t)stream, h->err);
+    hipStream_t st = (hipStream_t)stream;
+    float *inv, *seg;
+    int rc = network_at_head(h, "soccdpt_forward", dev_x, B, dev_workspace, workspace_bytes, st, &inv, &seg);
     if (rc) return rc;
     const bool occ_on = h->cfg.compute_occ != 0;
     if (occ_on && !dev_occ_bits) return fail(h, "soccdpt_forward: compute_occ needs dev_occ_bits");
-    {
-        ProfScope ps(h->prof, "project_voxelise", 0.0, project_bytes(h->cfg, B, S, S, dev_inv_up, dev_seg_up, dev_points), (hipStream_t)stream);
-        rc = launch_project(h->cfg, inv, seg, B, S, S, dev_inv_up, dev_seg_up, dev_points, occ_on ? dev_occ_bits : nullptr, 1,
-                            (hipStream_t)stream, h->err);
-    }
+    rc = profiled_project(h, inv, seg, B, S, S, dev_inv_up, dev_seg_up, dev_points, occ_on ? dev_occ_bits : nullptr, 1, st);
     if (rc) return rc;
-    if (occ_on && dev_occ) {
-        ProfScope ps(h->prof, "occ_expand", 0.0, occ_cells(h->cfg) * (4.0 * B + 0.125), (hipStream_t)stream);
-        rc = launch_occ_expand(h->cfg, dev_occ_bits, B, dev_occ, (hipStream_t)stream, h->err);
-    }
+    if (occ_on && dev_occ) rc = profiled_occ_expand(h, dev_occ_bits, B, dev_occ, st);
     return rc;
-}
-
-// algorithmic HBM bytes of the per-frame voxelisation: the inverse depth and the class maps once, the rows' clear
-static double voxelise_frames_bytes(const soccdpt_config& c, int B, int h, int w) {
-    return (double)B * ((double)c.cam_width * c.cam_height * 4.0 + (double)h * w * 4.0 * c.num_classes + occ_cells(c) * 0.125);
 }
 
 int soccdpt_voxelise_frames(void* handle, const float* dev_inv_up, const float* dev_seg, int B, int in_h, int in_w, uint32_t* dev_frame_bits,
@@ -394,8 +414,7 @@ int soccdpt_voxelise_frames(void* handle, const float* dev_inv_up, const float* 
     if (!h) return 1;
     if (!dev_inv_up || !dev_seg || !dev_frame_bits) return fail(h, "soccdpt_voxelise_frames: null argument");
     if (B <= 0 || in_h <= 0 || in_w <= 0) return fail(h, "soccdpt_voxelise_frames: empty input");
-    ProfScope ps(h->prof, "voxelise_frames", 0.0, voxelise_frames_bytes(h->cfg, B, in_h, in_w), (hipStream_t)stream);
-    return launch_voxelise_frames(h->cfg, dev_inv_up, dev_seg, B, in_h, in_w, dev_frame_bits, clear_bits, (hipStream_t)stream, h->err);
+    return profiled_voxelise_frames(h, dev_inv_up, dev_seg, B, in_h, in_w, dev_frame_bits, clear_bits, (hipStream_t)stream);
 }
 
 int soccdpt_occ_expand_frames(void* handle, const uint32_t* dev_frame_bits, int B, float* dev_occ, void* stream) {
@@ -403,8 +422,7 @@ int soccdpt_occ_expand_frames(void* handle, const uint32_t* dev_frame_bits, int 
     if (!h) return 1;
     if (!dev_frame_bits || !dev_occ) return fail(h, "soccdpt_occ_expand_frames: null argument");
     if (B <= 0) return fail(h, "soccdpt_occ_expand_frames: empty batch");
-    ProfScope ps(h->prof, "occ_expand_frames", 0.0, occ_cells(h->cfg) * (4.0 + 0.125) * B, (hipStream_t)stream);
-    return launch_occ_expand_frames(h->cfg, dev_frame_bits, B, dev_occ, (hipStream_t)stream, h->err);
+    return profiled_occ_expand_frames(h, dev_frame_bits, B, dev_occ, (hipStream_t)stream);
 }
 
 int soccdpt_forward_frames(void* handle, const float* dev_x, int B, float* dev_inv_up, float* dev_seg_up, float* dev_points, float* dev_occ,
@@ -417,27 +435,18 @@ int soccdpt_forward_frames(void* handle, const float* dev_x, int B, float* dev_i
     if (!dev_inv_up) return fail(h, "soccdpt_forward_frames: dev_inv_up is required (the per-frame voxelisation reads the inverse depth back)");
     if (!dev_frame_bits) return fail(h, "soccdpt_forward_frames: dev_frame_bits is required");
     const int S = h->img;
-    // the network outputs live at the head of the workspace (as in soccdpt_forward)
-    float* inv = static_cast<float*>(dev_workspace);
-    float* seg = inv + (size_t)B * S * S;
-    const size_t head = (size_t)B * S * S * (1 + h->cfg.num_classes) * sizeof(float);
-    if (workspace_bytes < head) return fail(h, "soccdpt_forward_frames: workspace too small");
     hipStream_t st = (hipStream_t)stream;
     // always eager: the per-frame passes read this call's outputs, and a captured network graph is keyed on soccdpt_forward's pointers
     const bool graph_was = h->use_graph;
     h->use_graph = false;
-    int rc = model_network(*h, dev_x, B, inv, seg, dev_workspace, workspace_bytes, st, h->err);
+    float *inv, *seg;
+    int rc = network_at_head(h, "soccdpt_forward_frames", dev_x, B, dev_workspace, workspace_bytes, st, &inv, &seg);
     h->use_graph = graph_was;
     if (rc) return rc;
-    {   // the union comes from the frame rows below, so the fused kernel skips its own marking
-        ProfScope ps(h->prof, "project_voxelise", 0.0, project_bytes(h->cfg, B, S, S, dev_inv_up, dev_seg_up, dev_points), st);
-        rc = launch_project(h->cfg, inv, seg, B, S, S, dev_inv_up, dev_seg_up, dev_points, nullptr, 0, st, h->err);
-    }
+    // the union comes from the frame rows below, so the fused kernel skips its own marking
+    rc = profiled_project(h, inv, seg, B, S, S, dev_inv_up, dev_seg_up, dev_points, nullptr, 0, st);
     if (rc) return rc;
-    {
-        ProfScope ps(h->prof, "voxelise_frames", 0.0, voxelise_frames_bytes(h->cfg, B, S, S), st);
-        rc = launch_voxelise_frames(h->cfg, dev_inv_up, seg, B, S, S, dev_frame_bits, 1, st, h->err);
-    }
+    rc = profiled_voxelise_frames(h, dev_inv_up, seg, B, S, S, dev_frame_bits, 1, st);
     if (rc) return rc;
     if (dev_occ_bits) {
         const size_t wbytes = soccdpt_occ_words(h) * sizeof(uint32_t);
@@ -446,10 +455,7 @@ int soccdpt_forward_frames(void* handle, const float* dev_x, int B, float* dev_i
         rc = launch_occ_or(h->cfg, dev_occ_bits, dev_frame_bits, B, st, h->err);
         if (rc) return rc;
     }
-    if (dev_occ) {
-        ProfScope ps(h->prof, "occ_expand_frames", 0.0, occ_cells(h->cfg) * (4.0 + 0.125) * B, st);
-        rc = launch_occ_expand_frames(h->cfg, dev_frame_bits, B, dev_occ, st, h->err);
-    }
+    if (dev_occ) rc = profiled_occ_expand_frames(h, dev_frame_bits, B, dev_occ, st);
     return rc;
 }
 

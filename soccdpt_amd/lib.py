@@ -122,6 +122,112 @@ def csrc_sha() -> str:
     return h.hexdigest()[:16]
 
 
+def _prototypes() -> dict:
+    """symbol -> (restype, argtypes) for every function include/soccdpt_hip.h declares, in the header's order.  tests/test_capi_symbols.py holds
+    this table against the header's prototypes (names, parameter counts, pointer / integer / float class and width of every position)."""
+    vp, ci, cs, cf, cd, cstr = ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t, ctypes.c_float, ctypes.c_double, ctypes.c_char_p
+    P = ctypes.POINTER
+    return {
+        # ---- lifetime ----
+        "soccdpt_create": (ci, [P(SoccdptConfig), P(vp)]),
+        "soccdpt_destroy": (None, [vp]),
+        "soccdpt_last_error": (cstr, [vp]),
+        "soccdpt_abi_version": (ci, []),
+        "soccdpt_sizeof": (cs, [ci]),
+        # ---- precision map ----
+        "soccdpt_prec_map_set": (ci, [vp, cstr, ci]),
+        "soccdpt_prec_map_get": (ci, [vp, cstr, ci]),
+        # ---- calibration of the precision map ----
+        "soccdpt_prec_calibrate_scratch_bytes": (cs, [vp, ci]),
+        "soccdpt_prec_calibrate": (ci, [vp, vp, ci, cf, vp, cs, vp, cs, vp, cs, P(CalibReport), vp]),
+        "soccdpt_prec_calibrate_ex": (ci, [vp, vp, ci, P(CalibOptions), vp, cs, vp, cs, vp, cs, P(CalibReport), vp]),
+        "soccdpt_prec_map_source": (ci, [vp]),
+        # ---- weights ----
+        "soccdpt_bind_weight": (ci, [vp, cstr, vp, ci, P(ctypes.c_int64), ci]),
+        "soccdpt_num_weights": (ci, [vp]),
+        "soccdpt_weight_key": (cstr, [vp, ci]),
+        "soccdpt_prepared_bytes": (cs, [vp]),
+        "soccdpt_workspace_bytes": (cs, [vp, ci]),
+        "soccdpt_workspace_invalidate": (ci, [vp]),
+        "soccdpt_workspace_zero_fills": (ci, [vp]),
+        "soccdpt_prepare": (ci, [vp, vp, cs, vp]),
+        # ---- the hot path ----
+        "soccdpt_forward": (ci, [vp, vp, ci, vp, vp, vp, vp, vp, vp, cs, vp]),
+        "soccdpt_set_streams": (ci, [vp, ci]),
+        "soccdpt_set_graph": (ci, [vp, ci]),
+        # ---- stage-level entry points ----
+        "soccdpt_network": (ci, [vp, vp, ci, vp, vp, vp, cs, vp]),
+        "soccdpt_project": (ci, [vp, vp, vp, ci, ci, ci, vp, vp, vp, vp, ci, vp]),
+        "soccdpt_project_backward_scratch_bytes": (cs, [vp, ci, ci]),
+        "soccdpt_project_backward": (ci, [vp, vp, vp, vp, vp, ci, ci, ci, vp, vp, vp, cs, vp]),
+        "soccdpt_occ_or": (ci, [vp, vp, vp, ci, vp]),
+        "soccdpt_occ_expand": (ci, [vp, vp, ci, vp, vp]),
+        "soccdpt_occ_zero": (ci, [vp, ci, vp, vp]),
+        "soccdpt_occ_set": (ci, [vp, vp, ci, vp, vp]),
+        "soccdpt_occ_words": (cs, [vp]),
+        # ---- per-frame occupancy grids ----
+        "soccdpt_voxelise_frames": (ci, [vp, vp, vp, ci, ci, ci, vp, ci, vp]),
+        "soccdpt_occ_expand_frames": (ci, [vp, vp, ci, vp, vp]),
+        "soccdpt_forward_frames": (ci, [vp, vp, ci, vp, vp, vp, vp, vp, vp, vp, cs, vp]),
+        # ---- occupancy evaluation ----
+        "soccdpt_occ_pack": (ci, [vp, ci, ci, cs, cf, ci, vp, vp]),
+        "soccdpt_occ_points_scratch_bytes": (cs, [ci, cs, ci]),
+        "soccdpt_occ_points_count": (ci, [vp, ci, cs, ci, vp, cs, vp, vp, vp]),
+        "soccdpt_occ_points_write": (ci, [vp, ci, P(ctypes.c_int32), ci, P(cf), vp, cs, cs, vp, vp, vp, vp]),
+        "soccdpt_occ_iou_counts": (ci, [vp, ci, vp, ci, cs, ci, vp, vp]),
+        "soccdpt_last_launch_count": (ci, [vp]),
+        "soccdpt_launch_counter": (ctypes.c_ulonglong, []),
+        # ---- evaluation metrics ----
+        "soccdpt_metrics_scratch_bytes": (cs, [ci, ci]),
+        "soccdpt_metrics_depth": (ci, [vp, vp, vp, ci, cs, vp, vp, vp]),
+        "soccdpt_metrics_iou": (ci, [vp, vp, ci, ci, cs, vp, vp, vp]),
+        # ---- per-kernel device time ----
+        "soccdpt_profile_enable": (ci, [vp, ci]),
+        "soccdpt_profile_collect": (ci, [vp, P(KernelStat), ci, P(ci)]),
+        # ---- training criterion ----
+        "soccdpt_loss_scratch_bytes": (cs, [ci, ci, ci, ci, ci]),
+        "soccdpt_training_loss": (ci, [ci, ci, ci, ci, ci, ci, ci, cf, cf, cf, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+        # ---- ground-truth occupancy generator ----
+        "soccdpt_gt_occupancy": (ci, [ci, ci, ci, ci, vp, vp, vp, vp, vp, vp, cf, vp, vp, vp, vp, vp, vp, vp]),
+        "soccdpt_op_mlp_ln": (ci, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, vp]),
+        # ---- input transform ----
+        "soccdpt_input_transform_u8": (ci, [vp, ci, ci, ci, ci, ci, P(cd), P(cd), vp, vp]),
+        "soccdpt_adam_step": (ci, [ci, vp, vp, vp, vp, vp, cd, cd, cd, cd, cd, ci, vp]),
+        # ---- in-network tile tuning ----
+        "soccdpt_profile_sites": (ci, [vp, ci]),
+        "soccdpt_site_count": (ci, [vp]),
+        "soccdpt_site_get": (ci, [vp, ci, P(ci), P(ci), P(ci), P(ci), P(ci), P(ci)]),
+        "soccdpt_tune_set": (ci, [vp, ci, ci, ci, ci, ci]),
+        "soccdpt_tune_clear": (ci, [vp]),
+        # ---- kernel-level entry points ----
+        "soccdpt_op_igemm": (ci, [P(IgemmArgs), vp]),
+        "soccdpt_op_depth_tail": (ci, [vp, vp, vp, vp, cf, vp, ci, ci, ci, ci, vp]),
+        "soccdpt_op_seg_tail": (ci, [vp, ci, vp, vp, vp, ci, ci, ci, ci, vp]),
+        "soccdpt_op_gn_finish": (ci, [vp, vp, ci, ci, ci, ci, ci, cf, vp]),
+        "soccdpt_op_gn_apply": (ci, [vp, vp, vp, ci, vp, vp, vp, vp, vp, ci, vp, vp, vp, vp, vp, vp, ci, ci, cs, ci, ci, ci, ci, cf, vp]),
+        "soccdpt_op_vit_attention": (ci, [vp, vp, ci, ci, ci, ci, vp]),
+        "soccdpt_op_wgrad_tn": (ci, [vp, ctypes.c_long, vp, ctypes.c_long, cs, ci, ci, ci, ci, ci, vp, cs, vp, vp]),
+        "soccdpt_op_window_attention": (ci, [vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, vp]),
+        "soccdpt_op_window_attention_qkv": (ci, [vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, vp, vp]),
+        "soccdpt_op_wino_weights": (ci, [vp, vp, vp, ci, ci, ci, vp]),
+        "soccdpt_op_wino_conv": (ci, [vp, vp, ci, ci, ci, ci, ci, vp, vp, vp, ci, ci, ci, ci, vp, vp, ci, ci, ci, vp, vp]),
+        # ---- training step ----
+        "soccdpt_bind_grad": (ci, [vp, cstr, vp]),
+        "soccdpt_train_set_amp": (ci, [vp, ci]),
+        "soccdpt_train_set_drop_path": (ci, [vp, cf]),
+        "soccdpt_train_unscale": (ci, [vp, cs, cf, vp, vp]),
+        "soccdpt_train_workspace_bytes": (cs, [vp, ci]),
+        "soccdpt_train_forward": (ci, [vp, vp, ci, vp, vp, vp, cs, cf, ctypes.c_uint32, vp]),
+        "soccdpt_train_backward": (ci, [vp, vp, ci, vp, vp, vp, cs, vp]),
+        "soccdpt_train_backward_encoder": (ci, [vp, ci, P(vp), vp, cs, vp]),
+        "soccdpt_train_workspace_tensor": (ci, [vp, ci, cstr, P(cs), P(cs)]),
+        "soccdpt_workspace_tensor": (ci, [vp, ci, cstr, P(cs), P(cs), P(ci), P(ci), P(ci), P(ci)]),
+    }
+
+
+PROTOTYPES = _prototypes()
+
+
 def load_library() -> ctypes.CDLL:
     """Load libsoccdpt_hip.so; fail loudly when it has not been built."""
     global _lib
@@ -132,153 +238,9 @@ def load_library() -> ctypes.CDLL:
             f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "(make -C soccdpt_amd/csrc).  The SOccDPT MI355X path has no CPU fallback.")
     L = ctypes.CDLL(LIB_PATH)
-    vp, ci, cs = ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t
-    L.soccdpt_abi_version.restype = ci
-    L.soccdpt_create.argtypes = [ctypes.POINTER(SoccdptConfig), ctypes.POINTER(vp)]
-    L.soccdpt_create.restype = ci
-    L.soccdpt_destroy.argtypes = [vp]
-    L.soccdpt_destroy.restype = None
-    L.soccdpt_last_error.argtypes = [vp]
-    L.soccdpt_last_error.restype = ctypes.c_char_p
-    L.soccdpt_bind_weight.argtypes = [vp, ctypes.c_char_p, vp, ci, ctypes.POINTER(ctypes.c_int64), ci]
-    L.soccdpt_bind_weight.restype = ci
-    L.soccdpt_num_weights.argtypes = [vp]
-    L.soccdpt_num_weights.restype = ci
-    L.soccdpt_weight_key.argtypes = [vp, ci]
-    L.soccdpt_weight_key.restype = ctypes.c_char_p
-    L.soccdpt_prepared_bytes.argtypes = [vp]
-    L.soccdpt_prepared_bytes.restype = cs
-    L.soccdpt_workspace_bytes.argtypes = [vp, ci]
-    L.soccdpt_workspace_bytes.restype = cs
-    L.soccdpt_workspace_invalidate.argtypes = [vp]
-    L.soccdpt_workspace_invalidate.restype = ci
-    L.soccdpt_workspace_zero_fills.argtypes = [vp]
-    L.soccdpt_workspace_zero_fills.restype = ci
-    L.soccdpt_prepare.argtypes = [vp, vp, cs, vp]
-    L.soccdpt_prepare.restype = ci
-    L.soccdpt_forward.argtypes = [vp, vp, ci, vp, vp, vp, vp, vp, vp, cs, vp]
-    L.soccdpt_forward.restype = ci
-    L.soccdpt_network.argtypes = [vp, vp, ci, vp, vp, vp, cs, vp]
-    L.soccdpt_network.restype = ci
-    L.soccdpt_project.argtypes = [vp, vp, vp, ci, ci, ci, vp, vp, vp, vp, ci, vp]
-    L.soccdpt_bind_grad.argtypes = [vp, ctypes.c_char_p, vp]
-    L.soccdpt_train_set_amp.argtypes = [vp, ci]
-    L.soccdpt_train_set_drop_path.argtypes = [vp, ctypes.c_float]
-    L.soccdpt_train_unscale.argtypes = [vp, cs, ctypes.c_float, vp, vp]
-    L.soccdpt_train_workspace_bytes.argtypes = [vp, ci]
-    L.soccdpt_train_workspace_bytes.restype = cs
-    L.soccdpt_train_forward.argtypes = [vp, vp, ci, vp, vp, vp, cs, ctypes.c_float, ctypes.c_uint32, vp]
-    L.soccdpt_train_backward.argtypes = [vp, vp, ci, vp, vp, vp, cs, vp]
-    L.soccdpt_train_backward_encoder.argtypes = [vp, ci, ctypes.POINTER(vp), vp, cs, vp]
-    L.soccdpt_train_workspace_tensor.argtypes = [vp, ci, ctypes.c_char_p, ctypes.POINTER(cs), ctypes.POINTER(cs)]
-    L.soccdpt_project.restype = ci
-    L.soccdpt_project_backward_scratch_bytes.argtypes = [vp, ci, ci]
-    L.soccdpt_project_backward_scratch_bytes.restype = cs
-    L.soccdpt_project_backward.argtypes = [vp, vp, vp, vp, vp, ci, ci, ci, vp, vp, vp, cs, vp]
-    L.soccdpt_project_backward.restype = ci
-    L.soccdpt_occ_or.argtypes = [vp, vp, vp, ci, vp]
-    L.soccdpt_occ_or.restype = ci
-    L.soccdpt_occ_expand.argtypes = [vp, vp, ci, vp, vp]
-    L.soccdpt_occ_expand.restype = ci
-    L.soccdpt_occ_words.argtypes = [vp]
-    L.soccdpt_occ_words.restype = cs
-    L.soccdpt_voxelise_frames.argtypes = [vp, vp, vp, ci, ci, ci, vp, ci, vp]
-    L.soccdpt_voxelise_frames.restype = ci
-    L.soccdpt_occ_expand_frames.argtypes = [vp, vp, ci, vp, vp]
-    L.soccdpt_occ_expand_frames.restype = ci
-    L.soccdpt_forward_frames.argtypes = [vp, vp, ci, vp, vp, vp, vp, vp, vp, vp, cs, vp]
-    L.soccdpt_forward_frames.restype = ci
-    L.soccdpt_occ_pack.argtypes = [vp, ci, ci, cs, ctypes.c_float, ci, vp, vp]
-    L.soccdpt_occ_pack.restype = ci
-    L.soccdpt_occ_points_scratch_bytes.argtypes = [ci, cs, ci]
-    L.soccdpt_occ_points_scratch_bytes.restype = cs
-    L.soccdpt_occ_points_count.argtypes = [vp, ci, cs, ci, vp, cs, vp, vp, vp]
-    L.soccdpt_occ_points_count.restype = ci
-    L.soccdpt_occ_points_write.argtypes = [vp, ci, ctypes.POINTER(ctypes.c_int32), ci, ctypes.POINTER(ctypes.c_float), vp, cs, cs, vp, vp, vp, vp]
-    L.soccdpt_occ_points_write.restype = ci
-    L.soccdpt_occ_iou_counts.argtypes = [vp, ci, vp, ci, cs, ci, vp, vp]
-    L.soccdpt_occ_iou_counts.restype = ci
-    L.soccdpt_last_launch_count.argtypes = [vp]
-    L.soccdpt_last_launch_count.restype = ci
-    L.soccdpt_launch_counter.argtypes = []
-    L.soccdpt_launch_counter.restype = ctypes.c_ulonglong
-    L.soccdpt_metrics_scratch_bytes.argtypes = [ci, ci]
-    L.soccdpt_metrics_scratch_bytes.restype = cs
-    L.soccdpt_metrics_depth.argtypes = [vp, vp, vp, ci, cs, vp, vp, vp]
-    L.soccdpt_metrics_depth.restype = ci
-    L.soccdpt_metrics_iou.argtypes = [vp, vp, ci, ci, cs, vp, vp, vp]
-    L.soccdpt_metrics_iou.restype = ci
-    cf = ctypes.c_float
-    L.soccdpt_loss_scratch_bytes.argtypes = [ci, ci, ci, ci, ci]
-    L.soccdpt_loss_scratch_bytes.restype = cs
-    L.soccdpt_training_loss.argtypes = [ci, ci, ci, ci, ci, ci, ci, cf, cf, cf, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
-    L.soccdpt_training_loss.restype = ci
-    cd = ctypes.c_double
-    L.soccdpt_profile_sites.argtypes = [vp, ci]
-    L.soccdpt_site_count.argtypes = [vp]
-    ip = ctypes.POINTER(ctypes.c_int)
-    L.soccdpt_site_get.argtypes = [vp, ci, ip, ip, ip, ip, ip, ip]
-    L.soccdpt_tune_set.argtypes = [vp, ci, ci, ci, ci, ci]
-    L.soccdpt_tune_clear.argtypes = [vp]
-    L.soccdpt_gt_occupancy.argtypes = [ci, ci, ci, ci, vp, vp, vp, vp, vp, vp, cf, vp, vp, vp, vp, vp, vp, vp]
-    L.soccdpt_gt_occupancy.restype = ci
-    L.soccdpt_input_transform_u8.argtypes = [vp, ci, ci, ci, ci, ci, ctypes.POINTER(cd), ctypes.POINTER(cd), vp, vp]
-    L.soccdpt_input_transform_u8.restype = ci
-    L.soccdpt_op_gn_finish.argtypes = [vp, vp, ci, ci, ci, ci, ci, ctypes.c_float, vp]
-    L.soccdpt_op_gn_finish.restype = ci
-    L.soccdpt_op_gn_apply.argtypes = [vp, vp, vp, ci, vp, vp, vp, vp, vp, ci, vp, vp, vp, vp, vp, vp, ci, ci, ctypes.c_size_t, ci, ci, ci, ci, ctypes.c_float, vp]
-    L.soccdpt_op_gn_apply.restype = ci
-    L.soccdpt_op_mlp_ln.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, vp]
-    L.soccdpt_op_mlp_ln.restype = ci
-    L.soccdpt_adam_step.argtypes = [ci, vp, vp, vp, vp, vp, cd, cd, cd, cd, cd, ci, vp]
-    L.soccdpt_adam_step.restype = ci
-    L.soccdpt_set_streams.argtypes = [vp, ci]
-    L.soccdpt_set_streams.restype = ci
-    L.soccdpt_set_graph.argtypes = [vp, ci]
-    L.soccdpt_set_graph.restype = ci
-    L.soccdpt_profile_enable.argtypes = [vp, ci]
-    L.soccdpt_profile_enable.restype = ci
-    L.soccdpt_profile_collect.argtypes = [vp, ctypes.POINTER(KernelStat), ci, ctypes.POINTER(ci)]
-    L.soccdpt_profile_collect.restype = ci
-    L.soccdpt_op_igemm.argtypes = [ctypes.POINTER(IgemmArgs), vp]
-    L.soccdpt_op_igemm.restype = ci
-    L.soccdpt_op_vit_attention.argtypes = [vp, vp, ci, ci, ci, ci, vp]
-    L.soccdpt_op_vit_attention.restype = ci
-    L.soccdpt_op_window_attention.argtypes = [vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, vp]
-    L.soccdpt_op_window_attention.restype = ci
-    L.soccdpt_op_window_attention_qkv.argtypes = [vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, vp, vp]
-    L.soccdpt_op_window_attention_qkv.restype = ci
-    L.soccdpt_op_wino_weights.argtypes = [vp, vp, vp, ci, ci, ci, vp]
-    L.soccdpt_op_wino_weights.restype = ci
-    L.soccdpt_op_wino_conv.argtypes = [vp, vp, ci, ci, ci, ci, ci, vp, vp, vp, ci, ci, ci, ci, vp, vp, ci, ci, ci, vp, vp]
-    L.soccdpt_op_wino_conv.restype = ci
-    L.soccdpt_op_depth_tail.argtypes = [vp, vp, vp, vp, ctypes.c_float, vp, ci, ci, ci, ci, vp]
-    L.soccdpt_op_depth_tail.restype = ci
-    L.soccdpt_op_seg_tail.argtypes = [vp, ci, vp, vp, vp, ci, ci, ci, ci, vp]
-    L.soccdpt_op_seg_tail.restype = ci
-    L.soccdpt_op_wgrad_tn.argtypes = [vp, ctypes.c_long, vp, ctypes.c_long, ctypes.c_size_t, ci, ci, ci, ci, ci, vp, ctypes.c_size_t, vp, vp]
-    L.soccdpt_op_wgrad_tn.restype = ci
-    L.soccdpt_workspace_tensor.argtypes = [vp, ci, ctypes.c_char_p, ctypes.POINTER(cs), ctypes.POINTER(cs),
-                                           ctypes.POINTER(ci), ctypes.POINTER(ci), ctypes.POINTER(ci), ctypes.POINTER(ci)]
-    L.soccdpt_workspace_tensor.restype = ci
-    L.soccdpt_occ_zero.argtypes = [vp, ci, vp, vp]
-    L.soccdpt_occ_zero.restype = ci
-    L.soccdpt_occ_set.argtypes = [vp, vp, ci, vp, vp]
-    L.soccdpt_occ_set.restype = ci
-    L.soccdpt_sizeof.argtypes = [ci]
-    L.soccdpt_sizeof.restype = cs
-    L.soccdpt_prec_map_set.argtypes = [vp, ctypes.c_char_p, ci]
-    L.soccdpt_prec_map_set.restype = ci
-    L.soccdpt_prec_map_get.argtypes = [vp, ctypes.c_char_p, ci]
-    L.soccdpt_prec_map_get.restype = ci
-    L.soccdpt_prec_calibrate_scratch_bytes.argtypes = [vp, ci]
-    L.soccdpt_prec_calibrate_scratch_bytes.restype = cs
-    L.soccdpt_prec_calibrate.argtypes = [vp, vp, ci, ctypes.c_float, vp, cs, vp, cs, vp, cs, ctypes.POINTER(CalibReport), vp]
-    L.soccdpt_prec_calibrate.restype = ci
-    L.soccdpt_prec_calibrate_ex.argtypes = [vp, vp, ci, ctypes.POINTER(CalibOptions), vp, cs, vp, cs, vp, cs, ctypes.POINTER(CalibReport), vp]
-    L.soccdpt_prec_calibrate_ex.restype = ci
-    L.soccdpt_prec_map_source.argtypes = [vp]
-    L.soccdpt_prec_map_source.restype = ci
+    for symbol, (restype, argtypes) in PROTOTYPES.items():
+        fn = getattr(L, symbol)
+        fn.restype, fn.argtypes = restype, argtypes
     if L.soccdpt_abi_version() != ABI_VERSION:
         raise RuntimeError("libsoccdpt_hip.so ABI version mismatch; rebuild the library")
     # the ctypes mirrors of the public structs must have the layout the library was compiled with (include/soccdpt_hip.h)
@@ -298,6 +260,21 @@ def _ptr(t: Optional[torch.Tensor]) -> Optional[int]:
 
 def _stream_ptr(device: torch.device) -> int:
     return torch.cuda.current_stream(device).cuda_stream
+
+
+def _call(symbol: str, *args, device: torch.device, guard: bool = True):
+    """One handle-less entry point (op_*, occupancy evaluation, metrics, criterion, Adam, ground-truth occupancy, input transform) on the current
+    stream of `device`, which goes last in every such prototype; guard=False leaves the current device alone, as the kernel-level op_* entries do."""
+    L = load_library()
+    fn = getattr(L, symbol)
+    if guard:
+        with torch.cuda.device(device):
+            rc = fn(*args, _stream_ptr(device))
+    else:
+        rc = fn(*args, _stream_ptr(device))
+    if rc != 0:
+        raise RuntimeError(f"{symbol} failed: {L.soccdpt_last_error(None).decode()}")
+
 
 
 def host_rotation_matrices(angles: Sequence[float]) -> np.ndarray:
@@ -376,10 +353,12 @@ class Engine:
             raise RuntimeError("soccdpt_create failed: " + self.L.soccdpt_last_error(None).decode())
         self._prepared: Optional[torch.Tensor] = None
         self._workspace: Optional[torch.Tensor] = None
+        self._train_ws: Optional[torch.Tensor] = None
         self._bound = {}
+        self._grads = {}
 
     def close(self):
-        if getattr(self, "_h", None):
+        if getattr(self, "_h", None):   # __del__ also runs when __init__ raised before the handle existed
             self.L.soccdpt_destroy(self._h)
             self._h = None
 
@@ -389,9 +368,20 @@ class Engine:
         except Exception:
             pass
 
-    def _check(self, rc: int, what: str):
+    def _fail(self, symbol: str):
+        raise RuntimeError(f"{symbol} failed: {self.L.soccdpt_last_error(self._h).decode()}")
+
+    def _call(self, symbol: str, *args, stream: bool = False):
+        """One entry point that takes the handle first.  stream=True: it launches, so it runs under this engine's device with the device's current
+        stream as its last argument; the others (setters, queries) take neither."""
+        fn = getattr(self.L, symbol)
+        if stream:
+            with torch.cuda.device(self.device):
+                rc = fn(self._h, *args, _stream_ptr(self.device))
+        else:
+            rc = fn(self._h, *args)
         if rc != 0:
-            raise RuntimeError(f"{what} failed: {self.L.soccdpt_last_error(self._h).decode()}")
+            self._fail(symbol)
 
     # ---- weights ----
     def weight_keys(self):
@@ -405,18 +395,21 @@ class Engine:
         rc = self.L.soccdpt_bind_weight(self._h, key.encode(), t.data_ptr(), 0, shape, t.dim())
         if rc == 2:
             return False
-        self._check(rc, "soccdpt_bind_weight")
+        if rc != 0:
+            self._fail("soccdpt_bind_weight")
         self._bound[key] = t  # keep alive
         return True
 
-    def prepare(self):
+    def _prepared_arena(self) -> int:
+        """Grow the arena of prepared weights to what the library asks for now -> that byte count (the arena itself only grows)."""
         nbytes = self.L.soccdpt_prepared_bytes(self._h)
         if self._prepared is None or self._prepared.numel() < nbytes:
             self._prepared = torch.zeros(max(nbytes, 16), dtype=torch.uint8, device=self.device)
-        with torch.cuda.device(self.device):
-            self._check(self.L.soccdpt_prepare(self._h, self._prepared.data_ptr(), nbytes, _stream_ptr(self.device)),
-                        "soccdpt_prepare")
+        return nbytes
 
+    def prepare(self):
+        nbytes = self._prepared_arena()
+        self._call("soccdpt_prepare", self._prepared.data_ptr(), nbytes, stream=True)
 
     # ---- precision map (PREC_MIXED handles) ----
     def prec_map(self) -> dict:
@@ -430,7 +423,7 @@ class Engine:
         """Set one group ('s2.b0.attn'), a prefix ('s2.*') or everything ('*') to PREC_F16 / PREC_F16X3; re-prepares the weights."""
         n = self.L.soccdpt_prec_map_set(self._h, group.encode(), int(fmt))
         if n < 0:
-            raise RuntimeError("soccdpt_prec_map_set failed: " + self.L.soccdpt_last_error(self._h).decode())
+            self._fail("soccdpt_prec_map_set")
         if self._bound:
             self.prepare()
         return n
@@ -454,14 +447,11 @@ class Engine:
         if nb == 0:
             raise RuntimeError("soccdpt_prec_calibrate: only SOCCDPT_PREC_MIXED handles have a precision map to calibrate")
         scratch = torch.empty(nb, dtype=torch.uint8, device=self.device)
-        npre = self.L.soccdpt_prepared_bytes(self._h)
-        if self._prepared is None or self._prepared.numel() < npre:
-            self._prepared = torch.zeros(max(npre, 16), dtype=torch.uint8, device=self.device)
+        self._prepared_arena()
         ws = self.workspace(B)
         rep = CalibReport()
-        with torch.cuda.device(self.device):
-            self._check(self.L.soccdpt_prec_calibrate_ex(self._h, x.data_ptr(), B, ctypes.byref(opt), self._prepared.data_ptr(), self._prepared.numel(), ws.data_ptr(), ws.numel(),
-                                                         scratch.data_ptr(), nb, ctypes.byref(rep), _stream_ptr(self.device)), "soccdpt_prec_calibrate_ex")
+        self._call("soccdpt_prec_calibrate_ex", x.data_ptr(), B, ctypes.byref(opt), self._prepared.data_ptr(), self._prepared.numel(), ws.data_ptr(), ws.numel(),
+                   scratch.data_ptr(), nb, ctypes.byref(rep), stream=True)
         out = {k: getattr(rep, k) for k, _ in CalibReport._fields_ if not k.startswith("err_")}
         out["err_holdout"] = dict(zip(CALIB_QUANTITIES, (float(v) for v in rep.err_holdout))) if rep.holdout_frames else None
         out["err_calibrated"] = dict(zip(CALIB_QUANTITIES, (float(v) for v in rep.err_calibrated)))
@@ -488,10 +478,7 @@ class Engine:
     # ---- stage-level calls ----
     def project(self, inv: torch.Tensor, seg: torch.Tensor, inv_up, seg_up, points, occ_bits, clear_bits: bool = True):
         B, h, w = inv.shape
-        with torch.cuda.device(self.device):
-            self._check(self.L.soccdpt_project(self._h, _ptr(inv), _ptr(seg), B, h, w, _ptr(inv_up), _ptr(seg_up),
-                                               _ptr(points), _ptr(occ_bits), 1 if clear_bits else 0,
-                                               _stream_ptr(self.device)), "soccdpt_project")
+        self._call("soccdpt_project", _ptr(inv), _ptr(seg), B, h, w, _ptr(inv_up), _ptr(seg_up), _ptr(points), _ptr(occ_bits), 1 if clear_bits else 0, stream=True)
 
     def project_backward(self, inv_up: torch.Tensor, d_inv_up, d_seg_up, d_points, in_h: int, in_w: int):
         """Gradients of the projection stage's differentiable outputs w.r.t. the network outputs (soccdpt_project_backward):
@@ -504,38 +491,33 @@ class Engine:
         scratch = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=self.device)
         prep = lambda t: None if t is None else t.detach().to(torch.float32).contiguous()
         a, b, c = prep(d_inv_up), prep(d_seg_up), prep(d_points)
-        with torch.cuda.device(self.device):
-            self._check(self.L.soccdpt_project_backward(self._h, _ptr(inv_up.contiguous()), _ptr(a), _ptr(b), _ptr(c), B, in_h, in_w, _ptr(d_inv), _ptr(d_seg),
-                                                        scratch.data_ptr(), scratch.numel(), _stream_ptr(self.device)), "soccdpt_project_backward")
+        self._call("soccdpt_project_backward", _ptr(inv_up.contiguous()), _ptr(a), _ptr(b), _ptr(c), B, in_h, in_w, _ptr(d_inv), _ptr(d_seg),
+                   scratch.data_ptr(), scratch.numel(), stream=True)
         return d_inv, d_seg
 
     # ---- in-network tile tuning (tools/autotune_network.py) ----
     def profile_sites(self, on: bool):
-        self._check(self.L.soccdpt_profile_sites(self._h, int(bool(on))), "soccdpt_profile_sites")
+        self._call("soccdpt_profile_sites", int(bool(on)))
 
     def sites(self):
         out = []
         for i in range(self.L.soccdpt_site_count(self._h)):
             v = [ctypes.c_int() for _ in range(6)]
-            self._check(self.L.soccdpt_site_get(self._h, i, *[ctypes.byref(x) for x in v]), "soccdpt_site_get")
+            self._call("soccdpt_site_get", i, *[ctypes.byref(x) for x in v])
             out.append(dict(site=f"site{i:03d}", M=v[0].value, N=v[1].value, K=v[2].value, taps=v[3].value, cfg=v[4].value, launches=v[5].value))
         return out
 
     def tune_set(self, M: int, N: int, K: int, taps: int, cfg: int):
-        self._check(self.L.soccdpt_tune_set(self._h, M, N, K, taps, cfg), "soccdpt_tune_set")
+        self._call("soccdpt_tune_set", M, N, K, taps, cfg)
 
     def tune_clear(self):
-        self._check(self.L.soccdpt_tune_clear(self._h), "soccdpt_tune_clear")
+        self._call("soccdpt_tune_clear")
 
     def occ_or(self, dst_bits: torch.Tensor, src_bits: torch.Tensor, n_sets: int):
-        with torch.cuda.device(self.device):
-            self._check(self.L.soccdpt_occ_or(self._h, _ptr(dst_bits), _ptr(src_bits), n_sets, _stream_ptr(self.device)),
-                        "soccdpt_occ_or")
+        self._call("soccdpt_occ_or", _ptr(dst_bits), _ptr(src_bits), n_sets, stream=True)
 
     def occ_expand(self, bits: torch.Tensor, B: int, occ: torch.Tensor):
-        with torch.cuda.device(self.device):
-            self._check(self.L.soccdpt_occ_expand(self._h, _ptr(bits), B, _ptr(occ), _stream_ptr(self.device)),
-                        "soccdpt_occ_expand")
+        self._call("soccdpt_occ_expand", _ptr(bits), B, _ptr(occ), stream=True)
 
     # ---- per-frame occupancy grids (include/soccdpt_hip.h: soccdpt_voxelise_frames / soccdpt_occ_expand_frames / soccdpt_forward_frames) ----
     def voxelise_frames(self, inv_up: torch.Tensor, seg: torch.Tensor, frame_bits: torch.Tensor, clear_bits: bool = True):
@@ -544,72 +526,57 @@ class Engine:
         B, h, w = seg.shape[0], seg.shape[2], seg.shape[3]
         assert tuple(inv_up.shape) == (B, self.cfg.cam_height, self.cfg.cam_width) and inv_up.dtype == torch.float32 and seg.dtype == torch.float32
         assert frame_bits.dtype == torch.int32 and frame_bits.numel() == B * self.occ_words()
-        with torch.cuda.device(self.device):
-            self._check(self.L.soccdpt_voxelise_frames(self._h, _ptr(inv_up), _ptr(seg), B, h, w, _ptr(frame_bits), 1 if clear_bits else 0,
-                                                       _stream_ptr(self.device)), "soccdpt_voxelise_frames")
+        self._call("soccdpt_voxelise_frames", _ptr(inv_up), _ptr(seg), B, h, w, _ptr(frame_bits), 1 if clear_bits else 0, stream=True)
 
     def occ_expand_frames(self, frame_bits: torch.Tensor, B: int, occ: torch.Tensor):
         """frame_bits [B, occ_words()] -> occ [B,g0,g1,g2,C] f32, row b from row b."""
         assert frame_bits.dtype == torch.int32 and frame_bits.numel() == B * self.occ_words() and occ.dtype == torch.float32
-        with torch.cuda.device(self.device):
-            self._check(self.L.soccdpt_occ_expand_frames(self._h, _ptr(frame_bits), B, _ptr(occ), _stream_ptr(self.device)),
-                        "soccdpt_occ_expand_frames")
+        self._call("soccdpt_occ_expand_frames", _ptr(frame_bits), B, _ptr(occ), stream=True)
 
     def forward_frames(self, x: torch.Tensor, inv_up, seg_up, points, occ, occ_bits, frame_bits):
         """`forward` with per-frame occupancy rows: occ (optional) and frame_bits [B, occ_words()] hold frame b's grid in row b, occ_bits (optional)
         the union as `forward` writes it.  Always eager (no hipGraph replay)."""
         B = x.shape[0]
         ws = self.workspace(B)
-        with torch.cuda.device(self.device):
-            self._check(self.L.soccdpt_forward_frames(self._h, _ptr(x), B, _ptr(inv_up), _ptr(seg_up), _ptr(points), _ptr(occ), _ptr(occ_bits),
-                                                      _ptr(frame_bits), ws.data_ptr(), ws.numel(), _stream_ptr(self.device)),
-                        "soccdpt_forward_frames")
+        self._call("soccdpt_forward_frames", _ptr(x), B, _ptr(inv_up), _ptr(seg_up), _ptr(points), _ptr(occ), _ptr(occ_bits), _ptr(frame_bits),
+                   ws.data_ptr(), ws.numel(), stream=True)
 
     def occ_zero(self, B: int, occ: torch.Tensor):
-        with torch.cuda.device(self.device):
-            self._check(self.L.soccdpt_occ_zero(self._h, B, _ptr(occ), _stream_ptr(self.device)), "soccdpt_occ_zero")
+        self._call("soccdpt_occ_zero", B, _ptr(occ), stream=True)
 
     def occ_set(self, bits: torch.Tensor, B: int, occ: torch.Tensor):
-        with torch.cuda.device(self.device):
-            self._check(self.L.soccdpt_occ_set(self._h, _ptr(bits), B, _ptr(occ), _stream_ptr(self.device)), "soccdpt_occ_set")
+        self._call("soccdpt_occ_set", _ptr(bits), B, _ptr(occ), stream=True)
 
     def network(self, x: torch.Tensor, inv256: torch.Tensor, seg256: torch.Tensor):
         B = x.shape[0]
         ws = self.workspace(B)
-        with torch.cuda.device(self.device):
-            self._check(self.L.soccdpt_network(self._h, _ptr(x), B, _ptr(inv256), _ptr(seg256), ws.data_ptr(), ws.numel(),
-                                               _stream_ptr(self.device)), "soccdpt_network")
+        self._call("soccdpt_network", _ptr(x), B, _ptr(inv256), _ptr(seg256), ws.data_ptr(), ws.numel(), stream=True)
 
     # ---- training step (include/soccdpt_hip.h: soccdpt_train_*) ----
     def bind_grad(self, key: str, g: Optional[torch.Tensor]):
         """Gradient destination of one weight (written by train_backward); None freezes the weight."""
         if g is not None:
             assert g.device.type == "cuda" and g.dtype == torch.float32 and g.is_contiguous(), key
-        self._check(self.L.soccdpt_bind_grad(self._h, key.encode(), _ptr(g)), "soccdpt_bind_grad")
-        self._grads = getattr(self, "_grads", {})
+        self._call("soccdpt_bind_grad", key.encode(), _ptr(g))
         self._grads[key] = g  # keep alive
 
     def train_set_amp(self, mode):
         """0 / False: f32; 1 / True / "bf16": bf16 operands for the gradient GEMMs; 2 / "f16": fp16 operands (use a GradScaler);
         3 / "x3" / "f16x3": split-fp16 operands (three fp16 MFMAs per product): f32-grade gradients, no loss scaling needed."""
         code = {False: 0, True: 1, 0: 0, 1: 1, 2: 2, 3: 3, "bf16": 1, "f16": 2, "fp16": 2, "x3": 3, "f16x3": 3, None: 0}[mode]
-        self._check(self.L.soccdpt_train_set_amp(self._h, code), "soccdpt_train_set_amp")
+        self._call("soccdpt_train_set_amp", code)
 
     def train_set_drop_path(self, rate: float):
         """Stochastic-depth rate of the Swin-V2 encoder's train-mode forward (timm drop_path_rate; 0 = off)."""
-        self._check(self.L.soccdpt_train_set_drop_path(self._h, float(rate)), "soccdpt_train_set_drop_path")
+        self._call("soccdpt_train_set_drop_path", float(rate))
 
     def train_unscale(self, grads: torch.Tensor, inv_scale: float, found_inf: torch.Tensor):
         assert grads.is_contiguous() and grads.dtype == torch.float32 and found_inf.dtype == torch.int32
-        with torch.cuda.device(self.device):
-            rc = self.L.soccdpt_train_unscale(grads.data_ptr(), grads.numel(), float(inv_scale), found_inf.data_ptr(), _stream_ptr(self.device))
-        if rc != 0:
-            raise RuntimeError("soccdpt_train_unscale failed: " + self.L.soccdpt_last_error(None).decode())
+        _call("soccdpt_train_unscale", grads.data_ptr(), grads.numel(), float(inv_scale), found_inf.data_ptr(), device=self.device)
 
     def train_workspace(self, B: int) -> torch.Tensor:
         nbytes = self.L.soccdpt_train_workspace_bytes(self._h, B)
-        cur = getattr(self, "_train_ws", None)
-        if cur is None or cur.numel() < nbytes:
+        if self._train_ws is None or self._train_ws.numel() < nbytes:
             self._train_ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=self.device)
         return self._train_ws
 
@@ -618,72 +585,61 @@ class Engine:
         ws = self.train_workspace(B)
         keep = [t.detach().to(torch.float32).contiguous() for t in d_feats]
         arr = (ctypes.c_void_p * 4)(*[t.data_ptr() for t in keep])
-        with torch.cuda.device(self.device):
-            self._check(self.L.soccdpt_train_backward_encoder(self._h, B, arr, ws.data_ptr(), ws.numel(), _stream_ptr(self.device)),
-                        "soccdpt_train_backward_encoder")
+        self._call("soccdpt_train_backward_encoder", B, arr, ws.data_ptr(), ws.numel(), stream=True)
+
+    def _train_bytes(self, B: int, name: str, elem_bytes: int) -> torch.Tensor:
+        """The bytes of one named buffer of the training workspace (soccdpt_train_workspace_tensor gives its offset and element count)."""
+        off, n = ctypes.c_size_t(), ctypes.c_size_t()
+        if self.L.soccdpt_train_workspace_tensor(self._h, B, name.encode(), ctypes.byref(off), ctypes.byref(n)) != 0:
+            raise KeyError(name)
+        return self.train_workspace(B)[off.value: off.value + elem_bytes * n.value]
 
     def train_tensor(self, B: int, name: str, channels: int) -> torch.Tensor:
         """A saved activation / gradient of the training workspace as an f32 [pixels, channels] view (see soccdpt_train_workspace_tensor)."""
-        off, n = ctypes.c_size_t(), ctypes.c_size_t()
-        if self.L.soccdpt_train_workspace_tensor(self._h, B, name.encode(), ctypes.byref(off), ctypes.byref(n)) != 0:
-            raise KeyError(name)
-        ws = self.train_workspace(B)
-        return ws[off.value: off.value + 4 * n.value].view(torch.float32).view(-1, channels)
+        return self._train_bytes(B, name, 4).view(torch.float32).view(-1, channels)
 
     def train_bytes(self, B: int, name: str, channels: int) -> torch.Tensor:
         """A uint8 buffer of the training workspace ("seg_keep", "hy.pool_idx") as a [pixels, channels] view."""
-        off, n = ctypes.c_size_t(), ctypes.c_size_t()
-        if self.L.soccdpt_train_workspace_tensor(self._h, B, name.encode(), ctypes.byref(off), ctypes.byref(n)) != 0:
-            raise KeyError(name)
-        ws = self.train_workspace(B)
-        return ws[off.value: off.value + n.value].view(-1, channels)
+        return self._train_bytes(B, name, 1).view(-1, channels)
 
     def train_forward(self, x: torch.Tensor, inv: torch.Tensor, seg: torch.Tensor, dropout_p: float = 0.1, seed: int = 0):
         B = x.shape[0]
         ws = self.train_workspace(B)
-        with torch.cuda.device(self.device):
-            self._check(self.L.soccdpt_train_forward(self._h, _ptr(x), B, _ptr(inv), _ptr(seg), ws.data_ptr(), ws.numel(), float(dropout_p),
-                                                     int(seed) & 0xFFFFFFFF, _stream_ptr(self.device)), "soccdpt_train_forward")
+        self._call("soccdpt_train_forward", _ptr(x), B, _ptr(inv), _ptr(seg), ws.data_ptr(), ws.numel(), float(dropout_p), int(seed) & 0xFFFFFFFF, stream=True)
 
     def train_backward(self, x: torch.Tensor, d_inv: torch.Tensor, d_seg: torch.Tensor):
         B = x.shape[0]
         ws = self.train_workspace(B)
         assert d_inv.is_contiguous() and d_seg.is_contiguous() and d_inv.dtype == torch.float32 and d_seg.dtype == torch.float32
-        with torch.cuda.device(self.device):
-            self._check(self.L.soccdpt_train_backward(self._h, _ptr(x), B, _ptr(d_inv), _ptr(d_seg), ws.data_ptr(), ws.numel(),
-                                                      _stream_ptr(self.device)), "soccdpt_train_backward")
+        self._call("soccdpt_train_backward", _ptr(x), B, _ptr(d_inv), _ptr(d_seg), ws.data_ptr(), ws.numel(), stream=True)
 
     def forward(self, x: torch.Tensor, inv_up, seg_up, points, occ, occ_bits):
         B = x.shape[0]
         ws = self.workspace(B)
-        with torch.cuda.device(self.device):
-            self._check(self.L.soccdpt_forward(self._h, _ptr(x), B, _ptr(inv_up), _ptr(seg_up), _ptr(points), _ptr(occ),
-                                               _ptr(occ_bits), ws.data_ptr(), ws.numel(), _stream_ptr(self.device)),
-                        "soccdpt_forward")
+        self._call("soccdpt_forward", _ptr(x), B, _ptr(inv_up), _ptr(seg_up), _ptr(points), _ptr(occ), _ptr(occ_bits), ws.data_ptr(), ws.numel(), stream=True)
 
     def set_streams(self, n: int):
         """Deal each batch to n concurrent sub-batches (see soccdpt_set_streams); invalidates the workspace."""
         with torch.cuda.device(self.device):
-            self._check(self.L.soccdpt_set_streams(self._h, int(n)), "soccdpt_set_streams")
+            self._call("soccdpt_set_streams", int(n))
         self._workspace = None
 
     def set_graph(self, on: bool = True):
-        self._check(self.L.soccdpt_set_graph(self._h, 1 if on else 0), "soccdpt_set_graph")
+        self._call("soccdpt_set_graph", 1 if on else 0)
 
     def profile_enable(self, on: bool = True):
-        self._check(self.L.soccdpt_profile_enable(self._h, 1 if on else 0), "soccdpt_profile_enable")
+        self._call("soccdpt_profile_enable", 1 if on else 0)
 
     def profile_collect(self):
         """-> {family: dict(launches, ms, flops, bytes)} summed over everything recorded since enable/collect."""
         buf = (KernelStat * 64)()
         n = ctypes.c_int(0)
-        self._check(self.L.soccdpt_profile_collect(self._h, buf, 64, ctypes.byref(n)), "soccdpt_profile_collect")
+        self._call("soccdpt_profile_collect", buf, 64, ctypes.byref(n))
         return {buf[i].name.decode(): dict(launches=buf[i].launches, ms=buf[i].ms, flops=buf[i].flops, bytes=buf[i].bytes)
                 for i in range(n.value)}
 
     def launch_count(self) -> int:
         return int(self.L.soccdpt_last_launch_count(self._h))
-
 
     def workspace_tensor(self, B: int, name: str):
         """View of a named intermediate of the last soccdpt_network(B) call (diagnostics / parity tests).
@@ -725,7 +681,6 @@ def op_igemm(x, wt, M, N, Cin, taps=1, ldx=0, H=0, W=0, bias=None, res1=None, re
     the generalised convolution addressing.  res2_h / res2_w: res2 is a low-res map sampled bilinearly; ln_*: the LayerNorm epilogue; dot3: the
     three-class classifier epilogue; out_fmt / halo_fmt: -1 = the launch's format, 1 = fp16 (x3 launch), 3 = x3 (fp16 launch) -- see
     include/soccdpt_hip.h soccdpt_igemm_args."""
-    L = load_library()
     c = conv or {}
     a = IgemmArgs(_ptr(x), _ptr(wt), M, N, Cin, taps, ldx, H, W, _ptr(bias), _ptr(res1), _ptr(res2), act, _ptr(out_f32),
                   act_on_f32, _ptr(out_bf16), out_halo, _ptr(dot_w), float(dot_b), _ptr(out_dot), tune,
@@ -737,134 +692,96 @@ def op_igemm(x, wt, M, N, Cin, taps=1, ldx=0, H=0, W=0, bias=None, res1=None, re
                   0 if gn_part is None else gn_part.numel(), 0 if gn_count is None else gn_count.numel(), _ptr(stamps), int(sk_defer),
                   int(res2_h), int(res2_w), _ptr(ln_g), _ptr(ln_b), _ptr(ln_xf), _ptr(ln_halo), int(ln_residual), int(dot3), int(out_fmt),
                   int(halo_fmt))
-    rc = L.soccdpt_op_igemm(ctypes.byref(a), _stream_ptr(x.device))
-    if rc != 0:
-        raise RuntimeError("soccdpt_op_igemm failed: " + L.soccdpt_last_error(None).decode())
+    _call("soccdpt_op_igemm", ctypes.byref(a), device=x.device, guard=False)
 
 
 def op_depth_tail(d1, wt, bias, w4, b4, out, B, h, w, precision=PREC_BF16):
     """Kernel-level entry (tests): the fused depth tail (soccdpt_op_depth_tail) on the current stream: d1 [B][h][w][128] and wt [32][9*128]
     16-bit (bf16 / fp16 by precision), bias / w4 [32] f32 -> out [B][2h][2w] f32."""
-    L = load_library()
-    rc = L.soccdpt_op_depth_tail(_ptr(d1), _ptr(wt), _ptr(bias), _ptr(w4), float(b4), _ptr(out), int(precision), int(B), int(h), int(w),
-                                 _stream_ptr(d1.device))
-    if rc != 0:
-        raise RuntimeError("soccdpt_op_depth_tail failed: " + L.soccdpt_last_error(None).decode())
+    _call("soccdpt_op_depth_tail", _ptr(d1), _ptr(wt), _ptr(bias), _ptr(w4), float(b4), _ptr(out), int(precision), int(B), int(h), int(w),
+          device=d1.device, guard=False)
 
 
 def op_seg_tail(part, nplanes, bias, tmp, out, B, h, w, sigmoid):
     """Kernel-level entry (tests): finish of a dot3 launch (soccdpt_op_seg_tail) on the current stream: part [nplanes][B*h*w][4] + bias [3] ->
     tmp [B*h*w][3] logits and out [B][3][2h][2w] = sigmoid / ScaledTanh of their x2 bilinear (align_corners) up-sampling."""
-    L = load_library()
-    rc = L.soccdpt_op_seg_tail(_ptr(part), int(nplanes), _ptr(bias), _ptr(tmp), _ptr(out), int(B), int(h), int(w), 1 if sigmoid else 0,
-                               _stream_ptr(part.device))
-    if rc != 0:
-        raise RuntimeError("soccdpt_op_seg_tail failed: " + L.soccdpt_last_error(None).decode())
+    _call("soccdpt_op_seg_tail", _ptr(part), int(nplanes), _ptr(bias), _ptr(tmp), _ptr(out), int(B), int(h), int(w), 1 if sigmoid else 0,
+          device=part.device, guard=False)
 
 
 def op_gn_finish(part, stats, B, tps, groups, hw, cpg, eps=1e-5):
     """Kernel-level entry (tests): per-tile GroupNorm partials -> {mean, rstd} (soccdpt_op_gn_finish) on the current stream."""
-    L = load_library()
-    rc = L.soccdpt_op_gn_finish(_ptr(part), _ptr(stats), int(B), int(tps), int(groups), int(hw), int(cpg), float(eps), _stream_ptr(part.device))
-    if rc != 0:
-        raise RuntimeError("soccdpt_op_gn_finish failed: " + L.soccdpt_last_error(None).decode())
+    _call("soccdpt_op_gn_finish", _ptr(part), _ptr(stats), int(B), int(tps), int(groups), int(hw), int(cpg), float(eps), device=part.device, guard=False)
 
 
 def op_gn_apply(raw, stats, gamma, beta, hw, w, cpg, part=None, tps=0, raw2=None, stats2=None, part2=None, tps2=0, gamma2=None, beta2=None, res=None,
                 out_f32=None, out_op=None, out_halo=None, out_format=PREC_F32, relu=True, eps=1e-5):
     """Kernel-level entry (tests): GroupNorm apply (+ shortcut) (+ ReLU) of raw [M][C] (soccdpt_op_gn_apply) on the current stream."""
-    L = load_library()
     M, C = raw.shape
-    rc = L.soccdpt_op_gn_apply(_ptr(raw), _ptr(stats), _ptr(part), int(tps), _ptr(gamma), _ptr(beta), _ptr(raw2), _ptr(stats2), _ptr(part2), int(tps2),
-                               _ptr(gamma2), _ptr(beta2), _ptr(res), _ptr(out_f32), _ptr(out_op), _ptr(out_halo), int(out_format), 1 if relu else 0, M, int(hw),
-                               int(w), int(C), int(cpg), float(eps), _stream_ptr(raw.device))
-    if rc != 0:
-        raise RuntimeError("soccdpt_op_gn_apply failed: " + L.soccdpt_last_error(None).decode())
+    _call("soccdpt_op_gn_apply", _ptr(raw), _ptr(stats), _ptr(part), int(tps), _ptr(gamma), _ptr(beta), _ptr(raw2), _ptr(stats2), _ptr(part2), int(tps2),
+          _ptr(gamma2), _ptr(beta2), _ptr(res), _ptr(out_f32), _ptr(out_op), _ptr(out_halo), int(out_format), 1 if relu else 0, M, int(hw),
+          int(w), int(C), int(cpg), float(eps), device=raw.device, guard=False)
 
 
 def op_vit_attention(qkv, out, B, N, heads, precision=PREC_BF16):
     """Kernel-level entry (tests): softmax(q k^T / 8) v of one ViT block on the current stream."""
-    L = load_library()
-    rc = L.soccdpt_op_vit_attention(_ptr(qkv), _ptr(out), int(precision), B, N, heads, _stream_ptr(qkv.device))
-    if rc != 0:
-        raise RuntimeError("soccdpt_op_vit_attention failed: " + L.soccdpt_last_error(None).decode())
+    _call("soccdpt_op_vit_attention", _ptr(qkv), _ptr(out), int(precision), B, N, heads, device=qkv.device, guard=False)
 
 
 def op_input_transform_u8(frames: torch.Tensor, Hd: int, Wd: int, mean=(0.5, 0.5, 0.5), std=(0.5, 0.5, 0.5)) -> torch.Tensor:
     """uint8 [B,Hs,Ws,3] device frames -> float32 [B,3,Hd,Wd] network input (soccdpt_input_transform_u8) on the current stream."""
-    L = load_library()
     assert frames.dtype == torch.uint8 and frames.dim() == 4 and frames.shape[3] == 3 and frames.is_cuda
     B, Hs, Ws, _ = frames.shape
     out = torch.empty((B, 3, Hd, Wd), dtype=torch.float32, device=frames.device)
     m, s = (ctypes.c_double * 3)(*mean), (ctypes.c_double * 3)(*std)
-    with torch.cuda.device(frames.device):
-        rc = L.soccdpt_input_transform_u8(_ptr(frames), B, Hs, Ws, Hd, Wd, m, s, _ptr(out), _stream_ptr(frames.device))
-    if rc != 0:
-        raise RuntimeError("soccdpt_input_transform_u8 failed: " + L.soccdpt_last_error(None).decode())
+    _call("soccdpt_input_transform_u8", _ptr(frames), B, Hs, Ws, Hd, Wd, m, s, _ptr(out), device=frames.device)
     return out
 
 
 def op_mlp_ln(x_op, x_f32, w1, b1, w2, b2, ln_g, ln_b, x_op_out=None, halo=None, precision=PREC_BF16, H=0, W=0):
     """Kernel-level entry (tests): x_f32 += LN(fc2(GELU(fc1(x_op)))) in one launch (soccdpt_op_mlp_ln) on the current stream."""
-    L = load_library()
     M, C = x_op.shape
-    rc = L.soccdpt_op_mlp_ln(_ptr(x_op), _ptr(x_f32), _ptr(w1), _ptr(b1), _ptr(w2), _ptr(b2), _ptr(ln_g), _ptr(ln_b), _ptr(x_op_out), _ptr(halo),
-                             int(precision), M, C, H, W, _stream_ptr(x_op.device))
-    if rc != 0:
-        raise RuntimeError("soccdpt_op_mlp_ln failed: " + L.soccdpt_last_error(None).decode())
+    _call("soccdpt_op_mlp_ln", _ptr(x_op), _ptr(x_f32), _ptr(w1), _ptr(b1), _ptr(w2), _ptr(b2), _ptr(ln_g), _ptr(ln_b), _ptr(x_op_out), _ptr(halo),
+          int(precision), M, C, H, W, device=x_op.device, guard=False)
 
 
 def op_wgrad_tn(a, lda, b, ldb, K, Nout, C, taps=1, rp=0, precision=PREC_BF16, b_row0=0):
     """Kernel-level entry (tests): weight gradient out [Nout][taps * C] from operands as stored (include/soccdpt_hip.h soccdpt_op_wgrad_tn).  a, b: flat device
     tensors (bf16 / fp16, or x3 bytes from x3_encode); b_row0: element offset of row 0 of b inside its tensor (margins in front for taps == 9)."""
-    L = load_library()
     out = torch.empty((Nout, taps * C), dtype=torch.float32, device=a.device)
     scratch = torch.empty((64 * Nout * taps * C,), dtype=torch.float32, device=a.device)
     es = 4 if precision == PREC_F16X3 else 2
-    rc = L.soccdpt_op_wgrad_tn(_ptr(a), lda, b.data_ptr() + b_row0 * es, ldb, K, Nout, C, taps, rp, int(precision), _ptr(scratch), scratch.numel(), _ptr(out),
-                               _stream_ptr(a.device))
-    if rc != 0:
-        raise RuntimeError("soccdpt_op_wgrad_tn failed: " + L.soccdpt_last_error(None).decode())
+    _call("soccdpt_op_wgrad_tn", _ptr(a), lda, b.data_ptr() + b_row0 * es, ldb, K, Nout, C, taps, rp, int(precision), _ptr(scratch), scratch.numel(), _ptr(out),
+          device=a.device, guard=False)
     return out
 
 
 def op_window_attention(qkv, cpb_table, scale, out, B, res, ws, shift, heads, precision=PREC_BF16):
-    L = load_library()
     nt = (ws * ws + 31) // 32
     scratch = torch.empty((heads * nt * nt * 1024,), dtype=torch.float32, device=qkv.device)
-    rc = L.soccdpt_op_window_attention(_ptr(qkv), _ptr(cpb_table), _ptr(scale), _ptr(out), _ptr(scratch), B, res, ws, shift,
-                                       heads, int(precision), _stream_ptr(qkv.device))
-    if rc != 0:
-        raise RuntimeError("soccdpt_op_window_attention failed: " + L.soccdpt_last_error(None).decode())
+    _call("soccdpt_op_window_attention", _ptr(qkv), _ptr(cpb_table), _ptr(scale), _ptr(out), _ptr(scratch), B, res, ws, shift,
+          heads, int(precision), device=qkv.device, guard=False)
 
 
 def op_window_attention_qkv(x, wqkv, qkv_bias, cpb_table, scale, out, B, res, ws, shift, heads, precision=PREC_F16, out_x3=False, stamps=None):
     """soccdpt_op_window_attention_qkv: one Swin-V2 block's qkv projection + window attention as ONE launch (csrc/attention_qkv.hip)."""
-    L = load_library()
     nt = (ws * ws + 31) // 32
     scratch = torch.empty((heads * nt * nt * 1024,), dtype=torch.float32, device=x.device)
-    rc = L.soccdpt_op_window_attention_qkv(_ptr(x), _ptr(wqkv), _ptr(qkv_bias), _ptr(cpb_table), _ptr(scale), _ptr(out), _ptr(scratch), B, res, ws, shift,
-                                           heads, int(precision), 1 if out_x3 else 0, _ptr(stamps), _stream_ptr(x.device))
-    if rc != 0:
-        raise RuntimeError("soccdpt_op_window_attention_qkv failed: " + L.soccdpt_last_error(None).decode())
+    _call("soccdpt_op_window_attention_qkv", _ptr(x), _ptr(wqkv), _ptr(qkv_bias), _ptr(cpb_table), _ptr(scale), _ptr(out), _ptr(scratch), B, res, ws, shift,
+          heads, int(precision), 1 if out_x3 else 0, _ptr(stamps), device=x.device, guard=False)
 
 
 def op_wino_weights(w, scale=None, precision=PREC_F16):
     """soccdpt_op_wino_weights: [N][C][3][3] f32 -> the Winograd-domain weights U = G g G^T, 16-bit [C/32][16][N][32] (csrc/wino.hip)."""
-    L = load_library()
     N, C = w.shape[0], w.shape[1]
     u = torch.empty((16 * N * C,), dtype=torch.float16 if precision == PREC_F16 else torch.bfloat16, device=w.device)
-    rc = L.soccdpt_op_wino_weights(_ptr(w), _ptr(scale), _ptr(u), N, C, int(precision), _stream_ptr(w.device))
-    if rc != 0:
-        raise RuntimeError("soccdpt_op_wino_weights failed: " + L.soccdpt_last_error(None).decode())
+    _call("soccdpt_op_wino_weights", _ptr(w), _ptr(scale), _ptr(u), N, C, int(precision), device=w.device, guard=False)
     return u
 
 
 def op_wino_conv(x_halo, u, B, H, W, C, N, bias=None, res1=None, res2=None, res2_hw=(0, 0), relu=False, act_on_f32=False, out_f32=None, out_op=None, out_halo=False,
                  out_x3=False, precision=PREC_F16, stamps=None):
     """soccdpt_op_wino_conv: 3x3 stride-1 convolution over a zero-halo NHWC image in the Winograd F(2x2, 3x3) form, igemm's epilogue options."""
-    L = load_library()
-    rc = L.soccdpt_op_wino_conv(_ptr(x_halo), _ptr(u), B, H, W, C, N, _ptr(bias), _ptr(res1), _ptr(res2), int(res2_hw[0]), int(res2_hw[1]), 1 if relu else 0,
-                                1 if act_on_f32 else 0, _ptr(out_f32), _ptr(out_op), 1 if out_halo else 0, 1 if out_x3 else 0, int(precision), _ptr(stamps), _stream_ptr(x_halo.device))
-    if rc != 0:
-        raise RuntimeError("soccdpt_op_wino_conv failed: " + L.soccdpt_last_error(None).decode())
+    _call("soccdpt_op_wino_conv", _ptr(x_halo), _ptr(u), B, H, W, C, N, _ptr(bias), _ptr(res1), _ptr(res2), int(res2_hw[0]), int(res2_hw[1]), 1 if relu else 0,
+          1 if act_on_f32 else 0, _ptr(out_f32), _ptr(out_op), 1 if out_halo else 0, 1 if out_x3 else 0, int(precision), _ptr(stamps),
+          device=x_halo.device, guard=False)

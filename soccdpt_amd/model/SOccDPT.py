@@ -95,6 +95,16 @@ class SOccDPT(BaseModel):
         self._weight_refs = {}
         self.occ_exchange = None  # set by soccdpt_amd.dist for multi-GPU: callable(bits) -> union bits
         self.grad_exchange = None  # set by soccdpt_amd.dist.attach_training: callable(flat_grads, runs) -> averaged in place
+        self.last_occ_bits = None        # packed union grid of the last forward with compute_occ (_finish_occupancy)
+        self.last_occ_frame_bits = None  # its packed per-frame rows; None in union mode
+        self._warned_uncalibrated = False
+        # ---- training step state ----
+        self.train_amp = False      # the reference's `amp` sweep parameter: False | True / "bf16" | "f16" (with a GradScaler) | "x3"
+        self._train_state = {}      # id(engine) -> bound pointers, the flat gradient buffer and its views (_bind_for_training)
+        self._train_x = None        # (engine, input) of the train_forward that backward() belongs to
+        self._train_generation = 0  # counts train-mode forwards: the library keeps one tape per handle
+        self._last_grad_runs = None  # (engine, flat gradients, runs) of the last backward (utils/optim.py GradScaler)
+        self._autograd_anchor = None  # a plain tensor attribute: never a parameter or buffer, so state_dict() does not see it
 
     # -- engine plumbing --
     def _engine_backbone(self) -> str:
@@ -133,74 +143,74 @@ class SOccDPT(BaseModel):
             seg_up = seg_up[0]
         return inv_up, seg_up, points, occ
 
+    def _camera_outputs(self, B: int, dev: torch.device):
+        """The camera-resolution outputs of one forward, uninitialised: inv_up [B,Hc,Wc], seg_up [B,C,Hc,Wc], points [B,Hc,Wc,3]."""
+        Hc, Wc = self.height, self.width
+        return (torch.empty((B, Hc, Wc), device=dev), torch.empty((B, self.num_classes, Hc, Wc), device=dev), torch.empty((B, Hc, Wc, 3), device=dev))
+
+    def _project_outputs(self, eng: Engine, inv: torch.Tensor, seg: torch.Tensor):
+        """Network outputs inv [B,h,w], seg [B,C,h,w] -> (inv_up, seg_up, points, packed union grid | None) by soccdpt_project.  The union grid is
+        marked here in union mode only: with occupancy_per_frame it comes from the frame rows (_finish_occupancy)."""
+        inv_up, seg_up, points = self._camera_outputs(inv.shape[0], inv.device)
+        union = self.compute_occ and not self.occupancy_per_frame
+        bits = torch.empty((eng.occ_words(),), dtype=torch.int32, device=inv.device) if union else None
+        eng.project(inv, seg, inv_up, seg_up, points, bits, clear_bits=True)
+        return inv_up, seg_up, points, bits
+
     def get_semantic_occupancy(self, inv_depth: torch.Tensor, segmentation: torch.Tensor):
         """inv_depth [B,h,w] (or [B,1,h,w]), segmentation [B,C,h,w] on a cuda device ->
         (inv_depth_up [B,Hc,Wc], seg_up [B,C,Hc,Wc] | [C,Hc,Wc], points [B,Hc,Wc,3], occupancy | None)."""
         if inv_depth.dim() == 4:
             inv_depth = inv_depth[:, 0]
         eng = self._engine(inv_depth.device)
-        dev = inv_depth.device
         inv = inv_depth.detach().to(torch.float32).contiguous()
         seg = segmentation.detach().to(torch.float32).contiguous()
-        B = inv.shape[0]
-        Hc, Wc, C = self.height, self.width, self.num_classes
-        inv_up = torch.empty((B, Hc, Wc), device=dev)
-        seg_up = torch.empty((B, C, Hc, Wc), device=dev)
-        points = torch.empty((B, Hc, Wc, 3), device=dev)
-        occ = None
-        if self.compute_occ and self.occupancy_per_frame:
-            eng.project(inv, seg, inv_up, seg_up, points, None)   # the union comes from the frame rows
-            occ = self._frames_occupancy(eng, inv_up, seg)
-            return self._shape_outputs(inv_up, seg_up, points, occ)
-        bits = torch.empty((eng.occ_words(),), dtype=torch.int32, device=dev) if self.compute_occ else None
-        eng.project(inv, seg, inv_up, seg_up, points, bits, clear_bits=True)
-        if self.compute_occ:
-            occ = self._finish_occupancy(eng, bits, B)
+        inv_up, seg_up, points, bits = self._project_outputs(eng, inv, seg)
+        occ = self._finish_occupancy(eng, inv.shape[0], bits, inv_up=inv_up, seg=seg) if self.compute_occ else None
         return self._shape_outputs(inv_up, seg_up, points, occ)
 
-    def _frames_occupancy(self, eng: Engine, inv_up: torch.Tensor, seg: torch.Tensor):
-        """occupancy_per_frame: one grid per frame from the projection's clamped inverse depth and the network-resolution class maps
-        (soccdpt_voxelise_frames), dense rows from their own bits, the union of the rows as last_occ_bits."""
-        B = inv_up.shape[0]
-        g = self.grid_size
-        frame_bits = torch.empty((B, eng.occ_words()), dtype=torch.int32, device=inv_up.device)
-        eng.voxelise_frames(inv_up, seg, frame_bits, clear_bits=True)
-        union = torch.zeros((eng.occ_words(),), dtype=torch.int32, device=inv_up.device)
-        eng.occ_or(union, frame_bits, B)
-        occ = torch.empty((B, g[0], g[1], g[2], self.num_classes), device=inv_up.device)
-        eng.occ_expand_frames(frame_bits, B, occ)
-        self._publish_frame_bits(eng, frame_bits, union)
-        return occ
-
-    def _publish_frame_bits(self, eng: Engine, frame_bits: torch.Tensor, union: torch.Tensor):
-        # multi-GPU: the per-frame rows are rank-local and stay here; only the union goes through the exchange, as in union mode
-        ex = self.occ_exchange
-        if ex is not None:
-            union = ex.finish(eng, union, ex.start(union)) if hasattr(ex, "start") else ex(eng, union)
-        self.last_occ_frame_bits = frame_bits
-        self.last_occ_bits = union
-
-    def _finish_occupancy(self, eng: Engine, bits: torch.Tensor, B: int):
-        g = self.grid_size
-        rows = 1 if self.share_occupancy_rows else B
-        occ = torch.empty((rows, g[0], g[1], g[2], self.num_classes), device=bits.device)
-        ex = self.occ_exchange
-        if ex is not None and hasattr(ex, "start"):
-            # multi-GPU: union over every rank's frames (SURVEY.md §8e).  The all-gather of the packed grids runs on RCCL's stream while this
-            # stream writes the rows' zeros (the bulk of the expansion's 25 MB per row); after the OR only the set voxels are written.
-            ticket = ex.start(bits)
-            eng.occ_zero(rows, occ)
-            bits = ex.finish(eng, bits, ticket)
-            eng.occ_set(bits, rows, occ)
-        else:
+    def _finish_occupancy(self, eng: Engine, B: int, bits, inv_up=None, seg=None, occ=None, frame_bits=None):
+        """The one way from the projection to the occupancy tensor [B,g0,g1,g2,C], and the only place that publishes last_occ_bits /
+        last_occ_frame_bits.  bits: the packed union grid soccdpt_project / soccdpt_forward marked (None with occupancy_per_frame after
+        _project_outputs: the frame rows are voxelised here from inv_up and seg).  occ / frame_bits: what the fused eng.forward /
+        eng.forward_frames already wrote; those steps are then not repeated."""
+        g, dev = self.grid_size, (bits if bits is not None else inv_up).device
+        ex = self.occ_exchange   # multi-GPU: union over every rank's frames (SURVEY.md §8e)
+        split = ex is not None and hasattr(ex, "start")
+        if self.occupancy_per_frame:
+            if frame_bits is None:
+                # one grid per frame from the projection's clamped inverse depth and the network-resolution class maps (soccdpt_voxelise_frames),
+                # dense rows from their own bits, the union of the rows as last_occ_bits
+                frame_bits = torch.empty((B, eng.occ_words()), dtype=torch.int32, device=dev)
+                eng.voxelise_frames(inv_up, seg, frame_bits, clear_bits=True)
+                bits = torch.zeros((eng.occ_words(),), dtype=torch.int32, device=dev)
+                eng.occ_or(bits, frame_bits, B)
+                occ = torch.empty((B, g[0], g[1], g[2], self.num_classes), device=dev)
+                eng.occ_expand_frames(frame_bits, B, occ)
+            # the per-frame rows are rank-local and stay here; only the union goes through the exchange, as in union mode
             if ex is not None:
-                bits = ex(eng, bits)
-            eng.occ_expand(bits, rows, occ)
+                bits = ex.finish(eng, bits, ex.start(bits)) if split else ex(eng, bits)
+        elif occ is None:
+            rows = 1 if self.share_occupancy_rows else B
+            occ = torch.empty((rows, g[0], g[1], g[2], self.num_classes), device=dev)
+            if split:
+                # The all-gather of the packed grids runs on RCCL's stream while this stream writes the rows' zeros (the bulk of the
+                # expansion's 25 MB per row); after the OR only the set voxels are written.
+                ticket = ex.start(bits)
+                eng.occ_zero(rows, occ)
+                bits = ex.finish(eng, bits, ticket)
+                eng.occ_set(bits, rows, occ)
+            else:
+                if ex is not None:
+                    bits = ex(eng, bits)
+                eng.occ_expand(bits, rows, occ)
+            # opt-in: ONE dense row viewed B times (stride 0).  The reference writes the same union grid into every batch row
+            # (/root/reference/SOccDPT/model/SOccDPT.py:449-455); a caller that only reads it saves (B - 1) x 25 MB of stores per step.
+            if self.share_occupancy_rows:
+                occ = occ.expand(B, -1, -1, -1, -1)
         self.last_occ_bits = bits
-        self.last_occ_frame_bits = None
-        # opt-in: ONE dense row viewed B times (stride 0).  The reference writes the same union grid into every batch row
-        # (/root/reference/SOccDPT/model/SOccDPT.py:449-455); a caller that only reads it saves (B - 1) x 25 MB of stores per step.
-        return occ.expand(B, -1, -1, -1, -1) if self.share_occupancy_rows else occ
+        self.last_occ_frame_bits = frame_bits
+        return occ
 
     def occupancy_points(self, class_2_color=None, frame=None):
         """The last forward's occupancy grid as the reference's point list (utils/__init__.py:532-568 occupancy_grid_to_points on occupancy[0]):
@@ -208,12 +218,12 @@ class SOccDPT(BaseModel):
         so it works the same with share_occupancy_rows=True and under occ_exchange.  With class_2_color also the [N,3] u8 colours.
         frame=None lists the union grid; frame=b (a model built with occupancy_per_frame=True) lists frame b's own grid from `last_occ_frame_bits`."""
         if frame is not None:
-            rows = getattr(self, "last_occ_frame_bits", None)
+            rows = self.last_occ_frame_bits
             if not self.occupancy_per_frame or rows is None:
                 raise RuntimeError("occupancy_points(frame=...) needs a forward of a model built with compute_occ=True and occupancy_per_frame=True")
             bits = rows[int(frame)]
         else:
-            bits = getattr(self, "last_occ_bits", None)
+            bits = self.last_occ_bits
         if bits is None:
             raise RuntimeError("occupancy_points() needs a forward of a model built with compute_occ=True first")
         from ..utils.occupancy import occupancy_bits_to_points
@@ -263,6 +273,17 @@ class SOccDPT_V3(SOccDPT):
         self._weight_refs.clear()
         return super()._apply(fn, *args, **kwargs)
 
+    def _live_tensors(self, eng: Engine):
+        """-> ({key: LIVE parameter / buffer}, the engine's keys in its order), every consumed tensor checked to be contiguous f32 on the engine's device."""
+        live = dict(self.named_parameters(remove_duplicate=False))
+        live.update(dict(self.named_buffers(remove_duplicate=False)))
+        keys = eng.weight_keys()
+        for k in keys:
+            t = live[k]
+            if t.device != eng.device or t.dtype != torch.float32 or not t.is_contiguous():
+                raise RuntimeError(f"weight {k} must be a contiguous float32 tensor on {eng.device} (got {t.device}, {t.dtype})")
+        return live, keys
+
     def _sync_weights(self, eng: Engine):
         """(Re-)bind and re-prepare when any consumed tensor changed: in-place updates bump `_version` (optimizers, the fused
         Adam, load_state_dict), `p.data = ...` changes `data_ptr()`.  The LIVE parameters / buffers are watched, not a
@@ -272,27 +293,23 @@ class SOccDPT_V3(SOccDPT):
             version = tuple((t._version, t.data_ptr()) for t in refs)
             if self._bound_versions.get(id(eng)) == version:
                 return
-        live = dict(self.named_parameters(remove_duplicate=False))
-        live.update(dict(self.named_buffers(remove_duplicate=False)))
-        keys = eng.weight_keys()
+        live, keys = self._live_tensors(eng)
         refs = [live[k] for k in keys]
         version = tuple((t._version, t.data_ptr()) for t in refs)
         for k, t in zip(keys, refs):
-            if t.device != eng.device or t.dtype != torch.float32 or not t.is_contiguous():
-                raise RuntimeError(f"weight {k} must be a contiguous float32 tensor on {eng.device} (got {t.device}, {t.dtype})")
             eng.bind(k, t.detach())
         was_calibrated = self.precision == PREC_MIXED and eng.prec_map_source() == 1
         eng.prepare()
         if was_calibrated and eng.prec_map_source() == 3:
             # the library compared a fingerprint of the bound values with the one the calibration ran on (soccdpt_prepare)
-            self.__dict__["_warned_uncalibrated"] = True
+            self._warned_uncalibrated = True
             print("soccdpt_amd: the weights changed since net.calibrate_precision() derived the precision map, so that map no longer carries its "
                   "within-tolerance claim: every GEMM / convolution runs x3 split-fp16 operands again until net.calibrate_precision(sample_frames) is re-run.")
         self._weight_refs[id(eng)] = refs
         self._bound_versions[id(eng)] = version
-        if self.precision == PREC_MIXED and eng.prec_map_source() == 3 and not self.__dict__.get("_warned_uncalibrated"):
+        if self.precision == PREC_MIXED and eng.prec_map_source() == 3 and not self._warned_uncalibrated:
             # printed, not raised: the reference's convention for checkpoint mismatches (model/base_model.py:30-34)
-            self.__dict__["_warned_uncalibrated"] = True
+            self._warned_uncalibrated = True
             print("soccdpt_amd: these are not the weights the shipped precision map of the default arithmetic (SOCCDPT_PREC_MIXED) was derived on, so its "
                   "within-tolerance claim does not carry over: every GEMM / convolution runs x3 split-fp16 operands (f32-grade, about 1.7x the step) "
                   "until net.calibrate_precision(sample_frames, budget=5e-4) has derived a map for THIS checkpoint.")
@@ -312,30 +329,22 @@ class SOccDPT_V3(SOccDPT):
         dev = x.device
         xin = x.detach().to(torch.float32).contiguous()
         B = xin.shape[0]
-        Hc, Wc, C = self.height, self.width, self.num_classes
-        inv_up = torch.empty((B, Hc, Wc), device=dev)
-        seg_up = torch.empty((B, C, Hc, Wc), device=dev)
-        points = torch.empty((B, Hc, Wc, 3), device=dev)
-        occ = None
-        bits = None
-        if self.compute_occ and self.occupancy_per_frame:
+        inv_up, seg_up, points = self._camera_outputs(B, dev)
+        occ = bits = frame_bits = None
+        if self.compute_occ:
             g = self.grid_size
-            occ = torch.empty((B, g[0], g[1], g[2], C), device=dev)
             bits = torch.empty((eng.occ_words(),), dtype=torch.int32, device=dev)
+            # the fused calls write the dense rows themselves where every row is this rank's own: the per-frame rows always, the union rows
+            # unless an exchange or the shared row comes in between (_finish_occupancy then expands the exchanged / the single row)
+            if self.occupancy_per_frame or (self.occ_exchange is None and not self.share_occupancy_rows):
+                occ = torch.empty((B, g[0], g[1], g[2], self.num_classes), device=dev)
+        if self.compute_occ and self.occupancy_per_frame:
             frame_bits = torch.empty((B, eng.occ_words()), dtype=torch.int32, device=dev)
             eng.forward_frames(xin, inv_up, seg_up, points, occ, bits, frame_bits)
-            self._publish_frame_bits(eng, frame_bits, bits)
-            return self._shape_outputs(inv_up, seg_up, points, occ)
+        else:
+            eng.forward(xin, inv_up, seg_up, points, occ, bits)
         if self.compute_occ:
-            bits = torch.empty((eng.occ_words(),), dtype=torch.int32, device=dev)
-            if self.occ_exchange is None and not self.share_occupancy_rows:
-                g = self.grid_size
-                occ = torch.empty((B, g[0], g[1], g[2], C), device=dev)
-        eng.forward(xin, inv_up, seg_up, points, occ, bits)
-        if self.compute_occ and occ is None:
-            occ = self._finish_occupancy(eng, bits, B)
-        self.last_occ_bits = bits
-        self.last_occ_frame_bits = None
+            occ = self._finish_occupancy(eng, B, bits, occ=occ, frame_bits=frame_bits)
         return self._shape_outputs(inv_up, seg_up, points, occ)
 
     def _forward_train(self, x: torch.Tensor):
@@ -344,29 +353,20 @@ class SOccDPT_V3(SOccDPT):
         expression of inv_depth / segmentation / points runs soccdpt_project_backward + soccdpt_train_backward and leaves the gradients in .grad of
         the parameters that have requires_grad (freeze / unfreeze-by-percentage / PatchWiseInplace work as with an nn.Module built from torch ops).
         The library keeps ONE tape per handle: backward belongs to the most recent train-mode forward."""
-        anchor = self.__dict__.get("_autograd_anchor")
-        if anchor is None or anchor.device != x.device:
-            anchor = torch.zeros((), device=x.device, requires_grad=True)   # makes autograd record the node: the parameters are not inputs of it
-            self.__dict__["_autograd_anchor"] = anchor
+        if self._autograd_anchor is None or self._autograd_anchor.device != x.device:
+            self._autograd_anchor = torch.zeros((), device=x.device, requires_grad=True)   # makes autograd record the node: the parameters are not inputs of it
         if not torch.is_grad_enabled():
             inv, seg = self.train_forward(x)
             return self.get_semantic_occupancy(inv, seg)
-        out = _TrainForward.apply(self, x, anchor)
-        inv_up, seg_up, points = out[0], out[1], out[2]
-        occ = out[3] if len(out) > 3 else None
-        if seg_up.shape[0] == 1:          # the reference's .squeeze() quirk (model/SOccDPT.py:276-285), as a differentiable view
-            seg_up = seg_up[0]
-        return inv_up, seg_up, points, occ
+        out = _TrainForward.apply(self, x, self._autograd_anchor)
+        return self._shape_outputs(out[0], out[1], out[2], out[3] if len(out) > 3 else None)   # (the B == 1 squeeze is a differentiable view)
 
     def _bind_for_training(self, eng: Engine):
         """Bind the LIVE parameters / buffers (the training step reads weights as bound: no prepare) and one gradient buffer per
         trainable parameter; frozen parameters (requires_grad False: model/loss.py:110-152) are unbound and their weight-gradient
         GEMMs skipped."""
-        live = dict(self.named_parameters(remove_duplicate=False))
-        live.update(dict(self.named_buffers(remove_duplicate=False)))
-        keys = eng.weight_keys()
-        state = self.__dict__.setdefault("_train_state", {})
-        st = state.setdefault(id(eng), {"ptrs": {}, "grads": {}, "req": {}, "flat": None, "span": {}})
+        live, keys = self._live_tensors(eng)
+        st = self._train_state.setdefault(id(eng), {"ptrs": {}, "grads": {}, "req": {}, "flat": None, "span": {}})
         if st["flat"] is None:
             # ONE flat f32 gradient buffer, a view per consumed tensor in the library's key order: a data-parallel job all-reduces contiguous runs
             # of it (soccdpt_amd.dist.attach_training) instead of one collective per tensor
@@ -378,8 +378,6 @@ class SOccDPT_V3(SOccDPT):
             st["flat"] = torch.zeros(off, dtype=torch.float32, device=eng.device)
         for k in keys:
             t = live[k]
-            if t.device != eng.device or t.dtype != torch.float32 or not t.is_contiguous():
-                raise RuntimeError(f"weight {k} must be a contiguous float32 tensor on {eng.device} (got {t.device}, {t.dtype})")
             if st["ptrs"].get(k) != t.data_ptr():
                 eng.bind(k, t.detach())
                 st["ptrs"][k] = t.data_ptr()
@@ -405,8 +403,8 @@ class SOccDPT_V3(SOccDPT):
         assert x.dim() == 4 and x.shape[1] == 3 and x.shape[2] == img and x.shape[3] == img, f"expected x [B,3,{img},{img}], got {tuple(x.shape)}"
         eng = self._engine(x.device)
         live, keys, st = self._bind_for_training(eng)
-        eng.train_set_amp(getattr(self, "train_amp", False))   # the reference's `amp` sweep parameter: False | True / "bf16" | "f16" (with a GradScaler) | "x3"
-        eng.train_set_drop_path(float(getattr(self, "drop_path_rate", 0.0)))
+        eng.train_set_amp(self.train_amp)
+        eng.train_set_drop_path(float(self.drop_path_rate))
         xin = x.detach().to(torch.float32).contiguous()
         B = xin.shape[0]
         inv = torch.empty((B, img, img), device=x.device)
@@ -421,7 +419,7 @@ class SOccDPT_V3(SOccDPT):
         eng.train_forward(xin, inv, seg, dropout_p=float(self.seg_head[3].p), seed=seed)
         # BatchNorm bookkeeping that lives on the host side of nn.BatchNorm2d
         bn = self.seg_head[1]
-        if getattr(self, "grad_exchange", None) is not None:
+        if self.grad_exchange is not None:
             self.grad_exchange.average_buffers([bn.running_mean, bn.running_var])   # keep the BatchNorm running buffers identical on every rank
         torch._C._increment_version([bn.running_mean, bn.running_var])
         bn.num_batches_tracked += 1
@@ -431,7 +429,7 @@ class SOccDPT_V3(SOccDPT):
     def backward(self, d_inv: torch.Tensor, d_seg: torch.Tensor):
         """d loss / d (inv_depth, segmentation) of the last train_forward -> .grad of every trainable parameter, accumulated like
         autograd does when .grad is already populated (no zero_grad since the previous backward).  Replaces loss.backward() of scripts/train_SOccDPT.py:390."""
-        if getattr(self, "_train_x", None) is None:
+        if self._train_x is None:
             raise RuntimeError("backward() needs a train_forward() first")
         eng, xin = self._train_x
         live, keys, st = self._bind_for_training(eng)
@@ -457,7 +455,7 @@ class SOccDPT_V3(SOccDPT):
                 else:
                     runs.append([lo, hi])
         self._last_grad_runs = (eng, st["flat"], runs)
-        if getattr(self, "grad_exchange", None) is not None:
+        if self.grad_exchange is not None:
             # data parallel: average the gradients over the ranks, one collective per run
             self.grad_exchange(st["flat"], runs)
         for g, prev in carried:
@@ -488,7 +486,7 @@ class SOccDPT_V3(SOccDPT):
         eng = self._engine(x.device)
         self._sync_weights(eng)
         rep = eng.calibrate_precision(x.detach().to(torch.float32).contiguous(), budget, holdout, headroom, per_pixel_p999)
-        self.__dict__["_warned_uncalibrated"] = True
+        self._warned_uncalibrated = True
         return rep
 
     def precision_map_source(self, device=None) -> str:
@@ -518,20 +516,13 @@ class _TrainForward(torch.autograd.Function):
     def forward(ctx, net, x, anchor):
         ctx.set_materialize_grads(False)
         inv, seg = net.train_forward(x)
-        net._train_generation = getattr(net, "_train_generation", 0) + 1
+        net._train_generation += 1
         eng = net._engine(x.device)
-        dev = x.device
-        B, C, Hc, Wc = inv.shape[0], net.num_classes, net.height, net.width
-        inv_up = torch.empty((B, Hc, Wc), device=dev)
-        seg_up = torch.empty((B, C, Hc, Wc), device=dev)
-        points = torch.empty((B, Hc, Wc, 3), device=dev)
-        per_frame = net.compute_occ and net.occupancy_per_frame
-        bits = torch.empty((eng.occ_words(),), dtype=torch.int32, device=dev) if (net.compute_occ and not per_frame) else None
-        eng.project(inv, seg, inv_up, seg_up, points, bits, clear_bits=True)
+        inv_up, seg_up, points, bits = net._project_outputs(eng, inv, seg)
         ctx.net, ctx.generation, ctx.hw = net, net._train_generation, (inv.shape[1], inv.shape[2])
         ctx.save_for_backward(inv_up)
         if net.compute_occ:
-            occ = net._frames_occupancy(eng, inv_up, seg) if per_frame else net._finish_occupancy(eng, bits, B)
+            occ = net._finish_occupancy(eng, inv.shape[0], bits, inv_up=inv_up, seg=seg)
             ctx.mark_non_differentiable(occ)
             return inv_up, seg_up, points, occ
         return inv_up, seg_up, points
@@ -539,7 +530,7 @@ class _TrainForward(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g_inv, g_seg, g_pts, *g_rest):
         net = ctx.net
-        if ctx.generation != getattr(net, "_train_generation", 0):
+        if ctx.generation != net._train_generation:
             raise RuntimeError("SOccDPT_V3: backward through a train-mode forward that is not the most recent one (the library keeps one tape per handle: "
                                "call loss.backward() before the next net(x))")
         (inv_up,) = ctx.saved_tensors

@@ -16,7 +16,7 @@ from typing import Dict, Optional, Sequence
 import numpy as np
 import torch
 
-from ..lib import _ptr, _stream_ptr, load_library
+from ..lib import _call, _ptr
 
 
 class OccupancyProcessor:
@@ -60,14 +60,10 @@ class OccupancyProcessor:
         occ = torch.empty((B, g[0], g[1], g[2], self.num_classes), dtype=torch.uint8, device=dev)
         arr = lambda vals, t: (t * len(vals))(*vals)
         intr = arr([self.fx, self.fy, self.cx, self.cy, self.baseline], ctypes.c_double)
-        L = load_library()
-        with torch.cuda.device(dev):
-            rc = L.soccdpt_gt_occupancy(B, H, W, self.num_classes, intr, arr(self.pc_scale, ctypes.c_double), arr(self.pc_shift, ctypes.c_double),
-                                        arr([float(v) for v in self._rot], ctypes.c_double), arr([float(v) for v in self.occupancy_shape], ctypes.c_float),
-                                        arr(list(g), ctypes.c_int), self.point_count_threshold, _ptr(d), _ptr(sc), _ptr(depth), _ptr(pts),
-                                        _ptr(counts), _ptr(occ), _stream_ptr(dev))
-        if rc != 0:
-            raise RuntimeError("soccdpt_gt_occupancy failed: " + L.soccdpt_last_error(None).decode())
+        _call("soccdpt_gt_occupancy", B, H, W, self.num_classes, intr, arr(self.pc_scale, ctypes.c_double), arr(self.pc_shift, ctypes.c_double),
+              arr([float(v) for v in self._rot], ctypes.c_double), arr([float(v) for v in self.occupancy_shape], ctypes.c_float),
+              arr(list(g), ctypes.c_int), self.point_count_threshold, _ptr(d), _ptr(sc), _ptr(depth), _ptr(pts),
+              _ptr(counts), _ptr(occ), device=dev)
         out = dict(depth=depth, points=pts, occupancy_grid=occ.bool(), counts=counts)
         if want_occupancy_points:
             from .occupancy import occupancy_bits_to_points, pack_occupancy

@@ -8,7 +8,7 @@ from typing import Dict
 
 import torch
 
-from ..lib import _ptr, _stream_ptr, load_library
+from ..lib import _call, _ptr, load_library
 
 
 def training_loss(inv: torch.Tensor, seg: torch.Tensor, y_disp: torch.Tensor, mask_disp: torch.Tensor, y_seg: torch.Tensor,
@@ -18,7 +18,6 @@ def training_loss(inv: torch.Tensor, seg: torch.Tensor, y_disp: torch.Tensor, ma
     the same shapes at camera resolution (all cuda).  Returns loss / loss_disp / loss_seg (0-dim), scale / shift [B], and
     d_inv [B,h,w], d_seg [B,C,h,w] = d loss / d network outputs."""
     assert inv.is_cuda, "the HIP path needs cuda tensors (no CPU fallback)"
-    L = load_library()
     B, h, w = inv.shape
     C = seg.shape[1]
     H, W = y_disp.shape[-2:]
@@ -31,11 +30,8 @@ def training_loss(inv: torch.Tensor, seg: torch.Tensor, y_disp: torch.Tensor, ma
     out = torch.empty(3 + 2 * B, dtype=torch.float32, device=dev)
     d_inv = torch.empty_like(inv_)
     d_seg = torch.empty_like(seg_)
-    scratch = torch.empty(int(L.soccdpt_loss_scratch_bytes(B, H, W, h, w)), dtype=torch.uint8, device=dev)
-    with torch.cuda.device(dev):
-        rc = L.soccdpt_training_loss(B, H, W, h, w, C, int(bool(compute_scale_and_shift)), float(alpha), float(loss_depth_w),
-                                     float(loss_seg_w), _ptr(inv_), _ptr(seg_), _ptr(yd), _ptr(md), _ptr(ys), _ptr(ms), _ptr(out),
-                                     _ptr(d_inv), _ptr(d_seg), _ptr(scratch), _stream_ptr(dev))
-    if rc != 0:
-        raise RuntimeError("soccdpt_training_loss failed: " + L.soccdpt_last_error(None).decode())
+    scratch = torch.empty(int(load_library().soccdpt_loss_scratch_bytes(B, H, W, h, w)), dtype=torch.uint8, device=dev)
+    _call("soccdpt_training_loss", B, H, W, h, w, C, int(bool(compute_scale_and_shift)), float(alpha), float(loss_depth_w),
+          float(loss_seg_w), _ptr(inv_), _ptr(seg_), _ptr(yd), _ptr(md), _ptr(ys), _ptr(ms), _ptr(out),
+          _ptr(d_inv), _ptr(d_seg), _ptr(scratch), device=dev)
     return dict(loss=out[0], loss_disp=out[1], loss_seg=out[2], scale=out[3::2], shift=out[4::2], d_inv=d_inv, d_seg=d_seg)

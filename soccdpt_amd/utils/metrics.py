@@ -8,7 +8,7 @@ from typing import Dict
 import torch
 import torch.nn.functional as F
 
-from ..lib import _ptr, _stream_ptr, load_library
+from ..lib import _call, _ptr, load_library
 
 DEPTH_KEYS = ("abs_rel", "sq_rel", "rmse", "rmse_log", "a1", "a2", "a3")
 
@@ -26,7 +26,6 @@ def depth_metrics(y_pred: torch.Tensor, y: torch.Tensor, mask: torch.Tensor) -> 
         y_pred = y_pred.unsqueeze(0)
     if y_pred.shape[-2:] != y.shape[-2:]:
         y_pred = F.interpolate(y_pred.unsqueeze(1), size=y.shape[-2:], mode="bicubic", align_corners=False)[:, 0]
-    L = load_library()
     B = y.shape[0]
     npix = y.shape[1] * y.shape[2]
     p = y_pred.detach().to(torch.float32).contiguous()
@@ -34,10 +33,7 @@ def depth_metrics(y_pred: torch.Tensor, y: torch.Tensor, mask: torch.Tensor) -> 
     m = mask.detach().to(torch.uint8).contiguous()
     out = torch.empty(7 + 2 * B, dtype=torch.float32, device=y.device)
     sc = _scratch(B, 1, y.device)
-    with torch.cuda.device(y.device):
-        rc = L.soccdpt_metrics_depth(_ptr(p), _ptr(t), _ptr(m), B, npix, _ptr(out), _ptr(sc), _stream_ptr(y.device))
-    if rc != 0:
-        raise RuntimeError("soccdpt_metrics_depth failed: " + L.soccdpt_last_error(None).decode())
+    _call("soccdpt_metrics_depth", _ptr(p), _ptr(t), _ptr(m), B, npix, _ptr(out), _ptr(sc), device=y.device)
     res = {k: out[i] for i, k in enumerate(DEPTH_KEYS)}
     res["scale"] = out[7::2]
     res["shift"] = out[8::2]
@@ -50,17 +46,13 @@ def iou_metric(y_pred: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
         y_pred = y_pred.unsqueeze(0)
     if y_pred.shape[-2:] != y.shape[-2:]:
         y_pred = F.interpolate(y_pred, size=y.shape[-2:], mode="bicubic", align_corners=False)
-    L = load_library()
     B, C = y.shape[0], y.shape[1]
     npix = y.shape[2] * y.shape[3]
     p = y_pred.detach().to(torch.float32).contiguous()
     t = y.detach().to(torch.float32).contiguous()
     out = torch.empty(B, dtype=torch.float32, device=y.device)
     sc = _scratch(B, C, y.device)
-    with torch.cuda.device(y.device):
-        rc = L.soccdpt_metrics_iou(_ptr(p), _ptr(t), B, C, npix, _ptr(out), _ptr(sc), _stream_ptr(y.device))
-    if rc != 0:
-        raise RuntimeError("soccdpt_metrics_iou failed: " + L.soccdpt_last_error(None).decode())
+    _call("soccdpt_metrics_iou", _ptr(p), _ptr(t), B, C, npix, _ptr(out), _ptr(sc), device=y.device)
     return out
 
 

@@ -15,7 +15,7 @@ from typing import NamedTuple, Optional, Sequence
 import numpy as np
 import torch
 
-from ..lib import _ptr, _stream_ptr, load_library
+from ..lib import _call, _ptr, load_library
 
 OCC_F32, OCC_U8, OCC_I32 = 0, 1, 2          # SOCCDPT_OCC_* of include/soccdpt_hip.h
 _DTYPES = {torch.float32: OCC_F32, torch.uint8: OCC_U8, torch.bool: OCC_U8, torch.int32: OCC_I32}
@@ -31,11 +31,6 @@ class OccupancyPoints(NamedTuple):
 def _need_cuda(t: torch.Tensor, what: str) -> None:
     if not isinstance(t, torch.Tensor) or t.device.type != "cuda":
         raise RuntimeError(f"{what}: the occupancy kernels run on the GPU only; pass a cuda tensor (there is no CPU fallback)")
-
-
-def _check(rc: int, what: str) -> None:
-    if rc != 0:
-        raise RuntimeError(f"{what} failed: " + load_library().soccdpt_last_error(None).decode())
 
 
 def occupancy_shape_f32(grid_size: Sequence[int], scale: Sequence[float]) -> np.ndarray:
@@ -60,10 +55,7 @@ def pack_occupancy(grid: torch.Tensor, threshold: float = 0.5, strict: bool = Fa
     g = grid.detach().contiguous()
     ncell = g.numel() // rows
     bits = torch.empty((rows, (ncell + 31) // 32), dtype=torch.int32, device=g.device)
-    L = load_library()
-    with torch.cuda.device(g.device):
-        rc = L.soccdpt_occ_pack(_ptr(g), _DTYPES[grid.dtype], rows, ncell, float(threshold), 1 if strict else 0, _ptr(bits), _stream_ptr(g.device))
-    _check(rc, "soccdpt_occ_pack")
+    _call("soccdpt_occ_pack", _ptr(g), _DTYPES[grid.dtype], rows, ncell, float(threshold), 1 if strict else 0, _ptr(bits), device=g.device)
     return bits
 
 
@@ -82,8 +74,7 @@ def occupancy_bits_to_points(bits: torch.Tensor, grid_size: Sequence[int] = (256
         raise ValueError(f"occupancy_bits_to_points: expected {rows} x {nwords} int32 words for grid {tuple(g)} x {C} classes, got {tuple(bits.shape)} {bits.dtype}")
     b = bits.detach().contiguous()
     dev = b.device
-    L = load_library()
-    nscratch = L.soccdpt_occ_points_scratch_bytes(rows, ncell, C)
+    nscratch = load_library().soccdpt_occ_points_scratch_bytes(rows, ncell, C)
     if nscratch == 0:
         raise ValueError("occupancy_bits_to_points: need 1 <= num_classes <= 8 and 1 <= rows <= 65535")
     scratch = torch.empty(nscratch, dtype=torch.uint8, device=dev)
@@ -91,20 +82,18 @@ def occupancy_bits_to_points(bits: torch.Tensor, grid_size: Sequence[int] = (256
     total = torch.empty((), dtype=torch.int64, device=dev)
     shape = occupancy_shape_f32(g, scale)
     table = colors = None
-    with torch.cuda.device(dev):
-        st = _stream_ptr(dev)
-        _check(L.soccdpt_occ_points_count(_ptr(b), rows, ncell, C, _ptr(scratch), nscratch, _ptr(counts), _ptr(total), st), "soccdpt_occ_points_count")
-        if max_points is None:
-            n = int(total.item())
-            points = torch.empty((n, 4), dtype=torch.float64, device=dev)
-        else:
-            n = int(max_points)
-            points = torch.zeros((n, 4), dtype=torch.float64, device=dev)
-        if class_2_color is not None:
-            table = torch.from_numpy(class_color_table(class_2_color, C)).to(dev)
-            colors = torch.empty((n, 3), dtype=torch.uint8, device=dev) if max_points is None else torch.zeros((n, 3), dtype=torch.uint8, device=dev)
-        _check(L.soccdpt_occ_points_write(_ptr(b), rows, (ctypes.c_int32 * 3)(*g), C, (ctypes.c_float * 3)(*[float(v) for v in shape]), _ptr(scratch), nscratch,
-                                          n, _ptr(points), _ptr(table), _ptr(colors), st), "soccdpt_occ_points_write")
+    _call("soccdpt_occ_points_count", _ptr(b), rows, ncell, C, _ptr(scratch), nscratch, _ptr(counts), _ptr(total), device=dev)
+    if max_points is None:
+        n = int(total.item())
+        points = torch.empty((n, 4), dtype=torch.float64, device=dev)
+    else:
+        n = int(max_points)
+        points = torch.zeros((n, 4), dtype=torch.float64, device=dev)
+    if class_2_color is not None:
+        table = torch.from_numpy(class_color_table(class_2_color, C)).to(dev)
+        colors = torch.empty((n, 3), dtype=torch.uint8, device=dev) if max_points is None else torch.zeros((n, 3), dtype=torch.uint8, device=dev)
+    _call("soccdpt_occ_points_write", _ptr(b), rows, (ctypes.c_int32 * 3)(*g), C, (ctypes.c_float * 3)(*[float(v) for v in shape]), _ptr(scratch), nscratch,
+          n, _ptr(points), _ptr(table), _ptr(colors), device=dev)
     return OccupancyPoints(points, colors, counts, total)
 
 
@@ -161,10 +150,7 @@ def occupancy_iou(pred: torch.Tensor, gt: torch.Tensor, num_classes: int = 3, gr
         raise ValueError("occupancy_iou: grid_size does not match the number of packed words")
     rows = gb.shape[0]
     counts = torch.empty((rows, C, 4), dtype=torch.int64, device=gb.device)
-    L = load_library()
-    with torch.cuda.device(gb.device):
-        rc = L.soccdpt_occ_iou_counts(_ptr(pb), pb.shape[0], _ptr(gb), rows, ncell, C, _ptr(counts), _stream_ptr(gb.device))
-    _check(rc, "soccdpt_occ_iou_counts")
+    _call("soccdpt_occ_iou_counts", _ptr(pb), pb.shape[0], _ptr(gb), rows, ncell, C, _ptr(counts), device=gb.device)
     c = counts.double()
     inter, union, npred, ngt = c[..., 0], c[..., 1], c[..., 2], c[..., 3]
     iou = inter / (union + 1e-7)

@@ -16,7 +16,7 @@ from typing import Iterable, Iterator, List, Tuple
 
 import torch
 
-from ..lib import _stream_ptr, load_library
+from ..lib import _call
 
 
 class Adam:
@@ -44,7 +44,6 @@ class Adam:
                 st = self.state[p] = dict(step=0, exp_avg=torch.zeros_like(p), exp_avg_sq=torch.zeros_like(p))
             st["step"] += 1
             groups.setdefault((st["step"], p.device), []).append((p, st))
-        L = load_library()
         for (step, dev), items in groups.items():
             n = len(items)
             arr = lambda ptrs: (ctypes.c_void_p * n)(*ptrs)
@@ -54,11 +53,7 @@ class Adam:
             ms = arr([s["exp_avg"].data_ptr() for _, s in items])
             vs = arr([s["exp_avg_sq"].data_ptr() for _, s in items])
             sizes = (ctypes.c_size_t * n)(*[p.numel() for p, _ in items])
-            with torch.cuda.device(dev):
-                rc = L.soccdpt_adam_step(n, ps, gs, ms, vs, sizes, self.lr, self.betas[0], self.betas[1], self.eps, self.weight_decay, step,
-                                         _stream_ptr(dev))
-            if rc != 0:
-                raise RuntimeError("soccdpt_adam_step failed: " + L.soccdpt_last_error(None).decode())
+            _call("soccdpt_adam_step", n, ps, gs, ms, vs, sizes, self.lr, self.betas[0], self.betas[1], self.eps, self.weight_decay, step, device=dev)
             # the kernel wrote through raw pointers: bump the autograd version counters so that everything keyed on
             # tensor._version (SOccDPT_V3._sync_weights re-runs soccdpt_prepare) sees the update
             torch._C._increment_version([p for p, _ in items])

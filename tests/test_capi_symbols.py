@@ -150,3 +150,66 @@ def test_igemm_kernels_use_no_scratch(tmp_path):
                 n += 1
                 assert int(scratch.group(1)) == 0, f"{name.group(1)} uses {scratch.group(1)} bytes of scratch per lane"
     assert n >= 40, f"only {n} igemm kernels found in the code object metadata"
+
+
+_C_SCALARS = {"int": ("int", True, 4), "int32_t": ("int", True, 4), "uint32_t": ("int", False, 4), "long": ("int", True, ctypes.sizeof(ctypes.c_long)),
+              "int64_t": ("int", True, 8), "uint64_t": ("int", False, 8), "size_t": ("int", False, ctypes.sizeof(ctypes.c_size_t)),
+              "unsigned long long": ("int", False, 8), "float": ("float", True, 4), "double": ("float", True, 8)}
+
+
+def _c_class(decl: str, is_param: bool):
+    """'const float* dev_x' / 'size_t' -> 'pointer' | 'void' | (int | float, signed, bytes)."""
+    if "*" in decl:
+        return "pointer"
+    words = [w for w in decl.split() if w != "const"]
+    if is_param and " ".join(words) not in _C_SCALARS:
+        words = words[:-1]                      # the parameter's name
+    t = " ".join(words)
+    return "void" if t == "void" else _C_SCALARS[t]
+
+
+def _ctypes_class(t):
+    if t is None:
+        return "void"
+    if t in (ctypes.c_void_p, ctypes.c_char_p) or issubclass(t, ctypes._Pointer):
+        return "pointer"
+    code = t._type_
+    assert code in "iIlLqQfd", f"{t}: not a pointer, integer or float"
+    return ("float" if code in "fd" else "int", code in "ilqfd", ctypes.sizeof(t))
+
+
+def _header_prototypes():
+    text = open(os.path.join(REPO, "include", "soccdpt_hip.h")).read()
+    code = re.sub(r"//[^\n]*", "", re.sub(r"/\*.*?\*/", "", text, flags=re.S))
+    out = {}
+    for ret, name, params in re.findall(r"^\s*([A-Za-z_][\w \*]*?[\s\*])(soccdpt_[a-z_0-9]+)\s*\(([^)]*)\)\s*;", code, flags=re.M):
+        assert name not in out, f"{name} is declared twice"
+        plist = [] if params.strip() in ("", "void") else [" ".join(p.split()) for p in params.split(",")]
+        out[name] = (_c_class(ret, False), [_c_class(p, True) for p in plist])
+    return out
+
+
+def test_prototype_table_matches_the_header():
+    """soccdpt_amd.lib.PROTOTYPES (what load_library() applies to the shared object) against the prototypes of include/soccdpt_hip.h: the same set of
+    names, the same number of parameters, and in every position -- the return value included -- the same class: pointer, or signed / unsigned
+    integer or float of the same width.  A parameter added to the header without the binding following fails here; no built library is needed."""
+    from soccdpt_amd.lib import PROTOTYPES
+    header = _header_prototypes()
+    assert sorted(header) == _declared() and len(header) == 78, "the prototype regex and the symbol regex disagree about what the header declares"
+    assert sorted(PROTOTYPES) == sorted(header), (sorted(set(header) - set(PROTOTYPES)), sorted(set(PROTOTYPES) - set(header)))
+    assert list(PROTOTYPES) == list(header), "the table follows the header's order"
+    for name, (restype, argtypes) in PROTOTYPES.items():
+        want_ret, want_args = header[name]
+        assert isinstance(argtypes, list), f"{name}: no argtypes"
+        assert _ctypes_class(restype) == want_ret, f"{name}: returns {want_ret} in the header, {restype} in the table"
+        assert len(argtypes) == len(want_args), f"{name}: {len(want_args)} parameters in the header, {len(argtypes)} in the table"
+        for i, (a, w) in enumerate(zip(argtypes, want_args)):
+            assert _ctypes_class(a) == w, f"{name}: parameter {i} is {w} in the header, {a} in the table"
+
+
+def test_load_library_leaves_no_function_on_ctypes_defaults():
+    from soccdpt_amd.lib import PROTOTYPES, load_library
+    L = load_library()
+    for name, (restype, argtypes) in PROTOTYPES.items():
+        f = getattr(L, name)
+        assert f.restype is restype and list(f.argtypes) == argtypes, name
