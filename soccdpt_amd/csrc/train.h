@@ -59,8 +59,8 @@ int tr_depth_tail_bwd(const float* dinv, const float* inv, const float* e, const
 int tr_merge_scatter(const float* dg, float* dx, int B, int R, int C, hipStream_t st, std::string& err);
 int tr_patch_im2col(const float* x, float* out, int B, int S, hipStream_t st, std::string& err);
 int tr_pad_cols(const float* in, float* out, int N, int cin, int cout, hipStream_t st, std::string& err);
-int tr_attention_bwd(const float* qkv, const float* attn_out, const float* dO, const float* table, const float* scale, float* dS, float* rowstat, float* dscale_part, float* part, float* dqkv, int B, int res, int ws, int shift, int heads, hipStream_t st, std::string& err);
-// MFMA form of tr_attention_bwd (train_attn.hip): no `part` scratch; rowstat holds {m + ln l, delta}; dscale_part has tr_attention_bwd_mfma_slots(ws) per (window, head)
+// Cosine window attention backward on the matrix cores (train_attn.hip): rowstat holds {m + ln l, delta}; dscale_part has tr_attention_bwd_mfma_slots(ws) per
+// (window, head); a window size without an instantiation is an error
 int tr_attention_bwd_mfma(const float* qkv, const float* attn_out, const float* dO, const float* table, const float* scale, float* dS, float* rowstat,
                           float* dscale_part, float* dqkv, int B, int res, int ws, int shift, int heads, hipStream_t st, std::string& err, OpFmt fmt);   // fmt: F32, BF16 or F16 products
 int tr_attention_bwd_mfma_slots(int ws);
@@ -79,7 +79,7 @@ struct TnDefer {
 int tn_flush(TnDefer& d, hipStream_t st, std::string& err);
 int tr_wgrad_tn(const void* A, long ldA, const void* B, long ldB, size_t K, int Nout, int C, int taps, int rp, OpFmt fmt, float* part, size_t part_floats,
                 float* out, hipStream_t st, std::string& err, float* bias_out = nullptr, TnDefer* defer = nullptr, int perm_C = 0);
-int tr_attn_param_grads(float* dS, const float* dscale_part, const float* table, const float* ls, const float* w0, const float* b0, const float* w2, float* dtable, float* dt, float* hid, float* dls, float* dw0, float* db0, float* dw2, int nwin, int ws, int pws, int heads, hipStream_t st, std::string& err, int dscale_slots = 0);
+int tr_attn_param_grads(float* dS, const float* dscale_part, const float* table, const float* ls, const float* w0, const float* b0, const float* w2, float* dtable, float* dt, float* hid, float* dls, float* dw0, float* db0, float* dw2, int nwin, int ws, int pws, int heads, int dscale_slots, hipStream_t st, std::string& err);
 int tr_drop_path_fill(float* out, int B, float p, unsigned seed, unsigned stream_id, hipStream_t st, std::string& err);
 int tr_scale_rows(const float* in, float* out, const float* scale, size_t M, int C, int rows_per_scale, hipStream_t st, std::string& err);
 int tr_unscale_check(float* g, size_t n, float inv_scale, int* found, hipStream_t st, std::string& err);
@@ -99,11 +99,7 @@ int th_maxpool_bwd(const float* dpool, const float* raw, const float* stats, con
 int th_readout_cat(const float* tok, float* cat, int B, int NT, int E, hipStream_t st, std::string& err);
 int th_readout_cat_bwd(const float* dcat, float* dtok, int B, int NT, int E, int accumulate, hipStream_t st, std::string& err);
 int th_tokens_to_patches(const float* dtok, float* dpatch, int B, int NT, int E, hipStream_t st, std::string& err);
-size_t th_vit_attention_part_floats(int B, int N, int heads);
-int th_vit_attention_fwd(const float* qkv, float* out, float* rowstat, float* part, int B, int N, int heads, hipStream_t st, std::string& err);
-int th_vit_attention_bwd(const float* qkv, const float* O, const float* dO, const float* rowstat, float* part, float* dqkv, int B, int N, int heads, hipStream_t st,
-                         std::string& err);
-// train_attn.hip: MFMA form of th_vit_attention_bwd without its `part` scratch; fmt: F32, BF16 or F16 products
+// train_attn.hip: global softmax attention backward of the ViT blocks on the matrix cores; fmt: F32, BF16 or F16 products
 int th_vit_attention_bwd_mfma(const float* qkv, const float* O, const float* dO, float* rowstat, float* dqkv, int B, int N, int heads, hipStream_t st, std::string& err, OpFmt fmt);
 
 // train_step.cpp: SOccDPT_V3 training step (model/SOccDPT.py:660-685 in train mode + autograd) on SOCCDPT_PREC_F32 handles; arithmetic by soccdpt_train_set_amp (OpFmt)

@@ -705,333 +705,6 @@ __global__ void pad_cols_kernel(const float* __restrict__ in, float* __restrict_
     }
 }
 
-// Cosine window attention backward, one workgroup (64 threads) per (sample, window, head, 64-query block); one thread = one query.
-//   q^ = scale * q/|q|, k^ = k/|k|, S = q^ k^T + bias(rel) + mask, P = softmax(S), O = P v
-// Pass A (this kernel, per query): with the row statistics of attn_rowstat_kernel and delta = dO . O, for every key: p, dP = dO . v, dS = p (dP - delta);
-//   accumulates dq^ (registers), and writes dS to a [.., N, N] scratch for pass B (per key) -- deterministic, no atomics.
-// The bias-table and logit-scale gradients are reduced from that scratch by their own kernels.
-__global__ __launch_bounds__(64) void attn_bwd_q_kernel(const float* __restrict__ qkv, const float* __restrict__ dO, const float* __restrict__ table,
-                                                        const float* __restrict__ scale, const float* __restrict__ rowstat, const float* __restrict__ attn_out,
-                                                        float* __restrict__ dS_out, float* __restrict__ dqkv_part, float* __restrict__ dscale_part, int res, int ws,
-                                                        int shift, int heads, int nseg, size_t part_stride) {
-    __shared__ float Kh[64][33];
-    __shared__ float Vs[64][33];
-    __shared__ float dsT[64][65];
-    const int N = ws * ws, nqb = (N + 63) / 64;
-    const int C = heads * 32, nw = res / ws;
-    int bid = blockIdx.x;
-    const int seg = bid % nseg;      // key tiles seg, seg + nseg, ...: more waves for the stages with few windows (deterministic partial sums)
-    bid /= nseg;
-    float* dqkv = dqkv_part + (size_t)seg * part_stride;
-    const int qb = bid % nqb;
-    bid /= nqb;
-    const int head = bid % heads;
-    bid /= heads;
-    const int wx = bid % nw;
-    bid /= nw;
-    const int wy = bid % nw;
-    const int b = bid / nw;
-    const int widx = (b * nw + wy) * nw + wx;
-    const int tid = threadIdx.x;
-    auto token_row = [&](int p) -> size_t {
-        const int r = p / ws, c = p % ws;
-        int sy = wy * ws + r + shift, sx = wx * ws + c + shift;
-        sy = sy >= res ? sy - res : sy;
-        sx = sx >= res ? sx - res : sx;
-        return (size_t)(b * res + sy) * res + sx;
-    };
-    const int q = qb * 64 + tid;
-    const bool qv = q < N;
-    const int qc = qv ? q : N - 1;
-    const int rq = qc / ws, cq = qc % ws;
-    const float sc = scale[head];
-    float qn[32], dOr[32], dqh[32];
-    float qnorm;
-    {
-        const float* src = qkv + token_row(qc) * (size_t)(3 * C) + head * 32;
-        float ss = 0.f;
-#pragma unroll
-        for (int d = 0; d < 32; ++d) { qn[d] = src[d]; ss += qn[d] * qn[d]; }
-        qnorm = fmaxf(sqrtf(ss), 1e-12f);
-#pragma unroll
-        for (int d = 0; d < 32; ++d) { qn[d] /= qnorm; dqh[d] = 0.f; }
-        const float* dsrc = dO + token_row(qc) * (size_t)C + head * 32;
-#pragma unroll
-        for (int d = 0; d < 32; ++d) dOr[d] = dsrc[d];
-    }
-    const bool lastrow = (shift > 0) && (wy == nw - 1), lastcol = (shift > 0) && (wx == nw - 1);
-    const int half = ws / 2;
-    auto stage = [&](int k0) {
-        __syncthreads();
-        const int k = k0 + tid;
-        const int kc = k < N ? k : N - 1;
-        const float* src = qkv + token_row(kc) * (size_t)(3 * C) + head * 32;
-        float ss = 0.f;
-        float kr[32];
-#pragma unroll
-        for (int d = 0; d < 32; ++d) { kr[d] = src[C + d]; ss += kr[d] * kr[d]; }
-        const float ki = 1.0f / fmaxf(sqrtf(ss), 1e-12f);
-#pragma unroll
-        for (int d = 0; d < 32; ++d) { Kh[tid][d] = kr[d] * ki; Vs[tid][d] = src[2 * C + d]; }
-        __syncthreads();
-    };
-    // row statistics {max, sum exp} come from attn_rowstat_kernel; delta = sum_j p_j (dO . v_j) = dO . O with O the saved attention output
-    float m, l, delta = 0.f;
-    {
-        const float* rs = rowstat + (((size_t)widx * heads + head) * N + qc) * 2;
-        m = rs[0];
-        l = rs[1];
-        const float* orow = attn_out + token_row(qc) * (size_t)C + head * 32;
-#pragma unroll
-        for (int d = 0; d < 32; ++d) delta = fmaf(dOr[d], orow[d], delta);
-    }
-    // dS, dq^.  The dS tile of 64 queries x 64 keys goes through LDS so that the global rows are written 256 bytes at a time
-    // (a lane writing its own row was one 4-byte store per cache line).
-    float dsc = 0.f;
-    float* dSbase = dS_out + ((size_t)widx * heads + head) * N * N;
-    for (int k0 = seg * 64; k0 < N; k0 += 64 * nseg) {
-        stage(k0);
-        const int nk = (N - k0) < 64 ? (N - k0) : 64;
-        for (int kk = 0; kk < nk; ++kk) {
-            float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f, p0 = 0.f, p1 = 0.f, p2 = 0.f, p3 = 0.f;   // independent FMA chains
-#pragma unroll
-            for (int d = 0; d < 32; d += 4) {
-                s0 = fmaf(qn[d], Kh[kk][d], s0); s1 = fmaf(qn[d + 1], Kh[kk][d + 1], s1); s2 = fmaf(qn[d + 2], Kh[kk][d + 2], s2); s3 = fmaf(qn[d + 3], Kh[kk][d + 3], s3);
-                p0 = fmaf(dOr[d], Vs[kk][d], p0); p1 = fmaf(dOr[d + 1], Vs[kk][d + 1], p1); p2 = fmaf(dOr[d + 2], Vs[kk][d + 2], p2); p3 = fmaf(dOr[d + 3], Vs[kk][d + 3], p3);
-            }
-            const float dot = (s0 + s1) + (s2 + s3), dp = (p0 + p1) + (p2 + p3);
-            const int k = k0 + kk, rk = k / ws, ck = k % ws;
-            float sl = dot * sc + table[(size_t)((rq - rk + ws - 1) * (2 * ws - 1) + (cq - ck + ws - 1)) * heads + head];
-            if ((lastrow && ((rk >= half) != (rq >= half))) || (lastcol && ((ck >= half) != (cq >= half)))) sl += -100.0f;
-            const float ds = __expf(sl - m) / l * (dp - delta);
-            dsT[tid][kk] = ds;
-#pragma unroll
-            for (int d = 0; d < 32; ++d) dqh[d] = fmaf(ds, Kh[kk][d], dqh[d]);
-            dsc += ds * dot;      // d scale: S = scale * (qn . k^) + ...
-        }
-        __syncthreads();
-        for (int i = 0; i < 64; ++i) {
-            const int qq = qb * 64 + i;
-            if (qq < N && tid < nk) dSbase[(size_t)qq * N + k0 + tid] = dsT[i][tid];
-        }
-    }
-    if (qv) {
-        // dq^ is w.r.t. q^ = scale * qn: dqn = scale * dqh; dq = (dqn - qn (qn . dqn)) / |q|
-        float dotq = 0.f;
-#pragma unroll
-        for (int d = 0; d < 32; ++d) dotq = fmaf(qn[d], dqh[d] * sc, dotq);
-        float* dst = dqkv + token_row(qc) * (size_t)(3 * C) + head * 32;
-#pragma unroll
-        for (int d = 0; d < 32; ++d) dst[d] = (dqh[d] * sc - qn[d] * dotq) / qnorm;
-    }
-    // per-(window, head, query block) partial of d scale (reduced in fixed order by attn_scale_reduce_kernel)
-    dsc = qv ? dsc : 0.f;
-    for (int o = 1; o < 64; o <<= 1) dsc += __shfl_xor(dsc, o);
-    if (tid == 0) dscale_part[(((size_t)widx * heads + head) * nqb + qb) * nseg + seg] = dsc;
-}
-
-// Pass B, one thread = one key: P[q][k] is recomputed from the logits with the row statistics of attn_rowstat_kernel, dS is read back:
-// dk^_k = sum_q dS[q][k] q^_q ; dv_k = sum_q P[q][k] dO_q.
-__global__ __launch_bounds__(64) void attn_bwd_k_kernel(const float* __restrict__ qkv, const float* __restrict__ dO, const float* __restrict__ table,
-                                                        const float* __restrict__ scale, const float* __restrict__ dS_in, const float* __restrict__ rowstat,
-                                                        float* __restrict__ dqkv_part, int res, int ws, int shift, int heads, int nseg, size_t part_stride) {
-    __shared__ float Qh[64][33];
-    __shared__ float dOs[64][33];
-    __shared__ float st_m[64], st_l[64];
-    const int N = ws * ws, nkb = (N + 63) / 64;
-    const int C = heads * 32, nw = res / ws;
-    int bid = blockIdx.x;
-    const int seg = bid % nseg;
-    bid /= nseg;
-    float* dqkv = dqkv_part + (size_t)seg * part_stride;
-    const int kb = bid % nkb;
-    bid /= nkb;
-    const int head = bid % heads;
-    bid /= heads;
-    const int wx = bid % nw;
-    bid /= nw;
-    const int wy = bid % nw;
-    const int b = bid / nw;
-    const int widx = (b * nw + wy) * nw + wx;
-    const int tid = threadIdx.x;
-    auto token_row = [&](int p) -> size_t {
-        const int r = p / ws, c = p % ws;
-        int sy = wy * ws + r + shift, sx = wx * ws + c + shift;
-        sy = sy >= res ? sy - res : sy;
-        sx = sx >= res ? sx - res : sx;
-        return (size_t)(b * res + sy) * res + sx;
-    };
-    const int k = kb * 64 + tid;
-    const bool kv = k < N;
-    const int kc = kv ? k : N - 1;
-    const int rk = kc / ws, ck = kc % ws;
-    const float sc = scale[head];
-    float kn[32], dkh[32], dv[32];
-    float knorm;
-    {
-        const float* src = qkv + token_row(kc) * (size_t)(3 * C) + head * 32 + C;
-        float ss = 0.f;
-#pragma unroll
-        for (int d = 0; d < 32; ++d) { kn[d] = src[d]; ss += kn[d] * kn[d]; }
-        knorm = fmaxf(sqrtf(ss), 1e-12f);
-#pragma unroll
-        for (int d = 0; d < 32; ++d) { kn[d] /= knorm; dkh[d] = 0.f; dv[d] = 0.f; }
-    }
-    const bool lastrow = (shift > 0) && (wy == nw - 1), lastcol = (shift > 0) && (wx == nw - 1);
-    const int half = ws / 2;
-    for (int q0 = seg * 64; q0 < N; q0 += 64 * nseg) {
-        __syncthreads();
-        {
-            const int q = q0 + tid;
-            const int qc = q < N ? q : N - 1;
-            const float* src = qkv + token_row(qc) * (size_t)(3 * C) + head * 32;
-            float ss = 0.f;
-            float qr[32];
-#pragma unroll
-            for (int d = 0; d < 32; ++d) { qr[d] = src[d]; ss += qr[d] * qr[d]; }
-            const float qi = 1.0f / fmaxf(sqrtf(ss), 1e-12f);
-            const float* dsrc = dO + token_row(qc) * (size_t)C + head * 32;
-#pragma unroll
-            for (int d = 0; d < 32; ++d) { Qh[tid][d] = qr[d] * qi; dOs[tid][d] = dsrc[d]; }
-            const float* rs = rowstat + (((size_t)widx * heads + head) * N + qc) * 2;
-            st_m[tid] = rs[0];
-            st_l[tid] = rs[1];
-        }
-        __syncthreads();
-        const int nq = (N - q0) < 64 ? (N - q0) : 64;
-        for (int qq = 0; qq < nq; ++qq) {
-            const int q = q0 + qq, rq = q / ws, cq = q % ws;
-            float s = 0.f;
-#pragma unroll
-            for (int d = 0; d < 32; ++d) s = fmaf(Qh[qq][d], kn[d], s);
-            s *= sc;
-            s += table[(size_t)((rq - rk + ws - 1) * (2 * ws - 1) + (cq - ck + ws - 1)) * heads + head];
-            if ((lastrow && ((rk >= half) != (rq >= half))) || (lastcol && ((ck >= half) != (cq >= half)))) s += -100.0f;
-            const float p = __expf(s - st_m[qq]) / st_l[qq];
-            const float ds = dS_in[(((size_t)widx * heads + head) * N + q) * N + kc];
-#pragma unroll
-            for (int d = 0; d < 32; ++d) {
-                dkh[d] = fmaf(ds * sc, Qh[qq][d], dkh[d]);     // dS/dk^ = scale * qn
-                dv[d] = fmaf(p, dOs[qq][d], dv[d]);
-            }
-        }
-    }
-    if (kv) {
-        float dotk = 0.f;
-#pragma unroll
-        for (int d = 0; d < 32; ++d) dotk = fmaf(kn[d], dkh[d], dotk);
-        float* dst = dqkv + token_row(kc) * (size_t)(3 * C) + head * 32;
-#pragma unroll
-        for (int d = 0; d < 32; ++d) {
-            dst[C + d] = (dkh[d] - kn[d] * dotk) / knorm;
-            dst[2 * C + d] = dv[d];
-        }
-    }
-}
-
-// row statistics {max, sum exp} of every query (pass A of the forward recomputation, shared by attn_bwd_k_kernel)
-__global__ __launch_bounds__(64) void attn_rowstat_kernel(const float* __restrict__ qkv, const float* __restrict__ table, const float* __restrict__ scale,
-                                                          float* __restrict__ rowstat_part, int res, int ws, int shift, int heads, int nseg, size_t part_stride) {
-    __shared__ float Kh[64][33];
-    const int N = ws * ws, nqb = (N + 63) / 64;
-    const int C = heads * 32, nw = res / ws;
-    int bid = blockIdx.x;
-    const int seg = bid % nseg;
-    bid /= nseg;
-    float* rowstat = rowstat_part + (size_t)seg * part_stride;
-    const int qb = bid % nqb;
-    bid /= nqb;
-    const int head = bid % heads;
-    bid /= heads;
-    const int wx = bid % nw;
-    bid /= nw;
-    const int wy = bid % nw;
-    const int b = bid / nw;
-    const int widx = (b * nw + wy) * nw + wx;
-    const int tid = threadIdx.x;
-    auto token_row = [&](int p) -> size_t {
-        const int r = p / ws, c = p % ws;
-        int sy = wy * ws + r + shift, sx = wx * ws + c + shift;
-        sy = sy >= res ? sy - res : sy;
-        sx = sx >= res ? sx - res : sx;
-        return (size_t)(b * res + sy) * res + sx;
-    };
-    const int q = qb * 64 + tid;
-    const int qc = q < N ? q : N - 1;
-    const int rq = qc / ws, cq = qc % ws;
-    const float sc = scale[head];
-    float qn[32];
-    {
-        const float* src = qkv + token_row(qc) * (size_t)(3 * C) + head * 32;
-        float ss = 0.f;
-#pragma unroll
-        for (int d = 0; d < 32; ++d) { qn[d] = src[d]; ss += qn[d] * qn[d]; }
-        const float qi = 1.0f / fmaxf(sqrtf(ss), 1e-12f);
-#pragma unroll
-        for (int d = 0; d < 32; ++d) qn[d] *= qi;
-    }
-    const bool lastrow = (shift > 0) && (wy == nw - 1), lastcol = (shift > 0) && (wx == nw - 1);
-    const int half = ws / 2;
-    float m = -3.0e38f, l = 0.f;
-    for (int k0 = seg * 64; k0 < N; k0 += 64 * nseg) {
-        __syncthreads();
-        {
-            const int k = k0 + tid;
-            const int kc = k < N ? k : N - 1;
-            const float* src = qkv + token_row(kc) * (size_t)(3 * C) + head * 32 + C;
-            float ss = 0.f;
-            float kr[32];
-#pragma unroll
-            for (int d = 0; d < 32; ++d) { kr[d] = src[d]; ss += kr[d] * kr[d]; }
-            const float ki = 1.0f / fmaxf(sqrtf(ss), 1e-12f);
-#pragma unroll
-            for (int d = 0; d < 32; ++d) Kh[tid][d] = kr[d] * ki;
-        }
-        __syncthreads();
-        const int nk = (N - k0) < 64 ? (N - k0) : 64;
-        for (int kk = 0; kk < nk; ++kk) {
-            float s = 0.f;
-#pragma unroll
-            for (int d = 0; d < 32; ++d) s = fmaf(qn[d], Kh[kk][d], s);
-            s *= sc;
-            const int k = k0 + kk, rk = k / ws, ck = k % ws;
-            s += table[(size_t)((rq - rk + ws - 1) * (2 * ws - 1) + (cq - ck + ws - 1)) * heads + head];
-            if ((lastrow && ((rk >= half) != (rq >= half))) || (lastcol && ((ck >= half) != (cq >= half)))) s += -100.0f;
-            const float mn = fmaxf(m, s);
-            l = l * __expf(m - mn) + __expf(s - mn);
-            m = mn;
-        }
-    }
-    if (q < N) {
-        float* rs = rowstat + (((size_t)widx * heads + head) * N + q) * 2;
-        rs[0] = m;
-        rs[1] = l;
-    }
-}
-
-// merge the per-segment {max, sum exp} pairs into the row statistics
-__global__ void attn_rowstat_combine_kernel(const float* __restrict__ part, float* __restrict__ rowstat, size_t rows, int nseg) {
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < rows; i += (size_t)gridDim.x * blockDim.x) {
-        float M = -3.0e38f;
-        for (int s = 0; s < nseg; ++s) M = fmaxf(M, part[((size_t)s * rows + i) * 2]);
-        float L = 0.f;
-        for (int s = 0; s < nseg; ++s) {
-            const float l = part[((size_t)s * rows + i) * 2 + 1];
-            if (l > 0.f) L += l * __expf(part[((size_t)s * rows + i) * 2] - M);
-        }
-        rowstat[i * 2] = M;
-        rowstat[i * 2 + 1] = L;
-    }
-}
-// sum of the per-segment gradient slabs, in segment order
-__global__ void attn_seg_sum_kernel(const float* __restrict__ part, float* __restrict__ out, size_t n, int nseg) {
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-        float s = 0.f;
-        for (int k = 0; k < nseg; ++k) s += part[(size_t)k * n + i];
-        out[i] = s;
-    }
-}
-
 // d table[r][h] = sum over (q, k with rel(q, k) = r) of dSsum[h][q][k], dSsum = dS summed over the windows (rowsum_kernel).
 // One wave per (r, h): lane = one key row rk of the window (ws <= 64), the ck loop inside; fixed-order wave reduction.
 __global__ __launch_bounds__(64) void attn_table_grad_kernel(const float* __restrict__ dSsum, float* __restrict__ dtable, int ws, int heads) {
@@ -1371,32 +1044,13 @@ int tr_pad_cols(const float* in, float* out, int N, int cin, int cout, hipStream
     SOCCDPT_LAUNCH(pad_cols_kernel, dim3(gs_blocks((size_t)N * cout)), dim3(256), 0, st, in, out, N, cin, cout);
     TK("pad_cols");
 }
-// Segments of the walked axis per (window, head, tile): up to 4 (one per 64-row tile of a 16 x 16 window)
-static int attn_nseg(int ws) {
-    const int tiles = (ws * ws + 63) / 64;
-    return tiles < 4 ? tiles : 4;
-}
-// dS scratch: nwin * heads * N * N floats; rowstat: nwin * heads * N * 2; dscale_part: nwin * heads * nqb * 4;
-// part: 4 * (B * res * res * 3 * heads * 32 + nwin * heads * N * 2) floats of scratch
-int tr_attention_bwd(const float* qkv, const float* attn_out, const float* dO, const float* table, const float* scale, float* dS, float* rowstat, float* dscale_part,
-                     float* part, float* dqkv, int B, int res, int ws, int shift, int heads, hipStream_t st, std::string& err) {
-    const int nw = res / ws, N = ws * ws, nqb = (N + 63) / 64, nseg = attn_nseg(ws);
-    const unsigned blocks = (unsigned)(B * nw * nw * heads * nqb * nseg);
-    const size_t rows = (size_t)B * nw * nw * heads * N, nq = (size_t)B * res * res * 3 * heads * 32;
-    float* part_stat = part + (size_t)nseg * nq;
-    SOCCDPT_LAUNCH(attn_rowstat_kernel, dim3(blocks), dim3(64), 0, st, qkv, table, scale, part_stat, res, ws, shift, heads, nseg, rows * 2);
-    SOCCDPT_LAUNCH(attn_rowstat_combine_kernel, dim3(gs_blocks(rows)), dim3(256), 0, st, part_stat, rowstat, rows, nseg);
-    SOCCDPT_LAUNCH(attn_bwd_q_kernel, dim3(blocks), dim3(64), 0, st, qkv, dO, table, scale, rowstat, attn_out, dS, part, dscale_part, res, ws, shift, heads, nseg, nq);
-    SOCCDPT_LAUNCH(attn_bwd_k_kernel, dim3(blocks), dim3(64), 0, st, qkv, dO, table, scale, dS, rowstat, part, res, ws, shift, heads, nseg, nq);
-    SOCCDPT_LAUNCH(attn_seg_sum_kernel, dim3(gs_blocks(nq)), dim3(256), 0, st, part, dqkv, nq, nseg);
-    TK("attention_bwd");
-}
-// dS is overwritten by its sum over the windows (first nwin = 1 slab); hid: 2 * (2ws-1)^2 * 512 floats of scratch
+// dS is overwritten by its sum over the windows (first nwin = 1 slab); hid: 2 * (2ws-1)^2 * 512 floats of scratch; dscale_part holds dscale_slots
+// partials per (window, head) (tr_attention_bwd_mfma_slots)
 int tr_attn_param_grads(float* dS, const float* dscale_part, const float* table, const float* ls, const float* w0, const float* b0, const float* w2, float* dtable,
-                        float* dt, float* hid, float* dls, float* dw0, float* db0, float* dw2, int nwin, int ws, int pws, int heads, hipStream_t st, std::string& err,
-                        int dscale_slots) {
-    const int T2 = (2 * ws - 1) * (2 * ws - 1), N = ws * ws, nqb = (N + 63) / 64;
-    if (dls) SOCCDPT_LAUNCH(attn_scale_reduce_kernel, dim3(heads), dim3(256), 0, st, dscale_part, ls, dls, nwin, heads, dscale_slots > 0 ? dscale_slots : nqb * attn_nseg(ws));
+                        float* dt, float* hid, float* dls, float* dw0, float* db0, float* dw2, int nwin, int ws, int pws, int heads, int dscale_slots, hipStream_t st,
+                        std::string& err) {
+    const int T2 = (2 * ws - 1) * (2 * ws - 1), N = ws * ws;
+    if (dls) SOCCDPT_LAUNCH(attn_scale_reduce_kernel, dim3(heads), dim3(256), 0, st, dscale_part, ls, dls, nwin, heads, dscale_slots);
     if (dw0 || db0 || dw2) {
         const size_t n = (size_t)heads * N * N;
         // in place: column i of slab 0 is read before it is written, the other slabs are only read

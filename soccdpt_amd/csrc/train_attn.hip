@@ -1,6 +1,6 @@
 // Cosine window attention BACKWARD on the exact-f32 matrix cores (v_mfma_f32_32x32x2_f32), training step of the Swin-V2 encoders.
-// Replaces the one-thread-per-query / per-key VALU kernels of train.hip (attn_rowstat / attn_bwd_q / attn_bwd_k + the segment sum; those stay as
-// the reference form behind SOCCDPT_ATTN_BWD_VALU=1).  Reference: autograd over timm WindowAttention (swin_transformer_v2.py, called from
+// The only attention backward of the library (the one-thread-per-query / per-key kernels of round 2 are gone: docs/DESIGN_HISTORY.md).
+// Reference: autograd over timm WindowAttention (swin_transformer_v2.py, called from
 // /root/reference/SOccDPT/model/backbones/swin_common.py:12-54 through scripts/train_SOccDPT.py:360-393).
 //
 //   q^ = scale q/|q|, k^ = k/|k|, S = q^ k^T + bias(rel) + mask, P = softmax(S), O = P v
@@ -14,8 +14,8 @@
 //           tr_attn_param_grads reduces it over the windows), dscale partial per wave, {m + ln l, delta} stored for pass 1.
 //   PASS 1 (owned = keys, walked = queries) P and dS are RECOMPUTED from the same operands (two more MFMA sets, cheaper than reading dS back), the
 //           per-query statistics ride along with the walked tile; dk^ and dv accumulate in two MFMA accumulators.
-// Every product is an f32 FMA chain inside the MFMA (bitwise an f32 dot product in k order): the gradients are f32-exact like the VALU form, the
-// summation order differs.  Deterministic: no atomics, each output element has one owner.
+// Every product is an f32 FMA chain inside the MFMA (bitwise an f32 dot product in k order): the gradients are f32-exact.
+// Deterministic: no atomics, each output element has one owner.
 #include <hip/hip_runtime.h>
 
 #include <string>
@@ -678,7 +678,7 @@ int tr_attention_bwd_mfma_slots(int ws) {
     return (NT + 3) / 4 * 4;
 }
 
-// Same contract as tr_attention_bwd (train.hip) without its `part` scratch: dqkv [B*res*res][3C] receives dq | dk | dv, dS [nwin][heads][N][N],
+// dqkv [B*res*res][3C] receives dq | dk | dv, dS [nwin][heads][N][N],
 // rowstat [nwin][heads][N][2] = {m + ln l, delta}, dscale_part [nwin][heads][tr_attention_bwd_mfma_slots(ws)].
 int tr_attention_bwd_mfma(const float* qkv, const float* attn_out, const float* dO, const float* table, const float* scale, float* dS, float* rowstat,
                           float* dscale_part, float* dqkv, int B, int res, int ws, int shift, int heads, hipStream_t st, std::string& err, OpFmt fmt) {

@@ -41,38 +41,20 @@ int conv_gen_bwd(Ctx& c, const float* dY, const float* Xhalo, const float* Wtap,
     Tape& T = c.T;
     const int B = c.B;
     const size_t Mo = (size_t)B * Ho * Ho;
-    {
-        // 16-bit amp modes, un-strided convolutions of the wide stages (N, C multiples of 128): dgrad on the 16-bit igemm over the zero-bordered dY image, weight
-        // gradient from the operands as stored in halo pixel order (train_wgrad_tn.hip) -- the path the decoder convolutions take in conv3_bwd, with the
-        // tap-major standardised weights of this encoder on both ends.  SOCCDPT_WGRAD_TRANSPOSE=1 keeps the f32 path below.
-        static const bool tn_off = getenv("SOCCDPT_WGRAD_TRANSPOSE") != nullptr;
-        const OpFmt fmt = amp_fmt(c);
-        const int rp = Ho + 2;
-        const size_t Kh = (size_t)B * rp * rp, Kp = (Kh + 63) / 64 * 64, mrg = (size_t)rp + 1;
-        if (!tn_off && op_is16(fmt) && stride == 1 && pad == 1 && Hi == Ho && N % 128 == 0 && C % 128 == 0 && tr_wgrad_tn_ok(Kp, N, C, 9)) {
-            const size_t es = op_size(fmt);
-            char* const hS = reinterpret_cast<char*>(T.S_halo);
-            TRY(tr_to_halo_full(dY, hS, fmt, B, Ho, Ho, N, c.st, c.err));
-            if (dX_out) {
-                TRY(th_conv_w_dgrad_tap(Wtap, T.S_dw, N, C, c.st, c.err));                         // [C][9][N] f32, rotated
-                TRY(cvt_op(c, T.S_dw, T.S_wt, (size_t)C * 9 * N, fmt));
-                IgemmDesc d;
-                d.X = hS; d.Wt = T.S_wt; d.M = (int)Mo; d.N = C; d.Cin = N; d.taps = 9; d.H = Ho; d.W = Ho; d.out_f32 = dX_out;
-                TRY(gemm(c, d, fmt));
-            }
-            if (dWtap_out) {
-                char* const xS = reinterpret_cast<char*>(T.S_T2);
-                hipError_t e = Kp > Kh ? hipMemsetAsync(hS + Kh * N * es, 0, (Kp - Kh) * N * es, c.st) : hipSuccess;
-                if (e == hipSuccess) e = hipMemsetAsync(xS, 0, mrg * C * es, c.st);
-                if (e == hipSuccess) e = hipMemsetAsync(xS + (mrg + Kh) * C * es, 0, (Kp - Kh + mrg) * C * es, c.st);
-                if (e != hipSuccess) { c.err = std::string("conv_gen_bwd memset: ") + hipGetErrorString(e); return 1; }
-                TRY(cvt_op(c, Xhalo, xS + mrg * C * es, Kh * C, fmt));
-                c.T.xt_tn_src = nullptr;   // S_T2 no longer holds conv3_bwd's staged image
-                TRY(tr_wgrad_tn(hS, N, xS + mrg * C * es, C, Kp, N, C, 9, rp, fmt, T.sk_part, kTrainSkPartFloats, dWtap_out, c.st, c.err));
-            }
-            if (db) TRY(tr_colsum(dY, nullptr, db, T.S_col, Mo, N, 0, c.st, c.err));
-            return 0;
+    // 16-bit amp modes, un-strided convolutions of the wide stages (N, C multiples of 128): the path the decoder convolutions take in conv3_bwd -- dgrad on the
+    // 16-bit igemm over the zero-bordered dY image, weight gradient from the operands as stored in halo pixel order (train_wgrad_tn.hip) -- with the tap-major
+    // standardised weights of this encoder on both ends.  Everything else takes the f32 path below.
+    const OpFmt fmt = amp_fmt(c);
+    if (op_is16(fmt) && stride == 1 && pad == 1 && Hi == Ho && tr_wgrad_tn_ok(conv3_tn_rows(B, Ho), N, C, 9)) {
+        TRY(conv3_dy_halo(c, dY, Ho, N, fmt));
+        if (dX_out) {
+            TRY(th_conv_w_dgrad_tap(Wtap, T.S_dw, N, C, c.st, c.err));                         // [C][9][N] f32, rotated
+            TRY(cvt_op(c, T.S_dw, T.S_wt, (size_t)C * 9 * N, fmt));
+            TRY(conv3_dgrad_s1(c, T.S_wt, Ho, N, C, fmt, dX_out, nullptr));
         }
+        if (dWtap_out) TRY(conv3_wgrad_tn(c, Xhalo, Ho, N, C, fmt, false, dWtap_out, nullptr, false));
+        if (db) TRY(tr_colsum(dY, nullptr, db, T.S_col, Mo, N, 0, c.st, c.err));
+        return 0;
     }
     if (dX_out) {
         if (stride == 1 && pad == 1) {
@@ -81,9 +63,7 @@ int conv_gen_bwd(Ctx& c, const float* dY, const float* Xhalo, const float* Wtap,
             if (e != hipSuccess) { c.err = std::string("conv_gen_bwd memset: ") + hipGetErrorString(e); return 1; }
             TRY(tr_to_halo(dY, T.S_halo, B, Ho, Ho, N, c.st, c.err));
             TRY(th_conv_w_dgrad_tap(Wtap, T.S_wt, N, C, c.st, c.err));
-            IgemmDesc d;
-            d.X = T.S_halo; d.Wt = T.S_wt; d.M = (int)Mo; d.N = C; d.Cin = N; d.taps = 9; d.H = Ho; d.W = Ho; d.out_f32 = dX_out;
-            TRY(gemm(c, d));
+            TRY(conv3_dgrad_s1(c, T.S_wt, Ho, N, C, OpFmt::F32, dX_out, nullptr));
         } else {
             TRY(tr_transpose(Wtap, T.S_wt, OpFmt::F32, N, 9 * C, N, c.st, c.err));   // [9C][N]
             IgemmDesc d;
@@ -184,7 +164,6 @@ void hy_carve(const Handle& h, int B, TArena& ar, Tape& T, size_t& maxAct) {
     Y.GT = ar.f(Mt * E);
     Y.GR = ar.f((size_t)B * H2 * H2 * 256);
     Y.xg = ar.f((size_t)B * (H2 / 2) * (H2 / 2) * 256);
-    Y.attn_part = ar.f(th_vit_attention_part_floats(B, NT, a.vit_heads));
 }
 
 int hy_forward(Ctx& c, const float* x) {
@@ -287,10 +266,7 @@ int hy_forward(Ctx& c, const float* x) {
         IgemmDesc d;
         d.X = v.ln1; d.Wt = c.W(k + "attn.qkv.weight"); d.M = Mt; d.N = 3 * E; d.Cin = E; d.ldx = E; d.bias = c.W(k + "attn.qkv.bias"); d.out_f32 = v.qkv;
         TRY(gemm_fwd(c, d, (size_t)Mt * E, (size_t)3 * E * E));   // x3 operands in the amp modes (train_step.cpp: gemm_fwd), exact f32 otherwise
-        // forward: the exact-f32 MFMA kernel of the inference path (vit_attention.hip); the VALU pair of round 2 stays behind SOCCDPT_ATTN_BWD_VALU
-        static const bool attn_valu = getenv("SOCCDPT_ATTN_BWD_VALU") != nullptr;
-        if (attn_valu) TRY(th_vit_attention_fwd(v.qkv, v.attn, v.rowstat, Y.attn_part, B, NT, a.vit_heads, st, err));
-        else TRY(launch_vit_attention(v.qkv, v.attn, SOCCDPT_PREC_F32, B, NT, a.vit_heads, st, err));
+        TRY(launch_vit_attention(v.qkv, v.attn, SOCCDPT_PREC_F32, B, NT, a.vit_heads, st, err));   // the exact-f32 MFMA kernel of the inference path (vit_attention.hip)
         d = IgemmDesc();
         d.X = v.attn; d.Wt = c.W(k + "attn.proj.weight"); d.M = Mt; d.N = E; d.Cin = E; d.ldx = E; d.bias = c.W(k + "attn.proj.bias"); d.res1 = v.xin; d.out_f32 = v.x1;
         TRY(gemm_fwd(c, d, (size_t)Mt * E, (size_t)E * E));
@@ -381,13 +357,9 @@ int hy_backward(Ctx& c) {
         TRY(tr_axpy(G[2], Y.GT, Mt * E, st, err));                                   // G2 = d x1
         // x1 = xin + proj(attn(qkv(LN1(xin))))
         TRY(linear_bwd(c, G[2], v.attn, c.W(k + "attn.proj.weight"), Mt, E, E, G[0], nullptr, c.Gd(k + "attn.proj.weight"), c.Gd(k + "attn.proj.bias")));
-        static const bool attn_valu = getenv("SOCCDPT_ATTN_BWD_VALU") != nullptr;
-        if (attn_valu) TRY(th_vit_attention_bwd(v.qkv, v.attn, G[0], v.rowstat, Y.attn_part, G[4], B, NT, a.vit_heads, st, err));
-        else {
-            static const bool attn_f32 = getenv("SOCCDPT_ATTN_BWD_F32") != nullptr;   // A/B: keep the exact products in the amp modes too
-            const OpFmt attn_fmt = !attn_f32 && op_is16(amp_fmt(c)) ? amp_fmt(c) : OpFmt::F32;
-            TRY(th_vit_attention_bwd_mfma(v.qkv, v.attn, G[0], v.rowstat, G[4], B, NT, a.vit_heads, st, err, attn_fmt));
-        }
+        // 16-bit products in the 16-bit amp modes (autocast semantics), exact ones otherwise; v.rowstat is this launch's scratch ({m + ln l, delta} per query)
+        const OpFmt attn_fmt = op_is16(amp_fmt(c)) ? amp_fmt(c) : OpFmt::F32;
+        TRY(th_vit_attention_bwd_mfma(v.qkv, v.attn, G[0], v.rowstat, G[4], B, NT, a.vit_heads, st, err, attn_fmt));
         TRY(linear_bwd(c, G[4], v.ln1, c.W(k + "attn.qkv.weight"), Mt, 3 * E, E, G[1], nullptr, c.Gd(k + "attn.qkv.weight"), c.Gd(k + "attn.qkv.bias")));
         TRY(ln_bwd(c, v.xin, c.W(k + "norm1.weight"), G[1], G[0], G[3], Mt, E, c.Gd(k + "norm1.weight"), c.Gd(k + "norm1.bias"), kLnEps));
         TRY(copy_d2d(c, Y.GT, G[2], Mt * E * 4, "hy_backward"));

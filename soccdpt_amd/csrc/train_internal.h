@@ -63,12 +63,12 @@ struct HyTape {
     float* gn_part[2] = {nullptr, nullptr};   // per-tile GroupNorm partials of the convolution(s) whose output is waiting for its gn_apply: [0] conv1 / conv2 / conv3, [1] the shortcut projection
     int gn_bm[2] = {0, 0};                     // M-tile rows of the launch that last filled each buffer
     size_t gn_part_floats = 0;
-    float *GT, *GR, *xg, *attn_part;           // token-stream / residual-stream gradients, strided-shortcut operand, attention segment partials
+    float *GT, *GR, *xg;                       // token-stream / residual-stream gradients, strided-shortcut operand
 };
 
 struct Tape {
     HyTape hy;
-    const float* xt_tn_src = nullptr;   // the halo image whose 16-bit copy (train_wgrad_tn.hip layout) is in S_T2, or nullptr: conv3_bwd's reuse_xt only holds within one layout
+    const float* xt_tn_src = nullptr;   // the halo image whose copy in conv3_wgrad_tn's layout is in S_T2, or nullptr: conv3_bwd's reuse_xt only holds within one layout
     // encoder
     float *patches, *pe_wpad, *pe_pre, *x0;
     std::vector<BlkT> blk[4];
@@ -86,7 +86,7 @@ struct Tape {
     // backward scratch
     float *G[5], *GX, *GP, *DOC, *DF[4];
     float *S_T1, *S_T2, *S_halo, *S_wt, *S_dw, *S_col, *S_vec;
-    float *dS, *rowstat, *dscale_part, *dtable, *dt, *S_cpb, *attn_part;
+    float *dS, *rowstat, *dscale_part, *dtable, *dt, *S_cpb;
     float* sk_part;
     float* tn_arena;
     size_t S_dw_n = 0;   // floats of S_dw (a weight gradient written THERE is post-processed at once by its caller: never deferred)
@@ -131,6 +131,12 @@ const void* staged_wt(const Ctx& c, const float* W);
 int linear_bwd(Ctx& c, const float* dY, const float* X, const float* W, size_t M, int N, int K, float* dX_out, const float* dX_res, float* dW, float* db);
 int conv3_bwd(Ctx& c, const float* dY, const float* Xhalo, const float* W, int r, int N, int C, float* dX_out, const float* dX_res, float* dW, float* db,
               bool reuse_xt = false);   // reuse_xt: the im2col^T of Xhalo is still in S_T2 from the previous call
+// The 3x3 staging conv3_bwd shares with the ViT-hybrid encoder's conv_gen_bwd (stride 1 / pad 1; the callers differ in the weight layout and the output permute)
+inline size_t conv3_tn_rows(int B, int r) { return ((size_t)B * (r + 2) * (r + 2) + 63) / 64 * 64; }   // K of conv3_wgrad_tn: halo pixels, padded to a k-tile
+int conv3_dy_halo(Ctx& c, const float* dY, int r, int N, OpFmt fmt);   // dY as a zero-bordered image of format fmt in S_halo
+int conv3_dgrad_s1(Ctx& c, const void* Wrot, int r, int N, int C, OpFmt fmt, float* dX_out, const float* dX_res);   // over S_halo and the rotated filter [C][9][N]
+// weight gradient from S_halo and Xhalo as stored (train_wgrad_tn.hip): tap-major into `out`, or -- param_layout -- [N][C][3][3] by this pass's batched sum
+int conv3_wgrad_tn(Ctx& c, const float* Xhalo, int r, int N, int C, OpFmt fmt, bool reuse_xt, float* out, float* bias, bool param_layout);
 int ln_bwd(Ctx& c, const float* y, const float* g, const float* dout, float* dy, float* xhat, size_t M, int C, float* dg, float* dbeta, float eps = 1e-5f);
 IgemmDesc conv_desc(const void* X, int Cin, const void* Wt, int N, int r, int B);
 bool any_grad(const Handle& h, const std::string& prefix);

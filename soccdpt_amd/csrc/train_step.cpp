@@ -11,7 +11,6 @@
 // Gradients are WRITTEN (not accumulated) to the buffers bound with soccdpt_bind_grad; a weight without a bound gradient is frozen and its
 // weight-gradient GEMM is skipped (the reference freezes / partially unfreezes the encoder: model/loss.py:110-152).
 #include <cstdio>
-#include <cstdlib>
 
 #include "train_internal.h"
 
@@ -77,7 +76,7 @@ void carve(const Handle& h, int B, TArena& ar, Tape& T) {
         const size_t nwin = (size_t)B * (res / ws) * (res / ws), N = (size_t)ws * ws;
         maxDS = std::max(maxDS, nwin * H * N * N);
         maxStat = std::max(maxStat, nwin * H * N * 2);
-        maxPart = std::max(maxPart, nwin * H * ((N + 63) / 64));
+        maxPart = std::max(maxPart, nwin * H * (size_t)tr_attention_bwd_mfma_slots(ws));
         maxTab = std::max(maxTab, (size_t)(2 * ws - 1) * (2 * ws - 1) * H);
         if (s < 3) {
             T.mg[s] = ar.f(M * C);            // [M/4][4C]
@@ -148,8 +147,7 @@ void carve(const Handle& h, int B, TArena& ar, Tape& T) {
     T.S_vec = ar.f(std::max((size_t)4 * Cmax, (size_t)4 * F) * 2);
     T.dS = ar.f(maxDS);
     T.rowstat = ar.f(maxStat);
-    T.dscale_part = ar.f(maxPart * 4);
-    T.attn_part = ar.f(a.hybrid ? 64 : 4 * (M0 * 3 * a.embed + maxStat));
+    T.dscale_part = ar.f(maxPart);
     T.dtable = ar.f(maxTab);
     T.dt = ar.f(maxTab);
     T.S_cpb = ar.f(a.hybrid ? 64 : (size_t)2 * (2 * a.window - 1) * (2 * a.window - 1) * 512);
@@ -206,11 +204,10 @@ int gemm_wgrad(Ctx& c, IgemmDesc d, OpFmt fmt) {
     // Tiles.  Default for the wide layers (M, N multiples of 128, >= 8 tiles): the 8-wave 128 x 128 tile -- these launches are L2 -> LDS fill bound and it
     // carries 64 FLOP per staged byte (16-bit) against 21 for 32 x 64 -- with the DEFERRED reduction (igemm.h sk_defer).  Rounds 2 and early 3 measured
     // the big tiles slower (f32 4 waves 51.2 vs 45.2 ms, x3 37.5 vs 36.6 ms per step): that was the last-arriver reduction, one workgroup walking 14
-    // partial tiles of 64 KB with L2-bypassing loads (~400 us per launch).  SOCCDPT_SK_SMALL_TILES=1 selects the round-2 forms for A/B.
+    // partial tiles of 64 KB with L2-bypassing loads (~400 us per launch).  The other shapes keep the small tiles.
     long tiles = amp ? (long)((d.M + 31) / 32) * ((d.N + 63) / 64) : (long)((d.M + 63) / 64) * ((d.N + 63) / 64);
     long nk = (long)d.taps * d.Cin / (amp ? 128 : 32);
-    static const bool small_tiles = getenv("SOCCDPT_SK_SMALL_TILES") != nullptr;
-    const bool big = !small_tiles && d.M % 128 == 0 && d.N % 128 == 0 && d.Cin % 64 == 0 && (long)(d.M / 128) * (d.N / 128) >= 8 &&
+    const bool big = d.M % 128 == 0 && d.N % 128 == 0 && d.Cin % 64 == 0 && (long)(d.M / 128) * (d.N / 128) >= 8 &&
                      (!d.wt_grp_rows || d.wt_grp_rows % 128 == 0);
     if (big) {
         d.tune = amp ? 46 : 3;
@@ -224,8 +221,7 @@ int gemm_wgrad(Ctx& c, IgemmDesc d, OpFmt fmt) {
     while (S > 1 && (size_t)S * d.M * d.N > kTrainSkPartFloats) --S;
     if (S > 1 && (size_t)tiles <= kTrainSkCountWords) {
         d.splitk = (int)S; d.sk_part = c.T.sk_part; d.sk_count = c.T.sk_count; d.sk_part_floats = kTrainSkPartFloats; d.sk_count_words = kTrainSkCountWords;
-        static const bool no_defer = getenv("SOCCDPT_SK_NO_DEFER") != nullptr;
-        if ((big || S >= 4) && !no_defer && d.N % 4 == 0) d.sk_defer = 1;   // many splits: sum them in a second chip-wide launch instead of in the last workgroup
+        if ((big || S >= 4) && d.N % 4 == 0) d.sk_defer = 1;   // many splits: sum them in a second chip-wide launch instead of in the last workgroup
     } else if (big) {
         d.tune = -1;
     }
@@ -238,23 +234,10 @@ int copy_d2d(Ctx& c, void* dst, const void* src, size_t bytes, const char* what)
     return 0;
 }
 
-// A/B switch: SOCCDPT_BIAS_COLSUM=1 keeps the separate column-sum launches for the bias gradients of the layers whose weight gradient runs on wgrad_tn
-static bool bias_in_wgrad() {
-    static const bool off = getenv("SOCCDPT_BIAS_COLSUM") != nullptr;
-    return !off;
-}
-
-// A/B switch: SOCCDPT_WGRAD_TRANSPOSE=1 keeps the transposing weight-gradient path of round 2 in the 16-bit amp modes
-static bool wgrad_tn_on() {
-    static const bool off = getenv("SOCCDPT_WGRAD_TRANSPOSE") != nullptr;
-    return !off;
-}
-
 int stage_weights(Ctx& c) {
-    static const bool off = getenv("SOCCDPT_NO_WEIGHT_BATCH") != nullptr;   // A/B switch: one staging launch per layer, as in rounds 2-3
     Tape& T = c.T;
     T.wt_by_ptr.clear();
-    if (off || !T.WT) return 0;
+    if (!T.WT) return 0;
     const OpFmt fmt = amp_fmt(c);
     TrBatchTable t;
     t.n = 0;
@@ -298,14 +281,14 @@ int linear_bwd(Ctx& c, const float* dY, const float* X, const float* W, size_t M
     // Weight gradient from the operands as stored (train_wgrad_tn.hip): no transposes.  Token counts that are not a k-tile multiple (577-token ViT
     // sequences) get zero rows appended to both operands (zero bytes are x3 zeros too).
     const size_t Mtn = (M + 63) / 64 * 64;
-    const bool tn = fmt != OpFmt::F32 && dW && wgrad_tn_on() && tr_wgrad_tn_ok(Mtn, N, K, 1);
+    const bool tn = fmt != OpFmt::F32 && dW && tr_wgrad_tn_ok(Mtn, N, K, 1);
     // Both operand conversions of the layer in ONE launch then: dY for the two gradient GEMMs, X for the weight gradient (round 5; two launches of a
     // scalar kernel per layer before)
     const bool pair = tn && (fmt == OpFmt::X3 || ((M * N) % 4 == 0 && (M * K) % 4 == 0));
     char* const yS = reinterpret_cast<char*>(T.S_T1);   // dY and X in the launch format
     char* const xS = reinterpret_cast<char*>(T.S_T2);
     // a gradient written into scratch (standardised ResNetV2 kernels, the padded patch embedding) is read by its caller's next launch: summed at once; parameter gradients wait for the batched sum
-    TnDefer* const df = c.may_defer(dW, bias_in_wgrad() ? db : nullptr) ? &c.tn : nullptr;   // (the qkv bias gradient, e.g., goes through scratch into q_bias / v_bias)
+    TnDefer* const df = c.may_defer(dW, db) ? &c.tn : nullptr;   // (the qkv bias gradient, e.g., goes through scratch into q_bias / v_bias)
     if (pair) TRY(tr_cvt_pair(dY, yS, M * N, X, xS, M * K, fmt, c.st, c.err));
     if (dX_out) {
         IgemmDesc d;
@@ -327,8 +310,8 @@ int linear_bwd(Ctx& c, const float* dY, const float* X, const float* W, size_t M
             if (e != hipSuccess) { c.err = std::string("linear_bwd memset: ") + hipGetErrorString(e); return 1; }
         }
         // (the bias gradient = column sums of dY rides in the same launch: one more MFMA per fragment against ones, train_wgrad_tn.hip)
-        TRY(tr_wgrad_tn(yS, N, xS, K, Mtn, N, K, 1, 0, fmt, T.sk_part, kTrainSkPartFloats, dW, c.st, c.err, bias_in_wgrad() ? db : nullptr, df));
-        if (bias_in_wgrad()) db = nullptr;
+        TRY(tr_wgrad_tn(yS, N, xS, K, Mtn, N, K, 1, 0, fmt, T.sk_part, kTrainSkPartFloats, dW, c.st, c.err, db, df));
+        db = nullptr;
     } else if (dW) {
         const int Mp = (int)(op_is16(fmt) ? (M + 127) / 128 * 128 : (M + 31) / 32 * 32);   // k-tile multiple; the padding rows are zero
         TRY(tr_transpose(dY, yS, fmt, (int)M, N, Mp, c.st, c.err));   // [N][Mp]
@@ -339,6 +322,50 @@ int linear_bwd(Ctx& c, const float* dY, const float* X, const float* W, size_t M
     }
     if (db) TRY(tr_colsum(dY, nullptr, db, T.S_col, M, N, 0, c.st, c.err));
     return 0;
+}
+
+// dY [B*r*r][N] as the zero-bordered image [B][r+2][r+2][N] of format fmt in S_halo: the X operand of the stride-1 / pad-1 dgrad (conv3_dgrad_s1) and the
+// A operand of conv3_wgrad_tn
+int conv3_dy_halo(Ctx& c, const float* dY, int r, int N, OpFmt fmt) {
+    if (N % 8 == 0) return tr_to_halo_full(dY, c.T.S_halo, fmt, c.B, r, r, N, c.st, c.err);   // writes the zero border itself
+    // (f32 only: the other formats have N % 32 == 0) clear the buffer first
+    hipError_t e = hipMemsetAsync(c.T.S_halo, 0, (size_t)c.B * (r + 2) * (r + 2) * N * op_size(fmt), c.st);
+    if (e != hipSuccess) { c.err = std::string("conv3_dy_halo memset: ") + hipGetErrorString(e); return 1; }
+    return tr_to_halo(dY, c.T.S_halo, c.B, r, r, N, c.st, c.err);
+}
+
+// Stride-1 / pad-1 dgrad: dX_out [B*r*r][C] = conv3x3(the dY image in S_halo, Wrot) (+ dX_res), the forward's implicit GEMM over the rotated filter
+// Wrot [C][9][N] in format fmt
+int conv3_dgrad_s1(Ctx& c, const void* Wrot, int r, int N, int C, OpFmt fmt, float* dX_out, const float* dX_res) {
+    IgemmDesc d;
+    d.M = c.B * r * r; d.N = C; d.Cin = N; d.taps = 9; d.H = r; d.W = r; d.res1 = dX_res; d.out_f32 = dX_out;
+    d.X = c.T.S_halo; d.Wt = Wrot;
+    return gemm(c, d, fmt);
+}
+
+// Weight gradient of a stride-1 / pad-1 3x3 convolution from the operands as stored, in halo pixel order (train_wgrad_tn.hip; shapes: tr_wgrad_tn_ok over
+// conv3_tn_rows): A = the dY image of conv3_dy_halo in S_halo, B = the input's halo image converted to the operand format into S_T2; tap (ky, kx) reads B
+// (ky - 1)(r + 2) + (kx - 1) rows further on.  K is padded to a k-tile with zero rows of A; B gets zero margins of r + 3 rows on both sides (border pixels of A
+// are zero, but 0 * NaN is not).  reuse_xt: B is left as it is when S_T2 still holds Xhalo's copy (Tape::xt_tn_src).  bias: the column sums of dY ride in the
+// launch (its zero border adds nothing).  param_layout: `out` is a bound gradient [N][C][3][3] that the batched sum of this pass writes (Ctx::may_defer holds);
+// otherwise `out` receives the kernel's tap-major [N][9][C] at once.
+int conv3_wgrad_tn(Ctx& c, const float* Xhalo, int r, int N, int C, OpFmt fmt, bool reuse_xt, float* out, float* bias, bool param_layout) {
+    Tape& T = c.T;
+    const size_t es = op_size(fmt);
+    char* const hS = reinterpret_cast<char*>(T.S_halo);
+    char* const xS = reinterpret_cast<char*>(T.S_T2);
+    const int rp = r + 2;
+    const size_t Kh = (size_t)c.B * rp * rp, Kp = conv3_tn_rows(c.B, r), mrg = (size_t)rp + 1;
+    hipError_t e = Kp > Kh ? hipMemsetAsync(hS + Kh * N * es, 0, (Kp - Kh) * N * es, c.st) : hipSuccess;
+    if (!reuse_xt || T.xt_tn_src != Xhalo) {
+        T.xt_tn_src = Xhalo;
+        if (e == hipSuccess) e = hipMemsetAsync(xS, 0, mrg * C * es, c.st);
+        if (e == hipSuccess) e = hipMemsetAsync(xS + (mrg + Kh) * C * es, 0, (Kp - Kh + mrg) * C * es, c.st);
+        if (e == hipSuccess) TRY(cvt_op(c, Xhalo, xS + mrg * C * es, Kh * C, fmt));
+    }
+    if (e != hipSuccess) { c.err = std::string("conv3_wgrad_tn memset: ") + hipGetErrorString(e); return 1; }
+    return tr_wgrad_tn(hS, N, xS + mrg * C * es, C, Kp, N, C, 9, rp, fmt, T.sk_part, kTrainSkPartFloats, out, c.st, c.err, bias, param_layout ? &c.tn : nullptr,
+                       param_layout ? C : 0);
 }
 
 // y = conv3x3(Xhalo, W) + b backward.  dY plain [B*r*r][N], Xhalo [B][r+2][r+2][C], W [N][C][3][3].
@@ -352,43 +379,21 @@ int conv3_bwd(Ctx& c, const float* dY, const float* Xhalo, const float* W, int r
     const size_t es = op_size(fmt);
     char* const yS = reinterpret_cast<char*>(T.S_T1);
     char* const xS = reinterpret_cast<char*>(T.S_T2);
-    char* const hS = reinterpret_cast<char*>(T.S_halo);
     if (dX_out) {
-        if (N % 8 == 0) TRY(tr_to_halo_full(dY, hS, fmt, B, r, r, N, c.st, c.err));   // writes the zero border itself
-        else {                                                                         // (f32 only: the other formats have N % 32 == 0) clear the buffer first
-            hipError_t e = hipMemsetAsync(hS, 0, (size_t)B * (r + 2) * (r + 2) * N * es, c.st);
-            if (e != hipSuccess) { c.err = std::string("conv3_bwd memset: ") + hipGetErrorString(e); return 1; }
-            TRY(tr_to_halo(dY, T.S_halo, B, r, r, N, c.st, c.err));
-        }
-        IgemmDesc d;
-        d.M = (int)M; d.N = C; d.Cin = N; d.taps = 9; d.H = r; d.W = r; d.res1 = dX_res; d.out_f32 = dX_out;
-        d.X = hS; d.Wt = staged_wt(c, W);
-        if (!d.Wt) { TRY(tr_conv_w_dgrad(W, T.S_wt, fmt, N, C, c.st, c.err)); d.Wt = T.S_wt; }   // [C][9][N], rotated
-        TRY(gemm(c, d, fmt));
+        TRY(conv3_dy_halo(c, dY, r, N, fmt));
+        const void* Wrot = staged_wt(c, W);
+        if (!Wrot) { TRY(tr_conv_w_dgrad(W, T.S_wt, fmt, N, C, c.st, c.err)); Wrot = T.S_wt; }   // [C][9][N], rotated
+        TRY(conv3_dgrad_s1(c, Wrot, r, N, C, fmt, dX_out, dX_res));
     }
-    if (dW && fmt != OpFmt::F32 && wgrad_tn_on() && tr_wgrad_tn_ok((size_t)((size_t)B * (r + 2) * (r + 2) + 63) / 64 * 64, N, C, 9)) {
-        // Operands as stored, in halo pixel order (train_wgrad_tn.hip): A = dY as the zero-bordered image the dgrad launch staged, B = the input's halo image
-        // converted to the operand format; tap (ky, kx) reads B (ky - 1)(r + 2) + (kx - 1) rows further on.  K is padded to a k-tile with zero rows of A; B gets
-        // zero margins of r + 3 rows on both sides (border pixels of A are zero, but 0 * NaN is not).
-        const int rp = r + 2;
-        const size_t Kh = (size_t)B * rp * rp, Kp = (Kh + 63) / 64 * 64, mrg = (size_t)rp + 1;
-        if (!dX_out) TRY(tr_to_halo_full(dY, hS, fmt, B, r, r, N, c.st, c.err));
-        hipError_t e = Kp > Kh ? hipMemsetAsync(hS + Kh * N * es, 0, (Kp - Kh) * N * es, c.st) : hipSuccess;
-        if (!reuse_xt || T.xt_tn_src != Xhalo) {
-            T.xt_tn_src = Xhalo;
-            if (e == hipSuccess) e = hipMemsetAsync(xS, 0, mrg * C * es, c.st);
-            if (e == hipSuccess) e = hipMemsetAsync(xS + (mrg + Kh) * C * es, 0, (Kp - Kh + mrg) * C * es, c.st);
-            if (e == hipSuccess) TRY(cvt_op(c, Xhalo, xS + mrg * C * es, Kh * C, fmt));
-        }
-        if (e != hipSuccess) { c.err = std::string("conv3_bwd memset: ") + hipGetErrorString(e); return 1; }
-        float* const bias = bias_in_wgrad() ? db : nullptr;   // dY in halo order: its zero border adds nothing to the column sums
-        if (C % 4 == 0 && c.may_defer(dW, bias)) {            // deferred: the batched sum writes the parameter layout itself
-            TRY(tr_wgrad_tn(hS, N, xS + mrg * C * es, C, Kp, N, C, 9, rp, fmt, T.sk_part, kTrainSkPartFloats, dW, c.st, c.err, bias, &c.tn, C));
+    if (dW && fmt != OpFmt::F32 && tr_wgrad_tn_ok(conv3_tn_rows(B, r), N, C, 9)) {
+        if (!dX_out) TRY(conv3_dy_halo(c, dY, r, N, fmt));   // (otherwise the image the dgrad launch staged)
+        if (c.may_defer(dW, db)) {   // deferred: the batched sum writes the parameter layout itself
+            TRY(conv3_wgrad_tn(c, Xhalo, r, N, C, fmt, reuse_xt, dW, db, true));
         } else {
-            TRY(tr_wgrad_tn(hS, N, xS + mrg * C * es, C, Kp, N, C, 9, rp, fmt, T.sk_part, kTrainSkPartFloats, T.S_dw, c.st, c.err, bias));
+            TRY(conv3_wgrad_tn(c, Xhalo, r, N, C, fmt, reuse_xt, T.S_dw, db, false));
             TRY(tr_wgrad_permute(T.S_dw, dW, N, C, c.st, c.err));
         }
-        if (bias_in_wgrad()) db = nullptr;
+        db = nullptr;
     } else if (dW && x3 && C % 64 == 0) {
         // x3 only, no im2col: like the shifted views below, but an x3 tensor is cut in 8-element units, so the views must start at multiples of 16 elements:
         // the pixel order pads every halo row to rpp = roundup(r + 2, 16) pixels (vertical taps = +- rpp) and the horizontal taps read three copies
@@ -776,14 +781,9 @@ static int encoder_backward(Ctx& c) {
             if (dp_on) { TRY(tr_scale_rows(G[3], G[4], b.dp, M, C, res * res, st, err)); g_att = G[4]; }
             TRY(ln_bwd(c, b.a_pre, c.W(k + "norm1.weight"), g_att, G[0], G[1], M, C, c.Gd(k + "norm1.weight"), c.Gd(k + "norm1.bias")));
             TRY(linear_bwd(c, G[0], b.attn, c.W(k + "attn.proj.weight"), M, C, C, G[2], nullptr, c.Gd(k + "attn.proj.weight"), c.Gd(k + "attn.proj.bias")));
-            // exact-f32 MFMA form (train_attn.hip); the VALU kernels of round 2 stay selectable for A/B and as the reference form
-            static const bool attn_valu = getenv("SOCCDPT_ATTN_BWD_VALU") != nullptr;
-            // amp modes: the four products of the attention backward on 16-bit MFMAs too (autocast semantics); SOCCDPT_ATTN_BWD_F32=1 keeps them exact (A/B)
-            static const bool attn_f32 = getenv("SOCCDPT_ATTN_BWD_F32") != nullptr;
-            const OpFmt attn_fmt = !attn_f32 && op_is16(amp_fmt(c)) ? amp_fmt(c) : OpFmt::F32;
-            const int dslots = attn_valu ? 0 : tr_attention_bwd_mfma_slots(wsz);
-            if (dslots) TRY(tr_attention_bwd_mfma(b.qkv, b.attn, G[2], b.table, b.scale, T.dS, T.rowstat, T.dscale_part, G[4], B, res, wsz, a.shift(s, j), H, st, err, attn_fmt));
-            else TRY(tr_attention_bwd(b.qkv, b.attn, G[2], b.table, b.scale, T.dS, T.rowstat, T.dscale_part, T.attn_part, G[4], B, res, wsz, a.shift(s, j), H, st, err));
+            // train_attn.hip.  amp modes: the four products of the attention backward on 16-bit MFMAs too (autocast semantics); exact f32 and x3: exact products
+            const OpFmt attn_fmt = op_is16(amp_fmt(c)) ? amp_fmt(c) : OpFmt::F32;
+            TRY(tr_attention_bwd_mfma(b.qkv, b.attn, G[2], b.table, b.scale, T.dS, T.rowstat, T.dscale_part, G[4], B, res, wsz, a.shift(s, j), H, st, err, attn_fmt));
             {
                 float* dls = c.Gd(k + "attn.logit_scale");
                 float* dw0 = c.Gd(k + "attn.cpb_mlp.0.weight");
@@ -792,7 +792,7 @@ static int encoder_backward(Ctx& c) {
                 if (dls || dw0 || db0 || dw2)
                     TRY(tr_attn_param_grads(T.dS, T.dscale_part, b.table, c.W(k + "attn.logit_scale"), c.W(k + "attn.cpb_mlp.0.weight"), c.W(k + "attn.cpb_mlp.0.bias"),
                                             c.W(k + "attn.cpb_mlp.2.weight"), T.dtable, T.dt, T.S_cpb, dls, dw0, db0, dw2, B * (res / wsz) * (res / wsz), wsz,
-                                            a.pretrained_window[s], H, st, err, dslots));
+                                            a.pretrained_window[s], H, tr_attention_bwd_mfma_slots(wsz), st, err));
             }
             {
                 float* dq = c.Gd(k + "attn.q_bias");

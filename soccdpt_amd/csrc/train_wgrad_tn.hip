@@ -371,8 +371,7 @@ int tr_wgrad_tn(const void* A, long ldA, const void* B, long ldB, size_t K, int 
     TnArgs a;
     a.A = static_cast<const uint16_t*>(A); a.B = static_cast<const uint16_t*>(B); a.ldA = ldA; a.ldB = ldB; a.K = (int)K; a.Nout = Nout; a.C = C; a.taps = taps; a.Ncols = taps * C; a.rp = rp; a.part = part;
     const long tiles = (long)((Nout + 127) / 128) * ((a.Ncols + 127) / 128), nk = (long)K / (x3 ? 32 : 64);
-    static const long target = getenv("SOCCDPT_TN_TILES") ? atol(getenv("SOCCDPT_TN_TILES")) : 512;
-    long S = target / tiles > 0 ? target / tiles : 1;   // one round of two workgroups per CU
+    long S = 512 / tiles > 0 ? 512 / tiles : 1;   // one round of two workgroups per CU
     if (S > nk / 2) S = nk / 2 > 0 ? nk / 2 : 1;
     if (S > 64) S = 64;
     const size_t per_split = (size_t)Nout * a.Ncols + (bias_out ? (size_t)(Nout + 3) / 4 * 4 : 0);   // the bias partials sit behind the weight partials
