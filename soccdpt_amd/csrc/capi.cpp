@@ -10,6 +10,8 @@
 #include "train.h"
 #include "kernels.h"
 #include "occ_eval.h"
+#include "visualise.h"
+#include "../../include/soccdpt_vis.h"
 
 using namespace soccdpt;
 
@@ -843,6 +845,61 @@ int soccdpt_workspace_tensor(void* handle, int B, const char* name, size_t* byte
     Handle* h = static_cast<Handle*>(handle);
     if (!h || !name) return 1;
     return model_workspace_tensor(*h, B, name, byte_offset, elems, kind, H, W, C);
+}
+
+// ---- evaluation pictures (include/soccdpt_vis.h; csrc/visualise.hip) ----
+size_t soccdpt_vis_minmax_scratch_bytes(int B, size_t npix) { return vis_minmax_scratch_bytes(B, npix); }
+
+int soccdpt_vis_minmax(const float* dev_x, int B, size_t npix, float* dev_minmax, void* dev_scratch, size_t scratch_bytes, void* stream) {
+    std::string err;
+    if (launch_vis_minmax(dev_x, B, npix, dev_minmax, dev_scratch, scratch_bytes, (hipStream_t)stream, err)) return fail(nullptr, "soccdpt_" + err);
+    return 0;
+}
+
+int soccdpt_vis_colorize(const float* dev_x, const float* dev_minmax, const uint8_t* dev_lut, int B, int H, int W, uint8_t* dev_dst,
+                         size_t dst_pitch_px, size_t dst_offset_px, size_t dst_frame_px, size_t dst_total_px, void* stream) {
+    std::string err;
+    const VisDst d{dst_pitch_px, dst_offset_px, dst_frame_px, dst_total_px};
+    if (launch_vis_colorize(dev_x, dev_minmax, dev_lut, B, H, W, dev_dst, d, (hipStream_t)stream, err)) return fail(nullptr, "soccdpt_" + err);
+    return 0;
+}
+
+int soccdpt_vis_color_masks(const float* dev_seg, int B, int C, int H, int W, int channels_last, const uint8_t* dev_class_colors, uint8_t* dev_dst,
+                            size_t dst_pitch_px, size_t dst_offset_px, size_t dst_frame_px, size_t dst_total_px, void* stream) {
+    std::string err;
+    const VisDst d{dst_pitch_px, dst_offset_px, dst_frame_px, dst_total_px};
+    if (launch_vis_color_masks(dev_seg, B, C, H, W, channels_last, dev_class_colors, dev_dst, d, (hipStream_t)stream, err))
+        return fail(nullptr, "soccdpt_" + err);
+    return 0;
+}
+
+int soccdpt_vis_resize_taps(int src, int dst, int32_t* host_taps) {
+    std::string err;
+    if (vis_resize_taps(src, dst, host_taps, err)) return fail(nullptr, "soccdpt_" + err);
+    return 0;
+}
+
+int soccdpt_vis_resize(const uint8_t* dev_src, int B, int Hs, int Ws, const int32_t* dev_ytaps, const int32_t* dev_xtaps, int Hd, int Wd,
+                       uint8_t* dev_dst, size_t dst_pitch_px, size_t dst_offset_px, size_t dst_frame_px, size_t dst_total_px, void* stream) {
+    std::string err;
+    const VisDst d{dst_pitch_px, dst_offset_px, dst_frame_px, dst_total_px};
+    if (launch_vis_resize(dev_src, B, Hs, Ws, dev_ytaps, dev_xtaps, Hd, Wd, dev_dst, d, (hipStream_t)stream, err)) return fail(nullptr, "soccdpt_" + err);
+    return 0;
+}
+
+int soccdpt_vis_half_size(int H, int W, int32_t* Hd, int32_t* Wd) {
+    if (!Hd || !Wd || H < 2 || W < 2) return fail(nullptr, "soccdpt_vis_half_size: null argument, or H or W below 2");
+    int h, w;
+    vis_half_size(H, W, &h, &w);
+    *Hd = h;
+    *Wd = w;
+    return 0;
+}
+
+int soccdpt_vis_shrink_half(const uint8_t* dev_src, int B, int H, int W, int swap_rb, uint8_t* dev_dst, void* stream) {
+    std::string err;
+    if (launch_vis_shrink_half(dev_src, B, H, W, swap_rb, dev_dst, (hipStream_t)stream, err)) return fail(nullptr, "soccdpt_" + err);
+    return 0;
 }
 
 }  // extern "C"

@@ -228,6 +228,25 @@ def _prototypes() -> dict:
 PROTOTYPES = _prototypes()
 
 
+def _vis_prototypes() -> dict:
+    """The same table for include/soccdpt_vis.h (the evaluation pictures, csrc/visualise.hip), in that header's order; tests/test_visualise_cpu.py
+    holds it against the header.  A second header and a second table: soccdpt_hip.h and its ABI version do not change for these."""
+    vp, ci, cs, i32 = ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t, ctypes.POINTER(ctypes.c_int32)
+    return {
+        "soccdpt_vis_minmax_scratch_bytes": (cs, [ci, cs]),
+        "soccdpt_vis_minmax": (ci, [vp, ci, cs, vp, vp, cs, vp]),
+        "soccdpt_vis_colorize": (ci, [vp, vp, vp, ci, ci, ci, vp, cs, cs, cs, cs, vp]),
+        "soccdpt_vis_color_masks": (ci, [vp, ci, ci, ci, ci, ci, vp, vp, cs, cs, cs, cs, vp]),
+        "soccdpt_vis_resize_taps": (ci, [ci, ci, i32]),
+        "soccdpt_vis_resize": (ci, [vp, ci, ci, ci, vp, vp, ci, ci, vp, cs, cs, cs, cs, vp]),
+        "soccdpt_vis_half_size": (ci, [ci, ci, i32, i32]),
+        "soccdpt_vis_shrink_half": (ci, [vp, ci, ci, ci, ci, vp, vp]),
+    }
+
+
+VIS_PROTOTYPES = _vis_prototypes()
+
+
 def load_library() -> ctypes.CDLL:
     """Load libsoccdpt_hip.so; fail loudly when it has not been built."""
     global _lib
@@ -238,9 +257,10 @@ def load_library() -> ctypes.CDLL:
             f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "(make -C soccdpt_amd/csrc).  The SOccDPT MI355X path has no CPU fallback.")
     L = ctypes.CDLL(LIB_PATH)
-    for symbol, (restype, argtypes) in PROTOTYPES.items():
-        fn = getattr(L, symbol)
-        fn.restype, fn.argtypes = restype, argtypes
+    for table in (PROTOTYPES, VIS_PROTOTYPES):
+        for symbol, (restype, argtypes) in table.items():
+            fn = getattr(L, symbol)
+            fn.restype, fn.argtypes = restype, argtypes
     if L.soccdpt_abi_version() != ABI_VERSION:
         raise RuntimeError("libsoccdpt_hip.so ABI version mismatch; rebuild the library")
     # the ctypes mirrors of the public structs must have the layout the library was compiled with (include/soccdpt_hip.h)
@@ -263,7 +283,7 @@ def _stream_ptr(device: torch.device) -> int:
 
 
 def _call(symbol: str, *args, device: torch.device, guard: bool = True):
-    """One handle-less entry point (op_*, occupancy evaluation, metrics, criterion, Adam, ground-truth occupancy, input transform) on the current
+    """One handle-less entry point (op_*, occupancy evaluation, evaluation pictures, metrics, criterion, Adam, ground-truth occupancy, input transform) on the current
     stream of `device`, which goes last in every such prototype; guard=False leaves the current device alone, as the kernel-level op_* entries do."""
     L = load_library()
     fn = getattr(L, symbol)

@@ -6,10 +6,10 @@ eval_SOccDPT.py:246-259), then `evaluate_seg` / `evaluate_depth` on the validati
 Differences, all forced by what exists on a GPU box: the datasets (and cv2) are not there, so when `--base_path`
 does not exist the 10-image validation subset is synthetic (seeded frames, ground truth = a smooth perturbation of
 the CPU-free model output, so the numbers are meaningful only as a smoke/regression signal); the PNG visual dumps of
-eval_SOccDPT.py:136-243 are skipped; the FPS loop synchronises the stream before stopping the clock (the reference does
+eval_SOccDPT.py:136-243 are opt-in (`--visuals [DIR]`, default off; see write_visuals); the FPS loop synchronises the stream before stopping the clock (the reference does
 not); metrics run on the GPU (soccdpt_amd.utils.metrics).  `-l/--load` may be omitted for random weights.
 
-    python -m soccdpt_amd.scripts.eval_SOccDPT -v 3 -dt bdd -t dpt_swin2_tiny_256 -d cuda:0 [-l ckpt.pth] [-o]
+    python -m soccdpt_amd.scripts.eval_SOccDPT -v 3 -dt bdd -t dpt_swin2_tiny_256 -d cuda:0 [-l ckpt.pth] [-o] [--visuals [DIR]]
 """
 import argparse
 import os
@@ -44,7 +44,56 @@ def build_parser() -> argparse.ArgumentParser:
     parser.add_argument("--occupancy-per-frame", dest="occupancy_per_frame", action="store_true", help="implies --occupancy, with the model built with "
                         "occupancy_per_frame=True: every frame's own grid (not the union over the batch) is scored against that frame's ground truth, "
                         "and OCC_POINTS is the mean point-list length per frame")
+    parser.add_argument("--visuals", nargs="?", const=os.path.join("media", "visuals"), default=None, metavar="DIR", help="also write the reference's PNG "
+                        "dumps of the validation frames (RGB, GT_Depth, GT_Seg, Pred_Depth, Pred_Seg) and the evaluation panel under "
+                        "DIR/{model_type}_{dataset}_{version}/ (bare flag: media/visuals), coloured on the GPU")
     return parser
+
+
+# class -> colour of the 3-class bdd layout, in the channel order of the frames (datasets/bengaluru_driving_dataset.py:59-64)
+CLASS_2_COLOR_BDD = {0: (0, 0, 0), 1: (0, 0, 142), 2: (220, 20, 60)}
+VISUAL_DIRS = ("RGB", "GT_Depth", "GT_Seg", "Pred_Depth", "Pred_Seg", "Panel")
+
+
+def write_visuals(net, dataset, device, root: str, class_2_color=None) -> str:
+    """The PNG dumps of the reference's evaluation script (eval_SOccDPT.py:138-244) for every frame of `dataset`, plus the evaluation panel:
+    root/{RGB,GT_Depth,GT_Seg,Pred_Depth,Pred_Seg,Panel}/000N.png.  Depth pictures are the per-frame normalised inverse depth through the plasma table,
+    class pictures color_segmentation; everything is coloured on the GPU (utils/visualise.py) and only the finished u8 pictures are copied to the host
+    for the PNG encoder.  GT_Seg is drawn from y_seg: the reference draws y_seg_pred there too (eval_SOccDPT.py:205-217, the same lines as its
+    Pred_Seg block), an evident slip that would make the two folders identical.  A sample without a raw frame (the synthetic subset) gets one made of
+    its network input: de-normalised, B <-> R swapped, resized to the camera size.  Every frame is run through the model once more here, after
+    evaluate_seg and evaluate_depth have already done so: the dump is opt-in and ten frames long, and keeping it apart leaves those two loops as
+    they are."""
+    from ..utils.visualise import color_masks, colorize_disparity, evaluation_panel, resize_bgr, write_png
+    class_2_color = class_2_color or CLASS_2_COLOR_BDD
+    for d in VISUAL_DIRS:
+        os.makedirs(os.path.join(root, d), exist_ok=True)
+    H, W = net.height, net.width
+    for index, batch in enumerate(dataset):
+        x, x_raw, _, y_disp, _, y_seg = batch
+        x = x.to(device=device, dtype=torch.float32)
+        y_disp = y_disp.to(device=device, dtype=torch.float32).reshape(-1, H, W)[0]
+        y_seg = y_seg.to(device=device, dtype=torch.float32).reshape(1, -1, H, W)
+        y_disp_pred, y_seg_pred, _, _ = net(x)
+        y_disp_pred = y_disp_pred.reshape(-1, H, W)[0]
+        y_seg_pred = y_seg_pred.reshape(1, -1, H, W)
+        if x_raw is None:
+            rgb = ((x[0] * 0.5 + 0.5) * 255.0).clamp(0.0, 255.0).to(torch.uint8).permute(1, 2, 0)
+            frame = resize_bgr(rgb.flip(2).contiguous(), (W, H))
+        else:
+            frame = x_raw[0].to(device=device, dtype=torch.uint8)
+        pictures = {
+            "RGB": frame,
+            "GT_Depth": colorize_disparity(y_disp),
+            "GT_Seg": color_masks(y_seg, class_2_color)[0],
+            "Pred_Depth": colorize_disparity(y_disp_pred),
+            "Pred_Seg": color_masks(y_seg_pred, class_2_color)[0],
+        }
+        for d, img in pictures.items():
+            write_png(os.path.join(root, d, f"{index:04d}.png"), img, bgr=True)      # cv2.imwrite takes B, G, R
+        panel = evaluation_panel(frame, y_disp_pred, y_seg_pred[0], class_2_color, disp_gt=y_disp, seg_gt=y_seg[0])
+        write_png(os.path.join(root, "Panel", f"{index:04d}.png"), panel)               # already R, G, B
+    return root
 
 
 def synthetic_val_set(net, device, img: int, n: int = 10):
@@ -139,6 +188,9 @@ def main(args) -> dict:
         result.update(evaluate_occupancy_set(net, dataset, device))
         print(f"IOU_3D: {result['iou_3D']:.4f}")
         print(f"OCC_POINTS: {result['occ_points']:.1f}")
+    if getattr(args, "visuals", None):
+        result["visuals"] = write_visuals(net, dataset, device, os.path.join(args.visuals, f"{args.model_type}_{args.dataset}_{args.version}"))
+        print(f"VISUALS: {result['visuals']}")
     print("=" * 20)
     return result
 

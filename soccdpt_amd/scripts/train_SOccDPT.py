@@ -4,7 +4,7 @@
 (:150-154), dataset split (:199-224), `load_model` (:248-253), `freeze_pretrained_encoder` + `unfreeze_pretrained_encoder_by_percentage`
 (:262-263), Adam (:311-318), ReduceLROnPlateau(min, patience 2) (:320-322), the `PatchWiseInplace` inner loop (:362-393), the criterion
 `loss_depth_w * SSI + loss_seg_w * BCE` (:323-338,380-386), the evaluation round every n_train // (3 * batch_size) steps (:406-430: the seven depth
-metrics and the IoU over the validation split, here on the GPU through csrc/metrics.hip; wandb histograms / images are not produced), one
+metrics and the IoU over the validation split, here on the GPU through csrc/metrics.hip; the image panel and the coloured point list of that round are utils.metrics.evaluate, not wired in here), one
 checkpoint per epoch (:437-449).
 
 What runs on MI355X: all of it.  The train-mode forward and the network backward (csrc/train_step.cpp, csrc/train_hybrid_step.cpp, csrc/train*.hip: exact f32, all
@@ -232,7 +232,7 @@ def train_net(SOccDPT_version=3, device="cuda:0", model_type="dpt_swin2_tiny_256
             division_step = max(n_train // (3 * batch_size), 1)
             if global_step % division_step == 0:
                 # evaluation round (train_SOccDPT.py:406-430 -> utils/__init__.py:598-768): the 7 depth metrics and the IoU over the validation
-                # split, computed on the GPU (csrc/metrics.hip); the wandb histograms / images of the reference are not produced
+                # split, computed on the GPU (csrc/metrics.hip); the reference's image panel and point list: utils.metrics.evaluate (not wired in here)
                 if rank == 0:      # the replicas are identical: one rank builds the validation batches, evaluates and prints
                     val_batches = [val_set[i] for i in range(len(val_set))]      # items carry their batch dimension (datasets' layout)
                     abs_rel, sq_rel, rmse, rmse_log, a1, a2, a3 = evaluate_depth(DepthNet(net), val_batches, device, amp=p["amp"])

@@ -99,16 +99,72 @@ def evaluate_seg(net, dataloader, device, amp=False):
     return float(torch.cat(ious).mean().item())
 
 
+def _histograms(net) -> dict:
+    """The reference's wandb.Histogram of every weight and gradient, only when wandb is installed."""
+    out = {}
+    try:
+        import wandb
+    except ImportError:
+        return out
+    for tag, value in net.named_parameters():
+        if value is not None and value.grad is not None:
+            tag = tag.replace("/", ".")
+            out["Weights/" + tag] = wandb.Histogram(value.data.cpu())
+            out["Gradients/" + tag] = wandb.Histogram(value.grad.data.cpu())
+    return out
+
+
+def evaluate(net, seg_wrapper, disp_wrapper, val_set, device, amp, x_raw, y_disp, y_disp_pred, y_seg, y_seg_pred, points, class_2_color, loss, lr,
+             global_step, epoch, experiment):
+    """The reference's per-epoch evaluate (SOccDPT/utils/__init__.py:598-765), same 18 positional parameters: evaluate_depth and evaluate_seg over
+    val_set (the same two printed lines), the image panel and the coloured point list of sample 0, all computed on the GPU.  Logs the reference's keys
+    through experiment.log and returns the logged dict: `learning rate`, the seven depth metrics, `iou`, `plot` as a uint8 RGB numpy array
+    [H, round(3 W / 2), 3] (the payload of its wandb.Image: frame | predicted | ground-truth depth over frame | predicted | ground-truth classes, at
+    half size), `plot_points` as an [N,6] numpy array (the payload of its wandb.Object3D: every tenth point of points[0] beside every tenth pixel of
+    the ground-truth class picture, rows whose first colour channel is 0 dropped), `loss`, `step`, `epoch`; the wandb histograms only when wandb is
+    installed."""
+    from .visualise import color_masks, evaluation_panel
+    dev = torch.device(device)
+    abs_rel, sq_rel, rmse, rmse_log, a1, a2, a3 = evaluate_depth(disp_wrapper, val_set, device, amp=amp)
+    print("abs_rel, sq_rel, rmse, rmse_log, a1, a2, a3", abs_rel, sq_rel, rmse, rmse_log, a1, a2, a3)
+    iou = evaluate_seg(seg_wrapper, val_set, device, amp=amp)
+    print("iou", iou)
+    frame_bgr = x_raw[0].detach().squeeze().to(device=dev, dtype=torch.uint8)
+    disp_pred = (y_disp_pred if y_disp_pred.dim() == 2 else y_disp_pred[0]).to(dev)
+    seg_pred = (y_seg_pred if y_seg_pred.dim() == 3 else y_seg_pred[0]).to(dev)
+    disp_gt, seg_gt = y_disp[0].to(dev), y_seg[0].to(dev)
+    vis_img = evaluation_panel(frame_bgr, disp_pred, seg_pred, class_2_color, disp_gt=disp_gt, seg_gt=seg_gt)
+    gt_colors = color_masks(seg_gt.unsqueeze(0), class_2_color)[0].reshape(-1, 3)[::10]
+    pts = torch.as_tensor(points)[0].detach().to(dev).reshape(-1, 3)[::10]
+    keep = gt_colors[:, 0] > 0
+    plot_points_colors = torch.cat([pts[keep], gt_colors[keep].to(pts.dtype)], dim=1).cpu().numpy()
+    print("plot_points_colors", plot_points_colors.shape)
+    print("loss: {}".format(loss))
+    log = {
+        "learning rate": lr,
+        "abs_rel": abs_rel, "sq_rel": sq_rel, "rmse": rmse, "rmse_log": rmse_log, "a1": a1, "a2": a2, "a3": a3,
+        "iou": iou,
+        "plot": vis_img.cpu().numpy(),
+        "plot_points": plot_points_colors,
+        "loss": loss.item() if hasattr(loss, "item") else float(loss),
+        "step": global_step,
+        "epoch": epoch,
+    }
+    log.update(_histograms(net))
+    experiment.log(log)
+    return log
+
+
 def evaluate_occupancy(net, val_set, device, amp, x_raw, y_occupancy_grid, y_occupancy_grid_pred, y_disp_pred, y_seg_pred, class_2_color, loss, lr,
                        global_step, epoch, experiment):
     """The reference's evaluate_occupancy (SOccDPT/utils/__init__.py:375-529), same 15 positional parameters, with the grids left on
     the GPU: both point lists of sample 0 come from csrc/occ_eval.hip (occupancy_grid_to_points), and `iou_3D` -- 0.0 with a "# TODO: Implement"
     there -- is the mean over the batch of occupancy_iou(pred, gt)["iou_3D"].  Logs the reference's keys through experiment.log and returns the
     logged dict: `learning rate`, `iou_3D`, `plot_points_gt` / `plot_points_pred` as [N,6] float64 numpy arrays (x, y, z, r, g, b: the payload of
-    the reference's wandb.Object3D), `loss`, `step`, `epoch`; the cv2 image panel (`plot`) and the wandb weight / gradient histograms are added only
-    when those packages are installed."""
-    import numpy as np
+    the reference's wandb.Object3D), `plot` as a uint8 RGB numpy array [H, W, 3] (the payload of its wandb.Image: frame | depth over frame | classes
+    at half size, utils.visualise.evaluation_panel), `loss`, `step`, `epoch`; the wandb weight / gradient histograms are added only when wandb is installed."""
     from .occupancy import occupancy_grid_to_points, occupancy_iou, semantic_pc_to_colors_and_pc
+    from .visualise import evaluation_panel
     grid_size = tuple(getattr(net, "grid_size", (256, 256, 32)))
     scale = tuple(getattr(net, "scale", (2.0, 2.0, 0.666)))
 
@@ -133,31 +189,11 @@ def evaluate_occupancy(net, val_set, device, amp, x_raw, y_occupancy_grid, y_occ
         "step": global_step,
         "epoch": epoch,
     }
-    try:
-        import cv2
-        frame_rgb = x_raw[0].detach().squeeze().cpu().numpy()
-        disp = (y_disp_pred[0] if y_disp_pred.dim() > 2 else y_disp_pred).detach().squeeze().cpu().numpy()
-        disp = (disp - np.min(disp)) / (np.max(disp) - np.min(disp))
-        disp = cv2.resize(cv2.applyColorMap((disp * 255).astype(np.uint8), cv2.COLORMAP_PLASMA), frame_rgb.shape[:2][::-1])
-        masks = (y_seg_pred[0] if y_seg_pred.dim() > 3 else y_seg_pred).permute(1, 2, 0).detach().cpu().numpy() > 0.5
-        if masks.shape[:2] != frame_rgb.shape[:2]:
-            masks = cv2.resize(masks.astype(np.uint8), frame_rgb.shape[:2][::-1], interpolation=cv2.INTER_NEAREST).astype(bool)
-        seg_img = np.zeros_like(frame_rgb)
-        for c in range(masks.shape[2]):
-            seg_img[masks[:, :, c]] = class_2_color[c]
-        vis = np.concatenate([np.concatenate([frame_rgb, disp], 1), np.concatenate([frame_rgb, seg_img], 1)], 0)
-        log["plot"] = cv2.resize(cv2.cvtColor(vis, cv2.COLOR_BGR2RGB), (0, 0), fx=0.5, fy=0.5)
-    except ImportError:
-        pass
-    try:
-        import wandb
-        for tag, value in net.named_parameters():
-            if value is not None and value.grad is not None:
-                tag = tag.replace("/", ".")
-                log["Weights/" + tag] = wandb.Histogram(value.data.cpu())
-                log["Gradients/" + tag] = wandb.Histogram(value.grad.data.cpu())
-    except ImportError:
-        pass
+    frame_bgr = x_raw[0].detach().squeeze().to(device=device, dtype=torch.uint8)
+    disp = y_disp_pred[0] if y_disp_pred.dim() > 2 else y_disp_pred
+    seg = y_seg_pred[0] if y_seg_pred.dim() > 3 else y_seg_pred
+    log["plot"] = evaluation_panel(frame_bgr, disp.to(device), seg.to(device), class_2_color).cpu().numpy()
+    log.update(_histograms(net))
     print("loss: {}".format(loss))
     experiment.log(log)
     return log
