@@ -69,6 +69,8 @@ h = hashlib.sha1()
 for k in (key, "depth_net.pretrained.model.layers.0.blocks.0.attn.qkv.weight", "seg_head.4.bias", "seg_head.1.running_mean"):
     t = dict(net.state_dict())[k]
     h.update(t.detach().cpu().contiguous().numpy().tobytes())
-print("RESULT", rank, f"{err:.3e}", h.hexdigest(), net.grad_exchange.calls, flush=True)
+# one write per line: the ranks share the launcher's pipe, and print() with several arguments writes them piecewise (interleaved lines were seen)
+sys.stdout.write(f"RESULT {rank} {err:.3e} {h.hexdigest()} {net.grad_exchange.calls}\n")
+sys.stdout.flush()
 dist.barrier()
 dist.destroy_process_group()

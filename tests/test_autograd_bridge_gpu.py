@@ -7,10 +7,10 @@ import tempfile
 
 import pytest
 import torch
-import torch.nn.functional as F
 
 from oracle import loss_ref
 from oracle import soccdpt_ref as R
+from tests.projection_geometries import project_backward_reference
 
 pytestmark = pytest.mark.gpu
 
@@ -53,26 +53,14 @@ def test_project_backward_matches_autograd(gpu_device, clamped):
     d_inv, d_seg = eng.project_backward(inv_up, w1.to(gpu_device), w2.to(gpu_device), None if w3 is None else w3.to(gpu_device), h, w)
     d_inv1, d_seg1 = eng.project_backward(inv_up, w1.to(gpu_device), None, None, h, w)          # absent gradients are zeros
     torch.cuda.synchronize()
-    # float64 reference
-    a = inv.double().requires_grad_(True); s = seg.double().requires_grad_(True)
-    up = F.interpolate(a.unsqueeze(1), size=(Hc, Wc), mode="bicubic", align_corners=False)[:, 0]
-    up = torch.where(up < 1e-8, torch.full_like(up, 1e-8), up)
-    su = F.interpolate(s, size=(Hc, Wc), mode="nearest")
-    loss = (up * w1.double()).sum() + (su * w2.double()).sum()
-    if w3 is not None:
-        d = 1.0 / up
-        vv = torch.arange(Wc, dtype=torch.float64)[None, None, :]; uu = torch.arange(Hc, dtype=torch.float64)[None, :, None]
-        P = torch.stack([(vv - float(m.cx)) * d / float(m.fx), (uu - float(m.cy)) * d / float(m.fy), d.expand(B, Hc, Wc)], dim=-1)
-        scale = torch.ones((Hc * Wc, 1), dtype=torch.float64); scale[:3, 0] = torch.tensor(m.pc_scale, dtype=torch.float64)
-        loss = loss + (P * scale.reshape(1, Hc, Wc, 1) * w3.double()).sum()
-    loss.backward()
-    e_inv, e_seg = _rel(d_inv.cpu(), a.grad), _rel(d_seg.cpu(), s.grad)
+    # float64 reference (shared with tests/test_projection_geometry_gpu.py)
+    a_grad, s_grad, up2 = project_backward_reference(inv, seg, Hc, Wc, m.fx, m.fy, m.cx, m.cy, m.pc_scale, w1, w2, w3)
+    e_inv, e_seg = _rel(d_inv.cpu(), a_grad), _rel(d_seg.cpu(), s_grad)
     print(f"project_backward (clamped={clamped}): rel L2 vs float64 autograd d_inv {e_inv:.2e}, d_seg {e_seg:.2e}")
     # clamped=True: pixels whose raw bicubic value is within f32 rounding of the 1e-8 threshold may fall on the other side in float64
     assert e_inv < (2e-3 if clamped else 2e-5), e_inv
     assert e_seg < 2e-6
     if clamped:   # the clamp really cut gradient paths: without the mask the result differs grossly
-        up2 = F.interpolate(a.detach().unsqueeze(1), size=(Hc, Wc), mode="bicubic", align_corners=False)[:, 0]
         assert int((up2 < 1e-8).sum()) > 1000
     assert float(d_seg1.abs().max()) == 0.0 and float(d_inv1.abs().max()) > 0.0
 
