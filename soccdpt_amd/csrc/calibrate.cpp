@@ -5,12 +5,16 @@
 // the outputs within the tolerance on THOSE weights.  Round 4 shipped maps fitted by an out-of-tree script to one synthetic draw; this is the same
 // procedure (one-group-out variances, greedy selection by variance removed per microsecond, measured prune) behind the C ABI, with the library's
 // own exact-f32 arithmetic on the same weights as the reference.  Nothing here touches the CPU oracle.
+//
+// This file drives the GPU (the f32 twin, one prepare + forward per candidate map, error read-back, restore on failure, fingerprint); which maps to
+// try and which to keep is decided in calib_select.cpp, which knows nothing of HIP and is tested on the CPU (tests/test_calib_select_cpu.py).
 #include "calibrate.h"
 
 #include <cmath>
-#include <cstdlib>
 #include <cstring>
+#include <functional>
 
+#include "calib_select.h"
 #include "prec_cost_table.h"
 
 namespace soccdpt {
@@ -142,88 +146,42 @@ int calib_weights_are_the_shipped_draw(Handle& h, unsigned long long* tmp, hipSt
 
 namespace {
 
-// one measured forward: relative L2 of the seven quantities (+ the optional per-pixel constraint as an eighth, scaled so that the same budget applies),
-// over the calibration frames (e) and, separately, over the held-out frames (h)
-constexpr int NQ = kCalibQuantities + 1;
-struct Err {
-    double e[NQ] = {0, 0, 0, 0, 0, 0, 0, 0};
-    double h[NQ] = {0, 0, 0, 0, 0, 0, 0, 0};
-    double p999 = 0, pmax = 0, h_p999 = 0, h_pmax = 0;   // per-pixel relative error of the inverse depth (only when measured)
-    double worst() const { double w = 0; for (double v : e) w = std::max(w, v); return w; }
-    double worst_l2() const { double w = 0; for (int q = 0; q < kCalibQuantities; ++q) w = std::max(w, e[q]); return w; }
-    double worst_holdout() const { double w = 0; for (double v : h) w = std::max(w, v); return w; }
-    double worst_holdout_l2() const { double w = 0; for (int q = 0; q < kCalibQuantities; ++q) w = std::max(w, h[q]); return w; }
-};
+using calib::Err;
+using calib::Map;
+static_assert(calib::kL2 == kCalibQuantities, "calib_select.h and calibrate.h count the same quantities");
 
-}  // namespace
+// a state of the selection (0 fp16, 1 x2w, 2 x3) <-> a Handle::prec_map code (absent = fp16, 4 = x2w, 3 = x3)
+int state_to_code(int state) { return state == 2 ? 3 : 4; }   // state != 0
+int code_to_state(int code) { return code == 3 ? 2 : (code == 4 ? 1 : 0); }
 
-int calib_run(Handle& h, const float* x, int B, const soccdpt_calib_options& opt, void* prepared, size_t prepared_bytes, void* ws, size_t ws_bytes, void* scratch,
-              size_t scratch_bytes, soccdpt_calib_report* rep, hipStream_t st, std::string& err) {
-    static const bool flags_no_x2w = getenv("SOCCDPT_CALIB_NO_X2W") != nullptr;   // measurement switch: the two-format (fp16 / x3) selection of round 4
-    const float budget = opt.budget;
-    const int V = opt.holdout, Bc = B - V;                                     // frames [0, Bc) select the map, frames [Bc, B) only verify it
-    const double headroom = opt.headroom > 0.f ? (double)opt.headroom : 0.85;   // internal target on the calibration frames = headroom x budget
-    const double pp_budget = opt.per_pixel_p999 > 0.f ? (double)opt.per_pixel_p999 : 0.0;
-    if (h.cfg.precision != SOCCDPT_PREC_MIXED) { err = "soccdpt_prec_calibrate: the handle was not created with SOCCDPT_PREC_MIXED"; return 1; }
-    if (!x || B <= 0 || !(budget > 0.f) || !prepared || !ws || !scratch) { err = "soccdpt_prec_calibrate: bad argument"; return 1; }
-    if (V < 0 || Bc < 1 || !(headroom > 0.0 && headroom <= 1.0)) { err = "soccdpt_prec_calibrate: holdout must leave at least one calibration frame, headroom must be in (0, 1]"; return 1; }
-    if (h.n_streams != 1 || h.use_graph) { err = "soccdpt_prec_calibrate: calibrate on one stream without graph replay (soccdpt_set_streams(1), soccdpt_set_graph(0))"; return 1; }
-    for (const auto& w : h.weights)
-        if (!w.ptr) { err = "soccdpt_prec_calibrate: weight not bound: " + w.key; return 1; }
-    if (prepared_bytes < h.prepared_bytes || ws_bytes < model_workspace_bytes(h, B)) { err = "soccdpt_prec_calibrate: prepared arena or workspace too small"; return 1; }
-    Handle* twin = make_twin(h, err);
-    if (!twin) return 1;
-    QuantGeo g;
-    Scratch s;
-    if (quant_geometry(h, B, g, err) || lay_scratch(h, twin, B, g, static_cast<char*>(scratch), s)) { delete twin; return 1; }
-    if (s.total > scratch_bytes) { delete twin; err = "soccdpt_prec_calibrate: scratch too small (soccdpt_prec_calibrate_scratch_bytes)"; return 1; }
+// The measure callback of calib::select: one forward of `h` under a map and its errors against the reference held in `s.ref` -- relative L2 of the seven
+// quantities (+ the optional per-pixel constraint as an eighth, scaled so that the same budget applies) over the calibration frames [0, Bc) and,
+// separately, over the held-out frames [Bc, B).
+struct Measurer {
+    // what it works on: one member per type, so the initialiser list cannot swap two of them unnoticed
+    Handle& h;
+    const std::vector<std::string>& groups;
+    const Scratch& s;
+    const QuantGeo& g;
+    std::string& err;
+    // the rest is set by name (calib_run)
+    const float* x = nullptr;
+    int B = 0, Bc = 0, V = 0;
+    float budget = 0.f;
+    double pp_budget = 0.0;
+    void* prepared = nullptr; size_t prepared_bytes = 0;
+    void* ws = nullptr; size_t ws_bytes = 0;
+    hipStream_t st = nullptr;
+    std::vector<float> ref_inv, got_inv, pix_err;   // the inverse depth on the host: the per-pixel percentiles are taken there (exact selection, 0.5 - 1.2 M values)
     int forwards = 0;
+    bool touched = false;   // has the handle's map been replaced?
 
-    // ---- 1. the reference: exact-f32 arithmetic on the same weights and frames ----
-    int rc = model_prepare(*twin, s.twin_prepared, s.twin_prepared_bytes, st, err);
-    if (!rc) rc = model_network(*twin, x, B, s.inv, s.seg, s.twin_ws, s.twin_ws_bytes, st, err);
-    for (int q = 0; q < kCalibQuantities && !rc; ++q) rc = extract(*twin, B, s.twin_ws, s.inv, g, q, s.ref + g.off[q], st, err);
-    const size_t npix = (size_t)B * h.img * h.img, pix_frame = (size_t)h.img * h.img;
-    std::vector<float> ref_inv, got_inv, pix_err;
-    if (!rc) {   // the host keeps the reference inverse depth: the per-pixel percentiles are taken on the host (exact selection, 0.5 - 1.2 M values)
-        ref_inv.resize(npix); got_inv.resize(npix); pix_err.resize(npix);
-        if (hipMemcpyAsync(ref_inv.data(), s.ref + g.off[5], npix * 4, hipMemcpyDeviceToHost, st) != hipSuccess) { err = "soccdpt_prec_calibrate: reference read-back failed"; rc = 1; }
-    }
-    if (!rc && hipStreamSynchronize(st) != hipSuccess) { err = "soccdpt_prec_calibrate: the f32 reference run failed"; rc = 1; }
-    delete twin;
-    if (rc) return 1;
-    ++forwards;
-
-    const std::vector<std::string> groups = model_prec_groups(h);
-    const int G = (int)groups.size();
-    // a map = one state per group: 0 fp16, 1 x2w (fp16 activations, x3 weight pairs), 2 x3
-    typedef std::vector<int> Map;
-
-    // the handle as it was handed over: every failure below puts it back (ADVICE r5: a failed launch used to leave a half-built map, unprepared)
-    const std::unordered_map<std::string, int> map_on_entry = h.prec_map;
-    const int source_on_entry = h.prec_source;
-    bool touched = false;
-
-    auto per_pixel = [&](size_t f0, size_t f1, double& p999, double& pmax) {   // frames [f0, f1): |d - ref| / max(|ref|, 1e-6), its 99.9th percentile and maximum
-        p999 = pmax = 0;
-        if (f1 <= f0) return;
-        const size_t n = (f1 - f0) * pix_frame;
-        float* e = pix_err.data();
-        for (size_t i = 0; i < n; ++i) {
-            const float r = ref_inv[f0 * pix_frame + i], d = got_inv[f0 * pix_frame + i];
-            const float v = std::fabs(d - r) / std::max(std::fabs(r), 1e-6f);
-            e[i] = v == v ? v : 3.0e38f;   // a NaN counts as the worst error
-        }
-        const size_t k = std::min(n - 1, (size_t)std::max<long long>(0, (long long)(0.999 * (double)n) - 1));   // torch.kthvalue(int(0.999 n)) of bench.py / tests
-        std::nth_element(e, e + k, e + n);
-        p999 = e[k];
-        pmax = *std::max_element(e + k, e + n);
-    };
-    auto measure = [&](const Map& m, Err& out, bool want_pixels) -> int {   // the forward under the map, its relative L2 errors against the reference
+    int operator()(const Map& m, Err& out, bool want_pixels) {
+        const size_t npix = (size_t)B * h.img * h.img, pix_frame = (size_t)h.img * h.img;
         touched = true;
         h.prec_map.clear();
-        for (int i = 0; i < G; ++i)
-            if (m[i]) h.prec_map[groups[i]] = m[i] == 2 ? 3 : 4;
+        for (size_t i = 0; i < groups.size(); ++i)
+            if (m[i]) h.prec_map[groups[i]] = state_to_code(m[i]);
         h.ws_key = Handle::WsKey();
         h.is_prepared = false;
         if (model_prepare(h, prepared, prepared_bytes, st, err)) return 1;
@@ -249,167 +207,107 @@ int calib_run(Handle& h, const float* x, int B, const soccdpt_calib_options& opt
             if (V > 0) { const double* hh = host + 2 * (kCalibQuantities + q); out.h[q] = hh[1] > 0 ? std::sqrt(hh[0] / hh[1]) : 0.0; }
         }
         if (want_pixels || pp_budget > 0) {
-            per_pixel(0, (size_t)Bc, out.p999, out.pmax);
-            per_pixel((size_t)Bc, (size_t)B, out.h_p999, out.h_pmax);
+            const size_t split = (size_t)Bc * pix_frame;
+            calib::per_pixel(ref_inv.data(), got_inv.data(), split, pix_err.data(), out.p999, out.pmax);
+            calib::per_pixel(ref_inv.data() + split, got_inv.data() + split, npix - split, pix_err.data(), out.h_p999, out.h_pmax);
             if (pp_budget > 0) { out.e[kCalibQuantities] = out.p999 * budget / pp_budget; out.h[kCalibQuantities] = out.h_p999 * budget / pp_budget; }
         }
         ++forwards;
         return 0;
-    };
-    // device-time cost of a group's state over fp16 (compiled-in table, prec_cost_table.h)
-    auto cost = [&](int i, int state) -> double {
-        if (state == 0) return 0.0;
-        return state == 2 ? (double)prec_cost_us(h.cfg.backbone, groups[i].c_str()) : (double)prec_cost_x2w_us(h.cfg.backbone, groups[i].c_str());
-    };
-    auto cost_of = [&](const Map& m) { double c = 0; for (int i = 0; i < G; ++i) c += cost(i, m[i]); return c; };
-    auto count_state = [&](const Map& m, int st_) { int n = 0; for (int v : m) n += v == st_; return n; };
-    const double hb = headroom * (double)budget;          // what the calibration frames are held to
-    auto accept = [&](const Err& e) { return e.worst() <= hb && (V == 0 || e.worst_holdout() <= (double)budget); };
-    auto fill_report = [&](const Map& chosen, const Err& e_final, const Map& shipped, const Err& e_ship, const Err& e_f16, const Err& e_x3) {
-        if (!rep) return;
-        memset(rep, 0, sizeof(*rep));
-        rep->n_groups = G; rep->n_x3 = count_state(chosen, 2); rep->n_x2w = count_state(chosen, 1); rep->n_x3_shipped = count_state(shipped, 2); rep->n_x2w_shipped = count_state(shipped, 1);
-        rep->forwards = forwards;
-        rep->met_budget = e_final.worst() <= budget ? 1 : 0; rep->shipped_met_budget = e_ship.worst() <= budget ? 1 : 0; rep->budget = budget;
-        rep->worst_calibrated = (float)e_final.worst_l2(); rep->worst_shipped = (float)e_ship.worst_l2(); rep->worst_all_fp16 = (float)e_f16.worst_l2(); rep->worst_all_x3 = (float)e_x3.worst_l2();
-        for (int q = 0; q < kCalibQuantities; ++q) { rep->err_calibrated[q] = (float)e_final.e[q]; rep->err_shipped[q] = (float)e_ship.e[q]; rep->err_holdout[q] = (float)e_final.h[q]; }
-        rep->cost_us_calibrated = (float)cost_of(chosen); rep->cost_us_shipped = (float)cost_of(shipped);
-        rep->calib_frames = Bc; rep->holdout_frames = V; rep->headroom = (float)headroom;
-        rep->met_headroom = e_final.worst() <= hb ? 1 : 0;
-        rep->met_holdout = V > 0 ? (e_final.worst_holdout() <= (double)budget ? 1 : 0) : -1;
-        rep->worst_holdout = (float)e_final.worst_holdout_l2(); rep->worst_holdout_shipped = (float)e_ship.worst_holdout_l2();
-        rep->per_pixel_budget = (float)pp_budget;
-        rep->inv_p999_calibrated = (float)e_final.p999; rep->inv_max_calibrated = (float)e_final.pmax;
-        rep->inv_p999_holdout = (float)e_final.h_p999; rep->inv_max_holdout = (float)e_final.h_pmax;
-        rep->inv_p999_all_fp16 = (float)e_f16.p999; rep->inv_p999_all_x3 = (float)e_x3.p999;
-    };
+    }
+};
 
-    auto body = [&]() -> int {
-    // ---- 2. the corner cases and the shipped map on these weights ----
-    const Map all3(G, 2), all16(G, 0);
-    Err e_x3, e_f16, e_ship;
-    if (measure(all3, e_x3, true) || measure(all16, e_f16, true)) return 1;
+int count_state(const Map& m, int state) { int n = 0; for (int v : m) n += v == state; return n; }
+
+void fill_report(soccdpt_calib_report* rep, const calib::Problem& p, const calib::Selection& sel, int forwards, int Bc, float budget, double pp_budget) {
+    if (!rep) return;
+    const Map& chosen = sel.chosen;
+    const Map& shipped = p.shipped;
+    const Err &e_final = sel.e_final, &e_ship = sel.e_ship, &e_f16 = sel.e_f16, &e_x3 = sel.e_x3;
+    const int V = p.holdout;
+    memset(rep, 0, sizeof(*rep));
+    rep->n_groups = p.G; rep->n_x3 = count_state(chosen, 2); rep->n_x2w = count_state(chosen, 1); rep->n_x3_shipped = count_state(shipped, 2); rep->n_x2w_shipped = count_state(shipped, 1);
+    rep->forwards = forwards;
+    rep->met_budget = e_final.worst() <= budget ? 1 : 0; rep->shipped_met_budget = e_ship.worst() <= budget ? 1 : 0; rep->budget = budget;
+    rep->worst_calibrated = (float)e_final.worst_l2(); rep->worst_shipped = (float)e_ship.worst_l2(); rep->worst_all_fp16 = (float)e_f16.worst_l2(); rep->worst_all_x3 = (float)e_x3.worst_l2();
+    for (int q = 0; q < kCalibQuantities; ++q) { rep->err_calibrated[q] = (float)e_final.e[q]; rep->err_shipped[q] = (float)e_ship.e[q]; rep->err_holdout[q] = (float)e_final.h[q]; }
+    rep->cost_us_calibrated = (float)p.cost_of(chosen); rep->cost_us_shipped = (float)p.cost_of(shipped);
+    rep->calib_frames = Bc; rep->holdout_frames = V; rep->headroom = (float)p.headroom;
+    rep->met_headroom = e_final.worst() <= p.headroom * p.budget ? 1 : 0;
+    rep->met_holdout = V > 0 ? (e_final.worst_holdout() <= (double)budget ? 1 : 0) : -1;
+    rep->worst_holdout = (float)e_final.worst_holdout_l2(); rep->worst_holdout_shipped = (float)e_ship.worst_holdout_l2();
+    rep->per_pixel_budget = (float)pp_budget;
+    rep->inv_p999_calibrated = (float)e_final.p999; rep->inv_max_calibrated = (float)e_final.pmax;
+    rep->inv_p999_holdout = (float)e_final.h_p999; rep->inv_max_holdout = (float)e_final.h_pmax;
+    rep->inv_p999_all_fp16 = (float)e_f16.p999; rep->inv_p999_all_x3 = (float)e_x3.p999;
+}
+
+}  // namespace
+
+int calib_run(Handle& h, const float* x, int B, const soccdpt_calib_options& opt, void* prepared, size_t prepared_bytes, void* ws, size_t ws_bytes, void* scratch,
+              size_t scratch_bytes, soccdpt_calib_report* rep, hipStream_t st, std::string& err) {
+    const float budget = opt.budget;
+    const int V = opt.holdout, Bc = B - V;                                     // frames [0, Bc) select the map, frames [Bc, B) only verify it
+    const double headroom = opt.headroom > 0.f ? (double)opt.headroom : 0.85;   // internal target on the calibration frames = headroom x budget
+    const double pp_budget = opt.per_pixel_p999 > 0.f ? (double)opt.per_pixel_p999 : 0.0;
+    if (h.cfg.precision != SOCCDPT_PREC_MIXED) { err = "soccdpt_prec_calibrate: the handle was not created with SOCCDPT_PREC_MIXED"; return 1; }
+    if (!x || B <= 0 || !(budget > 0.f) || !prepared || !ws || !scratch) { err = "soccdpt_prec_calibrate: bad argument"; return 1; }
+    if (V < 0 || Bc < 1 || !(headroom > 0.0 && headroom <= 1.0)) { err = "soccdpt_prec_calibrate: holdout must leave at least one calibration frame, headroom must be in (0, 1]"; return 1; }
+    if (h.n_streams != 1 || h.use_graph) { err = "soccdpt_prec_calibrate: calibrate on one stream without graph replay (soccdpt_set_streams(1), soccdpt_set_graph(0))"; return 1; }
+    for (const auto& w : h.weights)
+        if (!w.ptr) { err = "soccdpt_prec_calibrate: weight not bound: " + w.key; return 1; }
+    if (prepared_bytes < h.prepared_bytes || ws_bytes < model_workspace_bytes(h, B)) { err = "soccdpt_prec_calibrate: prepared arena or workspace too small"; return 1; }
+    Handle* twin = make_twin(h, err);
+    if (!twin) return 1;
+    QuantGeo g;
+    Scratch s;
+    if (quant_geometry(h, B, g, err) || lay_scratch(h, twin, B, g, static_cast<char*>(scratch), s)) { delete twin; return 1; }
+    if (s.total > scratch_bytes) { delete twin; err = "soccdpt_prec_calibrate: scratch too small (soccdpt_prec_calibrate_scratch_bytes)"; return 1; }
+
+    const std::vector<std::string> groups = model_prec_groups(h);
+    Measurer measure{h, groups, s, g, err};
+    measure.x = x; measure.B = B; measure.Bc = Bc; measure.V = V;
+    measure.budget = budget; measure.pp_budget = pp_budget;
+    measure.prepared = prepared; measure.prepared_bytes = prepared_bytes;
+    measure.ws = ws; measure.ws_bytes = ws_bytes;
+    measure.st = st;
+
+    // ---- the reference: exact-f32 arithmetic on the same weights and frames ----
+    int rc = model_prepare(*twin, s.twin_prepared, s.twin_prepared_bytes, st, err);
+    if (!rc) rc = model_network(*twin, x, B, s.inv, s.seg, s.twin_ws, s.twin_ws_bytes, st, err);
+    for (int q = 0; q < kCalibQuantities && !rc; ++q) rc = extract(*twin, B, s.twin_ws, s.inv, g, q, s.ref + g.off[q], st, err);
+    const size_t npix = (size_t)B * h.img * h.img;
+    if (!rc) {
+        measure.ref_inv.resize(npix); measure.got_inv.resize(npix); measure.pix_err.resize(npix);
+        if (hipMemcpyAsync(measure.ref_inv.data(), s.ref + g.off[5], npix * 4, hipMemcpyDeviceToHost, st) != hipSuccess) { err = "soccdpt_prec_calibrate: reference read-back failed"; rc = 1; }
+    }
+    if (!rc && hipStreamSynchronize(st) != hipSuccess) { err = "soccdpt_prec_calibrate: the f32 reference run failed"; rc = 1; }
+    delete twin;
+    if (rc) return 1;
+    ++measure.forwards;
+
+    // the handle as it was handed over: every failure below puts it back (ADVICE r5: a failed launch used to leave a half-built map, unprepared)
+    const std::unordered_map<std::string, int> map_on_entry = h.prec_map;
+    const int source_on_entry = h.prec_source;
+
+    // ---- the selection problem: what each group costs over fp16 (compiled-in table, prec_cost_table.h), which may take x2w, and the shipped map ----
+    calib::Problem p;
+    p.G = (int)groups.size();
+    p.budget = (double)budget; p.headroom = headroom; p.holdout = V;
+    p.shipped.assign(p.G, 0);
     model_prec_default(h);
-    Map shipped(G, 0);
-    for (int i = 0; i < G; ++i) {
+    for (int i = 0; i < p.G; ++i) {
+        p.cost_x3.push_back((double)prec_cost_us(h.cfg.backbone, groups[i].c_str()));
+        p.cost_x2w.push_back((double)prec_cost_x2w_us(h.cfg.backbone, groups[i].c_str()));
+        p.x2w_ok.push_back(model_prec_x2w_ok(groups[i]) ? 1 : 0);
         auto it = h.prec_map.find(groups[i]);
-        if (it != h.prec_map.end()) shipped[i] = it->second == 3 ? 2 : (it->second == 4 ? 1 : 0);
+        if (it != h.prec_map.end()) p.shipped[i] = code_to_state(it->second);
     }
-    if (measure(shipped, e_ship, false)) return 1;
-    if (e_x3.worst() > hb) {   // even every group in x3 misses the target (the fp16 attention core, or a budget under the f32 noise floor): nothing to select
-        Err tmp;
-        if (measure(all3, tmp, true)) return 1;
-        h.prec_source = 1;
-        fill_report(all3, tmp, shipped, e_ship, e_f16, e_x3);
-        return 0;
-    }
+    h.prec_map = map_on_entry;
 
-    // ---- 3. one-group-out variances: T = what the group adds in fp16, A = what it still adds as x2w (its activation rounding) ----
-    const bool use_x2w = !(flags_no_x2w);
-    std::vector<Err> T(G), A(G);
-    for (int i = 0; i < G; ++i) {
-        Map m = all3;
-        Err e;
-        m[i] = 0;
-        if (measure(m, e, false)) return 1;
-        for (int q = 0; q < NQ; ++q) T[i].e[q] = std::max(e.e[q] * e.e[q] - e_x3.e[q] * e_x3.e[q], 0.0);
-        A[i] = T[i];
-        if (use_x2w && model_prec_x2w_ok(groups[i])) {
-            m[i] = 1;
-            if (measure(m, e, false)) return 1;
-            for (int q = 0; q < NQ; ++q) A[i].e[q] = std::min(T[i].e[q], std::max(e.e[q] * e.e[q] - e_x3.e[q] * e_x3.e[q], 0.0));
-        }
-    }
-    auto rem = [&](int i, int state, int q) { return state == 2 ? 0.0 : (state == 1 ? A[i].e[q] : T[i].e[q]); };
-    auto predict = [&](const Map& m, Err& out) {
-        for (int q = 0; q < NQ; ++q) {
-            double v = e_x3.e[q] * e_x3.e[q];
-            for (int i = 0; i < G; ++i) v += rem(i, m[i], q);
-            out.e[q] = std::sqrt(v);
-        }
-    };
-    auto solve = [&](double target) {
-        Map m(G, 0);
-        for (;;) {   // greedy over single-group upgrades (fp16 -> x2w, fp16 -> x3, x2w -> x3) by violated variance removed per microsecond
-            Err e;
-            predict(m, e);
-            bool viol = false;
-            for (double v : e.e) viol |= v > target;
-            if (!viol) break;
-            int best = -1, best_to = 0;
-            double best_rate = 0;
-            for (int i = 0; i < G; ++i)
-                for (int to = m[i] + 1; to <= 2; ++to) {
-                    if (to == 1 && !(use_x2w && model_prec_x2w_ok(groups[i]))) continue;
-                    double gain = 0;
-                    for (int q = 0; q < NQ; ++q)
-                        if (e.e[q] > target) gain += std::min(rem(i, m[i], q) - rem(i, to, q), std::max(0.0, e.e[q] * e.e[q] - target * target));
-                    const double dc = std::max(cost(i, to) - cost(i, m[i]), 0.25);
-                    if (gain > 0 && (best < 0 || gain / dc > best_rate)) { best = i; best_to = to; best_rate = gain / dc; }
-                }
-            if (best < 0) break;
-            m[best] = best_to;
-        }
-        // predicted prune: single-level demotions, largest saving first, while the prediction stays under the target
-        for (bool changed = true; changed;) {
-            changed = false;
-            int bi = -1;
-            double bsave = 0;
-            for (int i = 0; i < G; ++i) {
-                if (!m[i]) continue;
-                const int to = (m[i] == 2 && use_x2w && model_prec_x2w_ok(groups[i])) ? 1 : 0;
-                Map t = m;
-                t[i] = to;
-                Err e;
-                predict(t, e);
-                const double save = cost(i, m[i]) - cost(i, to);
-                if (e.worst() <= target && save > bsave) { bi = i; bsave = save; }
-            }
-            if (bi >= 0) { m[bi] = (m[bi] == 2 && use_x2w && model_prec_x2w_ok(groups[bi])) ? 1 : 0; changed = true; }
-        }
-        return m;
-    };
-
-    // ---- 4. greedy selection, checked by a measured run: the calibration frames must come in under headroom x budget AND the held-out frames under
-    // the budget itself; the additive model is within a few per cent, so tighten and repeat when it was optimistic ----
-    Map chosen = all3;
-    Err e_chosen = e_x3;
-    double target = hb * 0.97;
-    for (int attempt = 0; attempt < 6; ++attempt) {
-        Map cand = solve(target);
-        Err e;
-        if (measure(cand, e, false)) return 1;
-        if (accept(e)) { chosen = cand; e_chosen = e; break; }
-        target *= 0.9;
-    }
-    // ---- 5. measured prune: demote one group by one level at a time, largest saving first, keeping every demotion the acceptance rule still passes ----
-    {
-        std::vector<int> order;
-        for (int i = 0; i < G; ++i) if (chosen[i]) order.push_back(i);
-        auto down = [&](int i) { return (chosen[i] == 2 && use_x2w && model_prec_x2w_ok(groups[i])) ? 1 : 0; };
-        auto saving = [&](int i) { return cost(i, chosen[i]) - cost(i, down(i)); };
-        std::sort(order.begin(), order.end(), [&](int a, int b) { return saving(a) > saving(b); });
-        for (int i : order) {
-            if (saving(i) < 1.0) continue;   // nothing to win
-            Map t = chosen;
-            t[i] = down(i);
-            Err e;
-            if (measure(t, e, false)) return 1;
-            if (accept(e)) { chosen = t; e_chosen = e; }
-        }
-    }
-    // the shipped map wins when it passes the same rule on these weights at no higher cost (keeps the tested default where it is valid)
-    if (accept(e_ship) && cost_of(shipped) <= cost_of(chosen)) { chosen = shipped; e_chosen = e_ship; }
-    Err e_final;
-    if (measure(chosen, e_final, true)) return 1;   // leaves the handle prepared for the chosen map
-    h.prec_source = 1;
-    model_drop_graph(h);
-    fill_report(chosen, e_final, shipped, e_ship, e_f16, e_x3);
-    return 0;
-    };
-
-    rc = body();
-    if (rc && touched) {   // put the handle back as it was handed over, prepared again if that still works (its own error is not the one reported)
+    calib::Selection sel;
+    rc = calib::select(p, std::ref(measure), sel);   // the last measured run leaves the handle prepared for the chosen map
+    if (rc && measure.touched) {   // put the handle back as it was handed over, prepared again if that still works (its own error is not the one reported)
         h.prec_map = map_on_entry;
         h.prec_source = source_on_entry;
         h.ws_key = Handle::WsKey();
@@ -420,7 +318,11 @@ int calib_run(Handle& h, const float* x, int B, const soccdpt_calib_options& opt
         (void)hipStreamSynchronize(st);
         return rc;
     }
-    if (!rc) {   // what the map was derived on: soccdpt_prepare compares it and falls back to all-x3 when other weights have been bound or loaded since
+    if (!rc) {
+        h.prec_source = 1;
+        model_drop_graph(h);
+        fill_report(rep, p, sel, measure.forwards, Bc, budget, pp_budget);
+        // what the map was derived on: soccdpt_prepare compares it and falls back to all-x3 when other weights have been bound or loaded since
         unsigned long long fp = 0;
         h.calib_fp_valid = calib_fingerprint(h, s.fp, st, &fp, err) == 0;
         h.calib_fp = fp;

@@ -153,7 +153,9 @@ def test_per_pixel_constraint_and_rebinding_voids_the_calibration(gpu_device, ca
 def test_failed_calibration_leaves_the_handle_as_it_was(gpu_device):
     """an error inside soccdpt_prec_calibrate_ex after its first measured forward used to leave a half-built map on an unprepared handle.
     Provoked here with a workspace that is too small for the calibration batch only AFTER entry checks pass is not possible from outside, so the
-    argument checks are exercised (they must not touch the handle) and the map / source / outputs are compared before and after."""
+    argument checks are exercised (they must not touch the handle) and the map / source / outputs are compared before and after.  A measured forward
+    that fails in the middle of the selection is covered on the CPU: tests/test_calib_select_cpu.py::test_failing_measure_ends_the_selection_at_once
+    (the selection returns at once, with no further forward; the driver then restores the snapshot taken on entry)."""
     from soccdpt_amd.utils.synth import named_weights, synth_input
     m = _build(named_weights("salt1"))
     x = synth_input(3, seed0=4).to(gpu_device)
@@ -166,6 +168,23 @@ def test_failed_calibration_leaves_the_handle_as_it_was(gpu_device):
     assert dict(eng.prec_map()) == map0 and eng.prec_map_source() == src0
     inv1, _ = m.network(x)
     assert torch.equal(inv0, inv1)
+
+
+def test_calibration_is_deterministic(gpu_device):
+    """Two calibrations of fresh models on the same weights and frames (the smallest batch with one selecting and one verifying frame) give the same
+    map and the same report, field for field: the premise of comparing one build of the library against another (profiles/calibrate_split_ab.json)."""
+    from soccdpt_amd.utils.synth import named_weights, synth_input
+    runs = []
+    for _ in range(2):
+        m = _build(named_weights("salt1"))
+        rep = m.calibrate_precision(synth_input(2, seed0=4).to(gpu_device), budget=5e-4, holdout=1)
+        runs.append((dict(m._engine(gpu_device).prec_map()), rep))
+    (map_a, rep_a), (map_b, rep_b) = runs
+    assert rep_a["calib_frames"] == 1 and rep_a["holdout_frames"] == 1
+    assert map_a == map_b
+    assert rep_a.keys() == rep_b.keys()
+    for k in rep_a:
+        assert rep_a[k] == rep_b[k], k
 
 
 def test_calibrate_errors(gpu_device):
