@@ -38,8 +38,10 @@ extern "C" {
  *   7 (occupancy evaluation: soccdpt_occ_pack, soccdpt_occ_points_scratch_bytes / _count / _write and soccdpt_occ_iou_counts are new; nothing
  *     that existed changed);
  *   8 (per-frame occupancy grids: soccdpt_voxelise_frames, soccdpt_occ_expand_frames and soccdpt_forward_frames are new; nothing that existed
- *     changed, soccdpt_config keeps its size). */
-#define SOCCDPT_ABI_VERSION 8
+ *     changed, soccdpt_config keeps its size);
+ *   9 (soccdpt_train_layer_bwd_args, soccdpt_op_train_layer_bwd_scratch_bytes and soccdpt_op_train_layer_bwd are new -- a test entry into the
+ *     training step's layer backward routines; soccdpt_sizeof(5); nothing that existed changed). */
+#define SOCCDPT_ABI_VERSION 9
 
 /* backbone ids: model/loader.py:65-77 (model_type switch), model/blocks.py:59-78 */
 #define SOCCDPT_BACKBONE_SWIN2T16_256 0 /* dpt_swin2_tiny_256 */
@@ -98,7 +100,7 @@ void soccdpt_destroy(void* handle);
 const char* soccdpt_last_error(void* handle); /* handle may be NULL: last create error */
 int soccdpt_abi_version(void);
 /* sizeof of the public structs as the LIBRARY was compiled (a binding checks its own layout against these): which = 0 soccdpt_config,
- * 1 soccdpt_igemm_args, 2 soccdpt_kernel_stat, 3 soccdpt_calib_report, 4 soccdpt_calib_options; unknown -> 0 */
+ * 1 soccdpt_igemm_args, 2 soccdpt_kernel_stat, 3 soccdpt_calib_report, 4 soccdpt_calib_options, 5 soccdpt_train_layer_bwd_args; unknown -> 0 */
 size_t soccdpt_sizeof(int which);
 
 /* ---- precision map (SOCCDPT_PREC_MIXED handles only) ----
@@ -547,6 +549,65 @@ int soccdpt_op_vit_attention(const void* dev_qkv, void* dev_out, int precision, 
  * modes run instead of transposing both operands (csrc/train_wgrad_tn.hip; autograd of nn.Linear / nn.Conv2d weights, scripts/train_SOccDPT.py:360-393). */
 int soccdpt_op_wgrad_tn(const void* dev_a, long lda, const void* dev_b, long ldb, size_t K, int Nout, int C, int taps, int rp, int precision,
                         float* dev_scratch, size_t scratch_floats, float* dev_out, void* stream);
+
+/* One layer backward of the training step (kernel-level entry, TESTS ONLY): runs linear_bwd, conv3_bwd or conv_gen_bwd of csrc/train_step.cpp /
+ * csrc/train_hybrid_step.cpp once on caller-supplied f32 device tensors, through the code soccdpt_train_backward runs (staging kernels, route decisions, gradient
+ * GEMMs); the operand format is the handle's (soccdpt_train_set_amp).  Nothing is read from the handle's weights.
+ *   SOCCDPT_LAYER_LINEAR    y = x W^T + b: dY [M][N], X [M][C], W [N][C] -> dX [M][C] = dY W (+ dX_res [M][C]), dW [N][C] = dY^T X, db [N] = column sums of dY.
+ *                           N % 32 == 0 when dX is requested (the dgrad GEMM's K), C % 4 == 0.
+ *   SOCCDPT_LAYER_CONV3     nn.Conv2d(C, N, 3, padding=1): dY [B*r*r][N] (NHWC pixels), X = the layer input as a zero-bordered image [B][r+2][r+2][C], W [N][C][3][3]
+ *                           -> dX [B*r*r][C] (+ dX_res alike), dW [N][C][3][3], db [N].  N % 32 == 0 when dX is requested, C % 4 == 0.
+ *   SOCCDPT_LAYER_CONV_GEN  the ViT-hybrid's 3x3 convolutions (stride 1 or 2; pad 1, or 0 = timm's 'SAME' padding at stride 2: one zero row / column behind the image)
+ *                           with TAP-MAJOR weights: dY [B*Ho*Ho][N], X [B][Hi+2][Hi+2][C] zero-bordered, W [N][9][C] -> dX [B*Hi*Hi][C], dW [N][9][C], db [N].
+ *                           No dX_res, never deferred.  N, C % 32 == 0.
+ * Outputs are optional (NULL = not computed, at least one must be given) and are OVERWRITTEN, never accumulated -- dW and db too, whether the sum is immediate or
+ * deferred.  stage_weight != 0: W is converted by the batched launch soccdpt_train_backward stages every bound weight with, when its shape has a slot there
+ * (N, C % 32 == 0; linear: C > 32); otherwise, and with stage_weight == 0, the layer converts it itself.  defer != 0: dW / db are treated as bound parameter
+ * gradients -- where the route allows it their split partials wait in an arena inside the scratch and the batched sum (which also writes the 3x3 parameter layout) runs
+ * before the entry returns.  reuse_xt != 0 (CONV3): the staged copy of X a previous call left in the scratch is used again; that call must have been the last one on
+ * this handle, a SOCCDPT_LAYER_CONV3 one on the same scratch and X with the same B, r, C and operand format (N may differ).
+ * scratch: soccdpt_op_train_layer_bwd_scratch_bytes(args) bytes (0 = bad arguments), 256-byte aligned; its contents on entry do not matter.
+ * *path_out (optional) receives SOCCDPT_ROUTE_* bits, set where the routines take their decisions. */
+#define SOCCDPT_LAYER_LINEAR 0
+#define SOCCDPT_LAYER_CONV3 1
+#define SOCCDPT_LAYER_CONV_GEN 2
+#define SOCCDPT_ROUTE_FMT_F32 0x0001u        /* operand format the layer's gradient GEMMs ran in: F32 inside an amp mode = the shape fell back */
+#define SOCCDPT_ROUTE_FMT_BF16 0x0002u
+#define SOCCDPT_ROUTE_FMT_F16 0x0004u
+#define SOCCDPT_ROUTE_FMT_X3 0x0008u
+#define SOCCDPT_ROUTE_WGRAD_TN 0x0010u       /* weight gradient from the operands as stored (train_wgrad_tn.hip) */
+#define SOCCDPT_ROUTE_WGRAD_X3SHIFT 0x0020u  /* x3: shifted views of three pitched transposed copies */
+#define SOCCDPT_ROUTE_WGRAD_IM2COLT 0x0040u  /* explicit im2col^T */
+#define SOCCDPT_ROUTE_WGRAD_HALOSHIFT 0x0080u /* f32 / 16-bit: shifted views of one (16-bit: two) transposed halo image */
+#define SOCCDPT_ROUTE_WGRAD_TRANSPOSE 0x0100u /* linear: both operands transposed */
+#define SOCCDPT_ROUTE_WGRAD_BIG_TILE 0x0200u /* gemm_wgrad chose the 128 x 128 tile */
+#define SOCCDPT_ROUTE_WGRAD_SK_DEFER 0x0400u /* gemm_wgrad's split-K partials summed by a second launch */
+#define SOCCDPT_ROUTE_DGRAD_SPLITK 0x0800u   /* the dgrad GEMM split K */
+#define SOCCDPT_ROUTE_W_STAGED 0x1000u       /* dgrad weight operand from the batched staging launch */
+#define SOCCDPT_ROUTE_W_FALLBACK 0x2000u     /* ... converted by the layer itself */
+#define SOCCDPT_ROUTE_SUM_DEFERRED 0x4000u   /* TN partials summed by the batched launch at the end */
+#define SOCCDPT_ROUTE_SUM_IMMEDIATE 0x8000u  /* ... by a launch of their own */
+#define SOCCDPT_ROUTE_ALL 0xffffu
+typedef struct soccdpt_train_layer_bwd_args {
+    int32_t kind;                 /* SOCCDPT_LAYER_* */
+    int32_t B;                    /* images (ignored for LINEAR) */
+    int32_t M;                    /* LINEAR: rows */
+    int32_t r;                    /* CONV3: image side */
+    int32_t Hi, Ho;               /* CONV_GEN: input / output side */
+    int32_t N, C;                 /* output / input channels (LINEAR: W is [N][C]) */
+    int32_t stride, pad;          /* CONV_GEN */
+    int32_t stage_weight, defer, reuse_xt;
+    int32_t reserved;             /* 0 */
+    const float* dY;
+    const float* X;
+    const float* W;
+    const float* dX_res;          /* optional */
+    float* dX;
+    float* dW;
+    float* db;
+} soccdpt_train_layer_bwd_args;
+size_t soccdpt_op_train_layer_bwd_scratch_bytes(const soccdpt_train_layer_bwd_args* args);
+int soccdpt_op_train_layer_bwd(void* handle, const soccdpt_train_layer_bwd_args* args, void* dev_scratch, size_t scratch_bytes, uint32_t* path_out, void* stream);
 
 /* Swin-V2 cosine window attention of one block (timm WindowAttention + shift/partition/reverse):
  * qkv [B*res*res][3*heads*32] -> out [B*res*res][heads*32], elements bf16 / f32 / fp16 by `precision` (SOCCDPT_PREC_*).  cpb_table [(2ws-1)^2][heads] f32 is

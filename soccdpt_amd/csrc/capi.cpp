@@ -109,6 +109,7 @@ size_t soccdpt_sizeof(int which) {
         case 2: return sizeof(soccdpt_kernel_stat);
         case 3: return sizeof(soccdpt_calib_report);
         case 4: return sizeof(soccdpt_calib_options);
+        case 5: return sizeof(soccdpt_train_layer_bwd_args);
         default: return 0;
     }
 }
@@ -753,6 +754,22 @@ int soccdpt_op_wgrad_tn(const void* dev_a, long lda, const void* dev_b, long ldb
     if (tr_wgrad_tn(dev_a, lda, dev_b, ldb, K, Nout, C, taps, rp, fmt, dev_scratch, scratch_floats, dev_out,
                     (hipStream_t)stream, err))
         return fail(nullptr, err);
+    return 0;
+}
+
+size_t soccdpt_op_train_layer_bwd_scratch_bytes(const soccdpt_train_layer_bwd_args* args) {
+    std::string err;
+    const size_t n = args ? train_layer_bwd_scratch_bytes(*args, err) : 0;
+    if (!n) fail(nullptr, args ? err : "soccdpt_op_train_layer_bwd_scratch_bytes: null args");
+    return n;
+}
+int soccdpt_op_train_layer_bwd(void* handle, const soccdpt_train_layer_bwd_args* args, void* dev_scratch, size_t scratch_bytes, uint32_t* path_out, void* stream) {
+    Handle* h = static_cast<Handle*>(handle);
+    if (!h) return fail(nullptr, "soccdpt_op_train_layer_bwd: null handle");
+    if (!args) return fail(h, "soccdpt_op_train_layer_bwd: null args");
+    unsigned path = 0;
+    if (train_layer_bwd(*h, *args, dev_scratch, scratch_bytes, &path, (hipStream_t)stream, h->err)) return 1;
+    if (path_out) *path_out = path;
     return 0;
 }
 

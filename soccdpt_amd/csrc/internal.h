@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <memory>
 #include <string>
 #include <unordered_map>
 #include <vector>
@@ -150,6 +151,7 @@ struct Handle {
         float drop_path = 0.f;    // were called in between (the reuse_xt staged operands and the DropPath scales belong to the forward)
     } train_key;
     float train_drop_path = 0.f;   // soccdpt_train_set_drop_path: timm drop_path_rate of the Swin-V2 encoder in train mode (0 = off)
+    std::shared_ptr<void> layer_state;   // soccdpt_op_train_layer_bwd (train_step.cpp: LayerState): the tape of the last layer call, kept for reuse_xt
     int train_amp = 0;        // soccdpt_train_set_amp: operand format of the gradient GEMMs (f32 accumulate, f32 weights / activations / gradients): 0 f32, 1 bf16, 2 fp16, 3 x3 split-fp16 (train.h OpFmt)
     hipGraph_t graph = nullptr;
     hipGraphExec_t graph_exec = nullptr;

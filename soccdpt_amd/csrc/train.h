@@ -108,5 +108,8 @@ int train_backward_encoder(Handle& h, int B, const float* const* d_feat, void* w
 int train_workspace_tensor(Handle& h, int B, const char* name, size_t* byte_offset, size_t* elems);
 int train_forward(Handle& h, const float* x, int B, float* inv, float* seg, void* ws, size_t ws_bytes, float dropout_p, unsigned seed, hipStream_t st, std::string& err);
 int train_backward(Handle& h, const float* x, int B, const float* d_inv, const float* d_seg, void* ws, size_t ws_bytes, hipStream_t st, std::string& err);
+// One call of linear_bwd / conv3_bwd / conv_gen_bwd on caller-supplied tensors (soccdpt_op_train_layer_bwd, include/soccdpt_hip.h: tests); *path_out: SOCCDPT_ROUTE_* bits
+size_t train_layer_bwd_scratch_bytes(const soccdpt_train_layer_bwd_args& a, std::string& err);   // 0: bad arguments
+int train_layer_bwd(Handle& h, const soccdpt_train_layer_bwd_args& a, void* scratch, size_t scratch_bytes, unsigned* path_out, hipStream_t st, std::string& err);
 
 }  // namespace soccdpt

@@ -34,6 +34,8 @@ void describe_blocks(const Arch& a, std::vector<RnBlkT>& out) {
     }
 }
 
+}  // namespace
+
 // Backward of a 3x3 convolution with tap-major weights Wtap [N][9][C] over a zero-haloed input [B][Hi+2][Hi+2][C], output Ho x Ho.
 // stride 1 / pad 1: dgrad as the same conv over the rotated filter; otherwise dcol = dY Wtap, then col2im.  dWtap_out [N][9][C].
 int conv_gen_bwd(Ctx& c, const float* dY, const float* Xhalo, const float* Wtap, int Hi, int Ho, int N, int C, int stride, int pad, float* dX_out, float* dWtap_out,
@@ -46,17 +48,24 @@ int conv_gen_bwd(Ctx& c, const float* dY, const float* Xhalo, const float* Wtap,
     // standardised weights of this encoder on both ends.  Everything else takes the f32 path below.
     const OpFmt fmt = amp_fmt(c);
     if (op_is16(fmt) && stride == 1 && pad == 1 && Hi == Ho && tr_wgrad_tn_ok(conv3_tn_rows(B, Ho), N, C, 9)) {
+        c.path |= route_fmt_bit(fmt);
         TRY(conv3_dy_halo(c, dY, Ho, N, fmt));
         if (dX_out) {
+            c.path |= SOCCDPT_ROUTE_W_FALLBACK;
             TRY(th_conv_w_dgrad_tap(Wtap, T.S_dw, N, C, c.st, c.err));                         // [C][9][N] f32, rotated
             TRY(cvt_op(c, T.S_dw, T.S_wt, (size_t)C * 9 * N, fmt));
             TRY(conv3_dgrad_s1(c, T.S_wt, Ho, N, C, fmt, dX_out, nullptr));
         }
-        if (dWtap_out) TRY(conv3_wgrad_tn(c, Xhalo, Ho, N, C, fmt, false, dWtap_out, nullptr, false));
+        if (dWtap_out) {
+            c.path |= SOCCDPT_ROUTE_WGRAD_TN | SOCCDPT_ROUTE_SUM_IMMEDIATE;
+            TRY(conv3_wgrad_tn(c, Xhalo, Ho, N, C, fmt, false, dWtap_out, nullptr, false));
+        }
         if (db) TRY(tr_colsum(dY, nullptr, db, T.S_col, Mo, N, 0, c.st, c.err));
         return 0;
     }
+    c.path |= SOCCDPT_ROUTE_FMT_F32;
     if (dX_out) {
+        c.path |= SOCCDPT_ROUTE_W_FALLBACK;
         if (stride == 1 && pad == 1) {
             const size_t hb = (size_t)B * (Ho + 2) * (Ho + 2) * N * sizeof(float);
             hipError_t e = hipMemsetAsync(T.S_halo, 0, hb, c.st);
@@ -73,6 +82,7 @@ int conv_gen_bwd(Ctx& c, const float* dY, const float* Xhalo, const float* Wtap,
         }
     }
     if (dWtap_out) {
+        c.path |= SOCCDPT_ROUTE_WGRAD_IM2COLT;
         const int Mp = (int)((Mo + 31) / 32 * 32);
         TRY(tr_transpose(dY, T.S_T1, OpFmt::F32, (int)Mo, N, Mp, c.st, c.err));
         TRY(th_im2colT_gen(Xhalo, T.S_T2, B, Hi, Ho, C, stride, pad, (size_t)Mp, c.st, c.err));
@@ -83,6 +93,8 @@ int conv_gen_bwd(Ctx& c, const float* dY, const float* Xhalo, const float* Wtap,
     if (db) TRY(tr_colsum(dY, nullptr, db, T.S_col, Mo, N, 0, c.st, c.err));
     return 0;
 }
+
+namespace {
 
 // GroupNorm statistics ride on the producing convolution as per-tile partials; its reader (gn_apply, gn_finish for the stem) adds them up and leaves
 // {mean, rstd} in `stats` for the backward pass (model.cpp's forward does the same: DESIGN.md 11.5)

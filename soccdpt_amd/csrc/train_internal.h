@@ -105,6 +105,7 @@ struct Ctx {
     int B;
     hipStream_t st;
     std::string& err;
+    unsigned path = 0;   // SOCCDPT_ROUTE_* bits (soccdpt_hip.h), set where linear_bwd / conv3_bwd / conv_gen_bwd / gemm / gemm_wgrad take their decisions; read by train_layer_bwd
     TnDefer tn;   // deferred weight-gradient sums of this pass (flushed by train_backward / train_backward_encoder before they return)
     std::unordered_set<const void*> grad_ptrs;   // the bound parameter-gradient buffers: only sums that land THERE may wait (a gradient written into scratch is read by its caller's next launch)
     bool may_defer(const float* dW, const float* db) const { return tn.arena && grad_ptrs.count(dW) && (!db || grad_ptrs.count(db)); }
@@ -115,6 +116,9 @@ struct Ctx {
 
 #define TRY(call) do { if (call) return 1; } while (0)
 
+inline unsigned route_fmt_bit(OpFmt f) {
+    return f == OpFmt::F32 ? SOCCDPT_ROUTE_FMT_F32 : f == OpFmt::BF16 ? SOCCDPT_ROUTE_FMT_BF16 : f == OpFmt::F16 ? SOCCDPT_ROUTE_FMT_F16 : SOCCDPT_ROUTE_FMT_X3;
+}
 inline OpFmt amp_fmt(const Ctx& c) { return static_cast<OpFmt>(c.h.train_amp); }   // the operand format soccdpt_train_set_amp selected
 int gemm(Ctx& c, IgemmDesc d, OpFmt fmt = OpFmt::F32);   // operands of format fmt, f32 outputs
 // a GEMM of the train-mode FORWARD: exact f32, or -- any train amp mode -- its operands converted to x3 into scratch first (outputs stay f32)
@@ -126,6 +130,9 @@ int copy_d2d(Ctx& c, void* dst, const void* src, size_t bytes, const char* what)
 // this backward pass: two or three launches instead of one per layer.  linear_bwd / conv3_bwd use a staged copy when they find one (staged_wt) and stage their
 // own otherwise (derived weights: padded patch embedding, standardised ResNetV2 kernels).
 int stage_weights(Ctx& c);
+struct WtStage { const float* src; long long off; int R, C, kind; };   // one weight [R][C] (kind 0) or [R][C][3][3] (kind 1) and the element offset of its slot in Tape::WT
+int wt_slot_kind(const int64_t* shape, size_t ndim);   // the kind of slot a weight of this shape has in Tape::WT, -1 = none (converted by its layer)
+int stage_weight_list(Ctx& c, const std::vector<WtStage>& list);   // the launches of stage_weights over an explicit list
 const void* staged_wt(const Ctx& c, const float* W);
 // y = x W^T + b backward.  dY [M][N], X [M][K], W [N][K].  dX_out = dY W (+ dX_res); dW = dY^T X; db = colsum(dY).
 int linear_bwd(Ctx& c, const float* dY, const float* X, const float* W, size_t M, int N, int K, float* dX_out, const float* dX_res, float* dW, float* db);
@@ -142,6 +149,9 @@ IgemmDesc conv_desc(const void* X, int Cin, const void* Wt, int N, int r, int B)
 bool any_grad(const Handle& h, const std::string& prefix);
 
 // train_hybrid_step.cpp
+// Backward of a 3x3 convolution with tap-major weights Wtap [N][9][C] over a zero-haloed input [B][Hi+2][Hi+2][C], output Ho x Ho; dWtap_out [N][9][C]
+int conv_gen_bwd(Ctx& c, const float* dY, const float* Xhalo, const float* Wtap, int Hi, int Ho, int N, int C, int stride, int pad, float* dX_out, float* dWtap_out,
+                 float* db);
 void hy_carve_halo(const Handle& h, int B, TArena& ar, Tape& T);   // inside the zero-filled zone
 void hy_carve(const Handle& h, int B, TArena& ar, Tape& T, size_t& maxAct);
 int hy_forward(Ctx& c, const float* x);       // fills T.feat[0..3]

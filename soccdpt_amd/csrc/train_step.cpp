@@ -15,6 +15,7 @@
 #include "train_internal.h"
 
 #include <cstring>
+#include <memory>
 
 namespace soccdpt {
 namespace trn {
@@ -134,9 +135,7 @@ void carve(const Handle& h, int B, TArena& ar, Tape& T) {
         size_t tot = 0;
         for (size_t i = 0; i < h.weights.size(); ++i) {
             const auto& sh = h.weights[i].shape;
-            const bool lin = (sh.size() == 2 || (sh.size() == 4 && sh[2] == 1 && sh[3] == 1)) && sh[0] % 32 == 0 && sh[1] % 32 == 0 && sh[1] > 32;
-            const bool c3 = sh.size() == 4 && sh[2] == 3 && sh[3] == 3 && sh[0] % 32 == 0 && sh[1] % 32 == 0;
-            if (!lin && !c3) continue;
+            if (wt_slot_kind(sh.data(), sh.size()) < 0) continue;
             T.wt_off[i] = (long long)tot;
             tot += (h.weights[i].numel() + 63) & ~size_t(63);
         }
@@ -169,7 +168,10 @@ int gemm(Ctx& c, IgemmDesc d, OpFmt fmt) {
         if (S > nk / 8) S = nk / 8;
         if (S > 16) S = 16;
         while (S > 1 && (size_t)S * d.M * d.N > kTrainSkPartFloats) --S;
-        if (S > 1) { d.splitk = (int)S; d.sk_part = c.T.sk_part; d.sk_count = c.T.sk_count; d.sk_part_floats = kTrainSkPartFloats; d.sk_count_words = kTrainSkCountWords; }
+        if (S > 1) {
+            d.splitk = (int)S; d.sk_part = c.T.sk_part; d.sk_count = c.T.sk_count; d.sk_part_floats = kTrainSkPartFloats; d.sk_count_words = kTrainSkCountWords;
+            c.path |= SOCCDPT_ROUTE_DGRAD_SPLITK;
+        }
     }
     return launch_igemm(d, c.st, c.err);
 }
@@ -222,6 +224,7 @@ int gemm_wgrad(Ctx& c, IgemmDesc d, OpFmt fmt) {
     if (S > 1 && (size_t)tiles <= kTrainSkCountWords) {
         d.splitk = (int)S; d.sk_part = c.T.sk_part; d.sk_count = c.T.sk_count; d.sk_part_floats = kTrainSkPartFloats; d.sk_count_words = kTrainSkCountWords;
         if ((big || S >= 4) && d.N % 4 == 0) d.sk_defer = 1;   // many splits: sum them in a second chip-wide launch instead of in the last workgroup
+        c.path |= (big ? SOCCDPT_ROUTE_WGRAD_BIG_TILE : 0u) | (d.sk_defer ? SOCCDPT_ROUTE_WGRAD_SK_DEFER : 0u);
     } else if (big) {
         d.tune = -1;
     }
@@ -234,7 +237,13 @@ int copy_d2d(Ctx& c, void* dst, const void* src, size_t bytes, const char* what)
     return 0;
 }
 
-int stage_weights(Ctx& c) {
+int wt_slot_kind(const int64_t* sh, size_t ndim) {
+    const bool lin = (ndim == 2 || (ndim == 4 && sh[2] == 1 && sh[3] == 1)) && sh[0] % 32 == 0 && sh[1] % 32 == 0 && sh[1] > 32;
+    const bool c3 = ndim == 4 && sh[2] == 3 && sh[3] == 3 && sh[0] % 32 == 0 && sh[1] % 32 == 0;
+    return lin ? 0 : c3 ? 1 : -1;
+}
+
+int stage_weight_list(Ctx& c, const std::vector<WtStage>& list) {
     Tape& T = c.T;
     T.wt_by_ptr.clear();
     if (!T.WT) return 0;
@@ -248,21 +257,29 @@ int stage_weights(Ctx& c) {
         tiles = 0;
         return 0;
     };
-    for (size_t i = 0; i < c.h.weights.size(); ++i) {
-        if (T.wt_off[i] < 0 || !c.h.weights[i].ptr) continue;
-        const auto& w = c.h.weights[i];
+    for (const WtStage& w : list) {
         TrBatchEntry& e = t.e[t.n++];
-        e.src = w.ptr;
-        e.dst = T.WT + T.wt_off[i];
-        e.R = (int)w.shape[0];
-        e.C = (int)w.shape[1];
-        e.kind = (w.shape.size() == 4 && w.shape[2] == 3) ? 1 : 0;
+        e.src = w.src;
+        e.dst = T.WT + w.off;
+        e.R = w.R;
+        e.C = w.C;
+        e.kind = w.kind;
         e.tile0 = tiles;
         tiles += e.kind ? (int)(((size_t)e.R * e.C * 9 + 1023) / 1024) : ((e.C + 31) / 32) * ((e.R + 31) / 32);
-        T.wt_by_ptr[w.ptr] = T.wt_off[i];
+        T.wt_by_ptr[w.src] = w.off;
         if (t.n == kTrBatchMax) TRY(flush());
     }
     return flush();
+}
+
+int stage_weights(Ctx& c) {
+    std::vector<WtStage> list;
+    for (size_t i = 0; i < c.h.weights.size() && c.T.WT; ++i) {
+        const auto& w = c.h.weights[i];
+        if (c.T.wt_off[i] < 0 || !w.ptr) continue;
+        list.push_back(WtStage{w.ptr, c.T.wt_off[i], (int)w.shape[0], (int)w.shape[1], (w.shape.size() == 4 && w.shape[2] == 3) ? 1 : 0});
+    }
+    return stage_weight_list(c, list);
 }
 
 const void* staged_wt(const Ctx& c, const float* W) {
@@ -278,32 +295,30 @@ int linear_bwd(Ctx& c, const float* dY, const float* X, const float* W, size_t M
     const bool fits = mode == OpFmt::X3 ? N % 32 == 0 && K % 32 == 0 && K > 32 : N % 32 == 0 && K % 4 == 0 && K > 32;
     const OpFmt fmt = fits ? mode : OpFmt::F32;
     const size_t es = op_size(fmt);
+    c.path |= route_fmt_bit(fmt);
     // Weight gradient from the operands as stored (train_wgrad_tn.hip): no transposes.  Token counts that are not a k-tile multiple (577-token ViT
     // sequences) get zero rows appended to both operands (zero bytes are x3 zeros too).
     const size_t Mtn = (M + 63) / 64 * 64;
     const bool tn = fmt != OpFmt::F32 && dW && tr_wgrad_tn_ok(Mtn, N, K, 1);
-    // Both operand conversions of the layer in ONE launch then: dY for the two gradient GEMMs, X for the weight gradient (round 5; two launches of a
-    // scalar kernel per layer before)
-    const bool pair = tn && (fmt == OpFmt::X3 || ((M * N) % 4 == 0 && (M * K) % 4 == 0));
+    // Both operand conversions of the layer go in ONE launch then: dY for the two gradient GEMMs, X for the weight gradient (round 5; two launches of a
+    // scalar kernel per layer before).  tr_wgrad_tn_ok's N, K % 32 == 0 give tr_cvt_pair the element counts it needs.
     char* const yS = reinterpret_cast<char*>(T.S_T1);   // dY and X in the launch format
     char* const xS = reinterpret_cast<char*>(T.S_T2);
     // a gradient written into scratch (standardised ResNetV2 kernels, the padded patch embedding) is read by its caller's next launch: summed at once; parameter gradients wait for the batched sum
     TnDefer* const df = c.may_defer(dW, db) ? &c.tn : nullptr;   // (the qkv bias gradient, e.g., goes through scratch into q_bias / v_bias)
-    if (pair) TRY(tr_cvt_pair(dY, yS, M * N, X, xS, M * K, fmt, c.st, c.err));
+    if (tn) TRY(tr_cvt_pair(dY, yS, M * N, X, xS, M * K, fmt, c.st, c.err));
     if (dX_out) {
         IgemmDesc d;
         d.M = (int)M; d.N = K; d.Cin = N; d.ldx = N; d.res1 = dX_res; d.out_f32 = dX_out;
         d.Wt = staged_wt(c, W);
+        c.path |= d.Wt ? SOCCDPT_ROUTE_W_STAGED : SOCCDPT_ROUTE_W_FALLBACK;
         if (!d.Wt) { TRY(tr_transpose(W, T.S_wt, fmt, N, K, N, c.st, c.err)); d.Wt = T.S_wt; }   // [K][N]
-        if (fmt != OpFmt::F32 && !pair) TRY(cvt_op(c, dY, yS, M * N, fmt));
+        if (fmt != OpFmt::F32 && !tn) TRY(cvt_op(c, dY, yS, M * N, fmt));
         d.X = fmt == OpFmt::F32 ? static_cast<const void*>(dY) : yS;
         TRY(gemm(c, d, fmt));
     }
-    if (dW && tn) {
-        if (!pair) {   // dY in the launch format is what the dgrad launch above already staged
-            if (!dX_out) TRY(cvt_op(c, dY, yS, M * N, fmt));
-            TRY(cvt_op(c, X, xS, M * K, fmt));
-        }
+    if (tn) {
+        c.path |= SOCCDPT_ROUTE_WGRAD_TN | (df ? SOCCDPT_ROUTE_SUM_DEFERRED : SOCCDPT_ROUTE_SUM_IMMEDIATE);
         if (Mtn > M) {
             hipError_t e = hipMemsetAsync(yS + M * N * es, 0, (Mtn - M) * N * es, c.st);
             if (e == hipSuccess) e = hipMemsetAsync(xS + M * K * es, 0, (Mtn - M) * K * es, c.st);
@@ -313,6 +328,7 @@ int linear_bwd(Ctx& c, const float* dY, const float* X, const float* W, size_t M
         TRY(tr_wgrad_tn(yS, N, xS, K, Mtn, N, K, 1, 0, fmt, T.sk_part, kTrainSkPartFloats, dW, c.st, c.err, db, df));
         db = nullptr;
     } else if (dW) {
+        c.path |= SOCCDPT_ROUTE_WGRAD_TRANSPOSE;
         const int Mp = (int)(op_is16(fmt) ? (M + 127) / 128 * 128 : (M + 31) / 32 * 32);   // k-tile multiple; the padding rows are zero
         TRY(tr_transpose(dY, yS, fmt, (int)M, N, Mp, c.st, c.err));   // [N][Mp]
         TRY(tr_transpose(X, xS, fmt, (int)M, K, Mp, c.st, c.err));    // [K][Mp]
@@ -327,11 +343,7 @@ int linear_bwd(Ctx& c, const float* dY, const float* X, const float* W, size_t M
 // dY [B*r*r][N] as the zero-bordered image [B][r+2][r+2][N] of format fmt in S_halo: the X operand of the stride-1 / pad-1 dgrad (conv3_dgrad_s1) and the
 // A operand of conv3_wgrad_tn
 int conv3_dy_halo(Ctx& c, const float* dY, int r, int N, OpFmt fmt) {
-    if (N % 8 == 0) return tr_to_halo_full(dY, c.T.S_halo, fmt, c.B, r, r, N, c.st, c.err);   // writes the zero border itself
-    // (f32 only: the other formats have N % 32 == 0) clear the buffer first
-    hipError_t e = hipMemsetAsync(c.T.S_halo, 0, (size_t)c.B * (r + 2) * (r + 2) * N * op_size(fmt), c.st);
-    if (e != hipSuccess) { c.err = std::string("conv3_dy_halo memset: ") + hipGetErrorString(e); return 1; }
-    return tr_to_halo(dY, c.T.S_halo, c.B, r, r, N, c.st, c.err);
+    return tr_to_halo_full(dY, c.T.S_halo, fmt, c.B, r, r, N, c.st, c.err);   // writes the zero border itself; N % 8 == 0 (every reader needs N % 32 == 0: the dgrad GEMM's K, the TN kernel's tiles)
 }
 
 // Stride-1 / pad-1 dgrad: dX_out [B*r*r][C] = conv3x3(the dY image in S_halo, Wrot) (+ dX_res), the forward's implicit GEMM over the rotated filter
@@ -377,16 +389,19 @@ int conv3_bwd(Ctx& c, const float* dY, const float* Xhalo, const float* W, int r
     const OpFmt fmt = N % 32 == 0 && C % 32 == 0 ? amp_fmt(c) : OpFmt::F32;   // the amp mode's operand format where the shapes permit it
     const bool x3 = fmt == OpFmt::X3, amp = op_is16(fmt);
     const size_t es = op_size(fmt);
+    c.path |= route_fmt_bit(fmt);
     char* const yS = reinterpret_cast<char*>(T.S_T1);
     char* const xS = reinterpret_cast<char*>(T.S_T2);
     if (dX_out) {
         TRY(conv3_dy_halo(c, dY, r, N, fmt));
         const void* Wrot = staged_wt(c, W);
+        c.path |= Wrot ? SOCCDPT_ROUTE_W_STAGED : SOCCDPT_ROUTE_W_FALLBACK;
         if (!Wrot) { TRY(tr_conv_w_dgrad(W, T.S_wt, fmt, N, C, c.st, c.err)); Wrot = T.S_wt; }   // [C][9][N], rotated
         TRY(conv3_dgrad_s1(c, Wrot, r, N, C, fmt, dX_out, dX_res));
     }
     if (dW && fmt != OpFmt::F32 && tr_wgrad_tn_ok(conv3_tn_rows(B, r), N, C, 9)) {
         if (!dX_out) TRY(conv3_dy_halo(c, dY, r, N, fmt));   // (otherwise the image the dgrad launch staged)
+        c.path |= SOCCDPT_ROUTE_WGRAD_TN | (c.may_defer(dW, db) ? SOCCDPT_ROUTE_SUM_DEFERRED : SOCCDPT_ROUTE_SUM_IMMEDIATE);
         if (c.may_defer(dW, db)) {   // deferred: the batched sum writes the parameter layout itself
             TRY(conv3_wgrad_tn(c, Xhalo, r, N, C, fmt, reuse_xt, dW, db, true));
         } else {
@@ -398,6 +413,7 @@ int conv3_bwd(Ctx& c, const float* dY, const float* Xhalo, const float* W, int r
         // x3 only, no im2col: like the shifted views below, but an x3 tensor is cut in 8-element units, so the views must start at multiples of 16 elements:
         // the pixel order pads every halo row to rpp = roundup(r + 2, 16) pixels (vertical taps = +- rpp) and the horizontal taps read three copies
         // of the transposed image pre-shifted by -1 / 0 / +1 pixel (x_halo_T_kernel).  9 views of 3 copies instead of a 9-fold im2col^T.
+        c.path |= SOCCDPT_ROUTE_WGRAD_X3SHIFT;
         const int rp = r + 2, rpp = (rp + 15) / 16 * 16, Mh = B * rp * rpp, margin = rpp + 16;
         const int ld = (2 * margin + Mh + 31) / 32 * 32;
         const size_t head = (size_t)rpp + 16;                        // zeroed elements in front of and behind each copy (the +- rpp views)
@@ -419,6 +435,7 @@ int conv3_bwd(Ctx& c, const float* dY, const float* Xhalo, const float* W, int r
         TRY(gemm_wgrad(c, d, fmt));
         TRY(tr_wgrad_permute(T.S_dw, dW, N, C, c.st, c.err));
     } else if (dW && (C % 64 != 0 || x3)) {   // (layer1_rn of tiny_256, C = 96: a weight tile would straddle two taps) explicit im2col^T
+        c.path |= SOCCDPT_ROUTE_WGRAD_IM2COLT;
         const int Mp = (int)(amp ? (M + 127) / 128 * 128 : (M + 31) / 32 * 32);
         TRY(tr_transpose(dY, yS, fmt, (int)M, N, Mp, c.st, c.err));             // [N][Mp]
         TRY(tr_im2colT(Xhalo, xS, fmt, B, r, r, C, (size_t)Mp, c.st, c.err));   // [9C][Mp]
@@ -429,6 +446,7 @@ int conv3_bwd(Ctx& c, const float* dY, const float* Xhalo, const float* W, int r
     } else if (dW) {
         // f32 and 16-bit, no im2col: both operands transposed in halo pixel order, tap (ky, kx) = the plain GEMM over a shifted view of the ONE transposed halo
         // image (train.hip: dy_halo_T_kernel).  Margins of r + 3 zero columns on both sides of every row absorb the shifts.
+        c.path |= SOCCDPT_ROUTE_WGRAD_HALOSHIFT;
         const int rp = r + 2, Mh = B * rp * rp, margin = r + 3;
         const int ld = (2 * margin + Mh + 127) / 128 * 128;
         const size_t head = (size_t)(margin + 13) / 8 * 8;     // zeroed elements in FRONT of each copy: the most negative shift reads base - (r + 4)
@@ -490,8 +508,148 @@ int check_train(Handle& h, int B, const void* ws, size_t ws_bytes, std::string& 
     return 0;
 }
 
+
+// ---- one layer backward on caller-supplied tensors (soccdpt_op_train_layer_bwd: tests) ----
+namespace {
+
+// floats of every backward-scratch region one call may touch: what carve() reserves for the whole network, from this layer's shapes, with carve()'s slack terms
+struct LayerGeom { size_t t1 = 0, t2 = 0, halo = 0, wt = 0, dw = 0, slot = 0, arena = 0; };
+// what survives between calls on one handle: the Tape (Tape::xt_tn_src: whose staged copy S_T2 holds) and what the copy was staged for
+struct LayerState {
+    Tape T;
+    const void* scratch = nullptr;
+    const float* X = nullptr;
+    int B = 0, r = 0, C = 0, amp = -1;
+    bool valid = false;
+};
+
+size_t up(size_t v, size_t m) { return (v + m - 1) / m * m; }
+
+int layer_geom(const soccdpt_train_layer_bwd_args& a, LayerGeom& g, std::string& err) {
+    auto bad = [&](const char* m) { err = std::string("soccdpt_op_train_layer_bwd: ") + m; return 1; };
+    if (a.kind != SOCCDPT_LAYER_LINEAR && a.kind != SOCCDPT_LAYER_CONV3 && a.kind != SOCCDPT_LAYER_CONV_GEN) return bad("kind is SOCCDPT_LAYER_LINEAR, _CONV3 or _CONV_GEN");
+    if (a.N <= 0 || a.C <= 0 || a.N % 4 || a.C % 4 || a.N > 8192 || a.C > 8192) return bad("N and C must be positive multiples of 4 (at most 8192)");
+    if (!a.dY || !a.X || !a.W) return bad("dY, X and W must be given");
+    if (!a.dX && !a.dW && !a.db) return bad("no output requested");
+    if (a.dX_res && !a.dX) return bad("dX_res without dX");
+    if (a.dX && a.N % 32) return bad("dX needs N % 32 == 0 (the dgrad GEMM's K)");
+    const size_t N = a.N, C = a.C;
+    size_t krows;   // K of the TN weight-gradient kernel
+    int taps = 9;
+    if (a.kind == SOCCDPT_LAYER_LINEAR) {
+        if (a.M <= 0 || a.M > (1 << 22)) return bad("M must be positive (at most 2^22)");
+        if (a.reuse_xt) return bad("reuse_xt is a SOCCDPT_LAYER_CONV3 flag");
+        taps = 1;
+        krows = up((size_t)a.M, 64);
+        const size_t rows = std::max(krows, up((size_t)a.M, 128)) + 128;   // zero rows up to a k-tile; + the rows an M tile / the TN kernel's column tiles may read past the end
+        g.t1 = rows * N + 256;
+        g.t2 = rows * C + 256;
+        g.halo = 64;
+        g.wt = N * C + 256;
+        g.dw = 64;
+    } else {
+        int r = a.r;
+        if (a.kind == SOCCDPT_LAYER_CONV_GEN) {
+            if (a.reuse_xt || a.dX_res) return bad("SOCCDPT_LAYER_CONV_GEN takes no reuse_xt and no dX_res");
+            if (a.N % 32 || a.C % 32) return bad("SOCCDPT_LAYER_CONV_GEN needs N, C % 32 == 0");
+            if (a.Hi <= 0 || a.Ho <= 0 || a.Hi > 1024) return bad("Hi and Ho must be positive (Hi at most 1024)");
+            const bool s1 = a.stride == 1 && a.pad == 1 && a.Ho == a.Hi;
+            const bool s2 = a.stride == 2 && a.pad == 1 && a.Ho == (a.Hi - 1) / 2 + 1;
+            const bool same2 = a.stride == 2 && a.pad == 0 && a.Hi % 2 == 0 && a.Ho == a.Hi / 2;   // 'SAME' at stride 2: one zero row / column behind an even image
+            if (!s1 && !s2 && !same2) return bad("SOCCDPT_LAYER_CONV_GEN: (stride, pad, Hi, Ho) is (1, 1, H, H), (2, 1, H, (H - 1) / 2 + 1) or (2, 0, H even, H / 2)");
+            r = a.Ho;
+        } else if (a.r <= 0 || a.r > 1024) return bad("r must be positive (at most 1024)");
+        if (a.B <= 0 || a.B > 64) return bad("B must be positive (at most 64)");
+        const size_t B = a.B, rp = r + 2, Kh = B * rp * rp, Kp = conv3_tn_rows(a.B, r), Mo = B * r * r, Mp = up(Mo, 128);
+        krows = Kp;
+        const size_t rpp = up(rp, 16), ld_x3 = up(2 * (rpp + 16) + B * rp * rpp, 32), head_x3 = rpp + 16;          // conv3_bwd's x3 three-copy layout
+        const size_t ld_hs = up(2 * (size_t)(r + 3) + Kh, 128), head_hs = (size_t)(r + 3 + 13) / 8 * 8;            // ... its halo-shift layout (two copies)
+        size_t x = (2 * (rp + 1) + Kp) * C;                                   // conv3_wgrad_tn: margins + halo pixels padded to a k-tile
+        x = std::max(x, 3 * (C * ld_x3 + 2 * head_x3));
+        x = std::max(x, 9 * C * Mp);                                          // im2col^T
+        x = std::max(x, head_hs + 2 * ((C + 1) * ld_hs + 64 + head_hs));
+        x = std::max(x, (Mo + 128) * 9 * C);                                  // conv_gen_bwd's dcol
+        g.t2 = x + 128 * 9 * C;
+        g.t1 = (N + 128) * std::max(std::max(ld_x3, ld_hs), Mp) + 256;
+        g.halo = (Kp + 64) * N + 256;
+        g.wt = 9 * N * C + 256;
+        g.dw = 9 * N * C + 256;
+    }
+    if (a.stage_weight && a.kind != SOCCDPT_LAYER_CONV_GEN) {   // (conv_gen_bwd's tap-major weights are derived ones: never staged)
+        const int64_t sh[4] = {a.N, a.C, 3, 3};
+        if (wt_slot_kind(sh, a.kind == SOCCDPT_LAYER_LINEAR ? 2 : 4) >= 0) g.slot = up(N * C * taps, 64);
+    }
+    if (a.defer) {   // the TN kernel's splits: at most 64, at most one per two k-tiles of at least 32 rows, partials within kTrainSkPartFloats (tr_wgrad_tn)
+        const size_t smax = std::min<size_t>(64, std::max<size_t>(1, krows / 64));
+        g.arena = std::min(smax * (N * taps * C + up(N, 4)), kTrainSkPartFloats) + 64;
+    }
+    return 0;
+}
+
+void carve_layer(const LayerGeom& g, TArena& ar, Tape& T) {
+    T.S_T2 = ar.f(g.t2);   // first: at the same place whatever N is (reuse_xt)
+    T.sk_count = reinterpret_cast<unsigned*>(ar.f(kTrainSkCountWords));
+    T.S_T1 = ar.f(g.t1);
+    T.S_halo = ar.f(g.halo);
+    T.S_wt = ar.f(g.wt);
+    T.S_dw = ar.f(g.dw);
+    T.S_dw_n = g.dw;
+    T.S_col = ar.f((size_t)1 << 20);
+    T.WT = g.slot ? ar.f(g.slot) : nullptr;
+    T.sk_part = ar.f(kTrainSkPartFloats);
+    T.tn_arena = g.arena ? ar.f(g.arena) : nullptr;
+}
+
+}  // namespace
 }  // namespace trn
 using namespace trn;
+
+size_t train_layer_bwd_scratch_bytes(const soccdpt_train_layer_bwd_args& a, std::string& err) {
+    LayerGeom g;
+    if (layer_geom(a, g, err)) return 0;
+    TArena ar(nullptr);
+    Tape T;
+    carve_layer(g, ar, T);
+    return ar.off + 256;
+}
+
+int train_layer_bwd(Handle& h, const soccdpt_train_layer_bwd_args& a, void* scratch, size_t scratch_bytes, unsigned* path_out, hipStream_t st, std::string& err) {
+    LayerGeom g;
+    if (layer_geom(a, g, err)) return 1;
+    if (!scratch || reinterpret_cast<uintptr_t>(scratch) % 256) { err = "soccdpt_op_train_layer_bwd: the scratch must be 256-byte aligned"; return 1; }
+    if (!h.layer_state) h.layer_state = std::make_shared<LayerState>();
+    LayerState& S = *static_cast<LayerState*>(h.layer_state.get());
+    const bool conv3 = a.kind == SOCCDPT_LAYER_CONV3;
+    if (a.reuse_xt && !(S.valid && S.scratch == scratch && S.X == a.X && S.B == a.B && S.r == a.r && S.C == a.C && S.amp == h.train_amp)) {
+        err = "soccdpt_op_train_layer_bwd: reuse_xt needs the previous call on this handle to have been a SOCCDPT_LAYER_CONV3 one on the same scratch, X, B, r, C and operand format";
+        return 1;
+    }
+    S.valid = false;
+    Tape& T = S.T;
+    if (!a.reuse_xt) T.xt_tn_src = nullptr;
+    TArena ar(scratch);
+    carve_layer(g, ar, T);
+    if (scratch_bytes < ar.off + 256) { err = "soccdpt_op_train_layer_bwd: scratch too small"; return 1; }
+    T.wt_by_ptr.clear();
+    {
+        hipError_t e = hipMemsetAsync(T.sk_count, 0, kTrainSkCountWords * sizeof(unsigned), st);   // the split-K arrival counters are zero at rest
+        if (e != hipSuccess) { err = std::string("soccdpt_op_train_layer_bwd memset: ") + hipGetErrorString(e); return 1; }
+    }
+    Ctx c{h, T, conv3 || a.kind == SOCCDPT_LAYER_CONV_GEN ? a.B : 1, st, err};
+    if (a.defer) {   // dW / db take the route of bound parameter gradients
+        c.arm_defer(T.tn_arena, g.arena);
+        if (a.dW) c.grad_ptrs.insert(a.dW);
+        if (a.db) c.grad_ptrs.insert(a.db);
+    }
+    if (g.slot) TRY(stage_weight_list(c, {WtStage{a.W, 0, a.N, a.C, conv3 ? 1 : 0}}));
+    if (a.kind == SOCCDPT_LAYER_LINEAR) TRY(linear_bwd(c, a.dY, a.X, a.W, (size_t)a.M, a.N, a.C, a.dX, a.dX_res, a.dW, a.db));
+    else if (conv3) TRY(conv3_bwd(c, a.dY, a.X, a.W, a.r, a.N, a.C, a.dX, a.dX_res, a.dW, a.db, a.reuse_xt != 0));
+    else TRY(conv_gen_bwd(c, a.dY, a.X, a.W, a.Hi, a.Ho, a.N, a.C, a.stride, a.pad, a.dX, a.dW, a.db));
+    TRY(tn_flush(c.tn, st, err));
+    if (path_out) *path_out = c.path;
+    if (conv3) { S.scratch = scratch; S.X = a.X; S.B = a.B; S.r = a.r; S.C = a.C; S.amp = h.train_amp; S.valid = true; }
+    return 0;
+}
 
 // Named tape tensors for tests / debugging: f32, plain [rows][C] unless noted.
 int train_workspace_tensor(Handle& h, int B, const char* name, size_t* byte_offset, size_t* elems) {

@@ -15,7 +15,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SOCCDPT_LIB_PATH") or os.path.join(_HERE, "libsoccdpt_hip.so")   # override: A/B of two builds in one GPU call (tools/ab_bench.sh)
 
-ABI_VERSION = 8
+ABI_VERSION = 9
 BACKBONE_IDS = {"swin2t16_256": 0, "swin2b24_384": 1, "vitb_rn50_384": 2}
 PREC_BF16 = 0
 PREC_F32 = 1
@@ -98,6 +98,24 @@ class IgemmArgs(ctypes.Structure):
         ("ln_residual", ctypes.c_int32), ("dot3", ctypes.c_int32), ("out_fmt", ctypes.c_int32), ("halo_fmt", ctypes.c_int32),
     ]
 
+
+class TrainLayerBwdArgs(ctypes.Structure):
+    """soccdpt_train_layer_bwd_args (include/soccdpt_hip.h)."""
+    _fields_ = [
+        ("kind", ctypes.c_int32), ("B", ctypes.c_int32), ("M", ctypes.c_int32), ("r", ctypes.c_int32), ("Hi", ctypes.c_int32), ("Ho", ctypes.c_int32),
+        ("N", ctypes.c_int32), ("C", ctypes.c_int32), ("stride", ctypes.c_int32), ("pad", ctypes.c_int32),
+        ("stage_weight", ctypes.c_int32), ("defer", ctypes.c_int32), ("reuse_xt", ctypes.c_int32), ("reserved", ctypes.c_int32),
+        ("dY", ctypes.c_void_p), ("X", ctypes.c_void_p), ("W", ctypes.c_void_p), ("dX_res", ctypes.c_void_p),
+        ("dX", ctypes.c_void_p), ("dW", ctypes.c_void_p), ("db", ctypes.c_void_p),
+    ]
+
+
+LAYER_LINEAR, LAYER_CONV3, LAYER_CONV_GEN = 0, 1, 2
+# SOCCDPT_ROUTE_* (include/soccdpt_hip.h): which way one layer backward went
+ROUTE_BITS = {"fmt_f32": 0x1, "fmt_bf16": 0x2, "fmt_f16": 0x4, "fmt_x3": 0x8, "wgrad_tn": 0x10, "wgrad_x3shift": 0x20, "wgrad_im2colT": 0x40,
+              "wgrad_haloshift": 0x80, "wgrad_transpose": 0x100, "wgrad_big_tile": 0x200, "wgrad_sk_defer": 0x400, "dgrad_splitk": 0x800,
+              "w_staged": 0x1000, "w_fallback": 0x2000, "sum_deferred": 0x4000, "sum_immediate": 0x8000}
+ROUTE_ALL = 0xffff
 
 _lib = None
 
@@ -207,6 +225,8 @@ def _prototypes() -> dict:
         "soccdpt_op_gn_apply": (ci, [vp, vp, vp, ci, vp, vp, vp, vp, vp, ci, vp, vp, vp, vp, vp, vp, ci, ci, cs, ci, ci, ci, ci, cf, vp]),
         "soccdpt_op_vit_attention": (ci, [vp, vp, ci, ci, ci, ci, vp]),
         "soccdpt_op_wgrad_tn": (ci, [vp, ctypes.c_long, vp, ctypes.c_long, cs, ci, ci, ci, ci, ci, vp, cs, vp, vp]),
+        "soccdpt_op_train_layer_bwd_scratch_bytes": (cs, [P(TrainLayerBwdArgs)]),
+        "soccdpt_op_train_layer_bwd": (ci, [vp, P(TrainLayerBwdArgs), vp, cs, P(ctypes.c_uint32), vp]),
         "soccdpt_op_window_attention": (ci, [vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, vp]),
         "soccdpt_op_window_attention_qkv": (ci, [vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, vp, vp]),
         "soccdpt_op_wino_weights": (ci, [vp, vp, vp, ci, ci, ci, vp]),
@@ -264,7 +284,7 @@ def load_library() -> ctypes.CDLL:
     if L.soccdpt_abi_version() != ABI_VERSION:
         raise RuntimeError("libsoccdpt_hip.so ABI version mismatch; rebuild the library")
     # the ctypes mirrors of the public structs must have the layout the library was compiled with (include/soccdpt_hip.h)
-    for which, cls in ((0, SoccdptConfig), (1, IgemmArgs), (2, KernelStat), (3, CalibReport), (4, CalibOptions)):
+    for which, cls in ((0, SoccdptConfig), (1, IgemmArgs), (2, KernelStat), (3, CalibReport), (4, CalibOptions), (5, TrainLayerBwdArgs)):
         if L.soccdpt_sizeof(which) != ctypes.sizeof(cls):
             raise RuntimeError(f"libsoccdpt_hip.so: sizeof mismatch for {cls.__name__}: library {L.soccdpt_sizeof(which)}, binding {ctypes.sizeof(cls)}")
     _lib = L
@@ -774,6 +794,23 @@ def op_wgrad_tn(a, lda, b, ldb, K, Nout, C, taps=1, rp=0, precision=PREC_BF16, b
     _call("soccdpt_op_wgrad_tn", _ptr(a), lda, b.data_ptr() + b_row0 * es, ldb, K, Nout, C, taps, rp, int(precision), _ptr(scratch), scratch.numel(), _ptr(out),
           device=a.device, guard=False)
     return out
+
+
+def op_train_layer_bwd_scratch_bytes(args: TrainLayerBwdArgs) -> int:
+    """Bytes of scratch soccdpt_op_train_layer_bwd needs for `args`; bad arguments raise."""
+    L = load_library()
+    n = L.soccdpt_op_train_layer_bwd_scratch_bytes(ctypes.byref(args))
+    if n == 0:
+        raise RuntimeError(f"soccdpt_op_train_layer_bwd_scratch_bytes failed: {L.soccdpt_last_error(None).decode()}")
+    return n
+
+
+def op_train_layer_bwd(engine: "Engine", args: TrainLayerBwdArgs, scratch: torch.Tensor) -> int:
+    """Kernel-level entry (tests): one linear_bwd / conv3_bwd / conv_gen_bwd of the training step on caller-supplied tensors, in the operand format of
+    Engine.train_set_amp, on the current stream (include/soccdpt_hip.h soccdpt_op_train_layer_bwd) -> the SOCCDPT_ROUTE_* bits of the route taken."""
+    path = ctypes.c_uint32(0)
+    engine._call("soccdpt_op_train_layer_bwd", ctypes.byref(args), scratch.data_ptr(), scratch.numel() * scratch.element_size(), ctypes.byref(path), stream=True)
+    return int(path.value)
 
 
 def op_window_attention(qkv, cpb_table, scale, out, B, res, ws, shift, heads, precision=PREC_BF16):

@@ -115,7 +115,7 @@ def test_training_entry_points_return_errors(gpu_device):
     m.drop_path_rate = 0.0        # the raw C calls below use the handle's default (no stochastic depth); the Python mirror must do the same step
     eng = m._engine(gpu_device)
     need = eng.L.soccdpt_train_workspace_bytes(eng._h, 1)
-    big = torch.full((need,), 0xA5, dtype=torch.uint8, device=gpu_device)        # garbage: NaN patterns in every float
+    big = torch.full((need,), 0xFF, dtype=torch.uint8, device=gpu_device)        # garbage: 0xFF bytes are NaN as f32, bf16, fp16 and in both halves of x3
     # weights not bound yet
     assert eng.L.soccdpt_train_forward(eng._h, x.data_ptr(), 1, inv.data_ptr(), seg.data_ptr(), big.data_ptr(), big.numel(), 0.0, 0, stream) != 0
     assert "not bound" in err(eng)

@@ -6,7 +6,7 @@ HIP backward and float64 autograd differentiate the same piecewise-linear functi
 tests/test_train_step_gpu.py (3e-3 .. 2e-2) is gone, and every parameter gradient, d_path1 and d_feat0..3 (the gradients w.r.t. path_1 and
 the four hooked encoder maps) is held to what f32 arithmetic allows.  torch's f32 autograd over the same pinned oracle is the yardstick.
 
-Each run fills the training workspace with 0xA5 garbage first, uses random-sign upstream gradients, and prints per-site flip counts (how often
+Each run fills the training workspace with 0xFF bytes (NaN in every operand format) first, uses random-sign upstream gradients, and prints per-site flip counts (how often
 the HIP mask disagrees with the sign of the float64 pre-activation), the forward's distance from float64, and median / worst / block-local
 errors next to torch f32.  Bounds (tests/pinned_backward.py SWIN / HYBRID; relative L2 against the pinned float64 gradient, measured on
 MI355X with torch's f32 autograd over the same pinned oracle in brackets):
@@ -66,7 +66,7 @@ def _run(gpu_device, m, sd, model_type, B, sigmoid, dropout_p=0.0, drop_path_rat
     a = torch.randn((B, img, img), generator=g)
     b = torch.randn((B, 3, img, img), generator=g)
     eng = m._engine(gpu_device)
-    eng.train_workspace(B).fill_(0xA5)     # garbage (NaN bit patterns): every region the step reads must be written by the library first
+    eng.train_workspace(B).fill_(0xFF)     # garbage (0xFF bytes: NaN as f32, bf16, fp16 and x3): every region the step reads must be written by the library first
     inv, seg = m.train_forward(x.to(gpu_device), seed=11)
     torch.cuda.synchronize()
     masks, fwd = PB.read_forward(eng, model_type, B, inv, dropout_p)

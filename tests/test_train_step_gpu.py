@@ -450,7 +450,7 @@ def test_amp_gradients_with_criterion(gpu_device):
     inv0, seg0 = m.train_forward(x.to(dev))
     inv0, seg0 = inv0.clone(), seg0.clone()
     m.train_amp = True
-    m._engine(dev).train_workspace(B).fill_(0xA5)     # garbage: the bf16 staging buffers (two shifted copies, margins) must be fully initialised
+    m._engine(dev).train_workspace(B).fill_(0xFF)     # garbage (0xFF bytes: NaN as f32, bf16, fp16 and x3): the bf16 staging buffers (two shifted copies, margins) must be fully initialised
     inv, seg = m.train_forward(x.to(dev))
     assert _rel(inv, inv0) < 5e-6 and _rel(seg, seg0) < 5e-5, (_rel(inv, inv0), _rel(seg, seg0))
     r = training_loss(inv, seg, y_disp.to(dev), mask_disp.to(dev), y_seg.to(dev), mask_seg.to(dev), 0.5, 0.5, compute_scale_and_shift=True)
@@ -621,7 +621,7 @@ def test_hybrid_vit_backward_exact(gpu_device):
     ws = [torch.zeros(feats[0].shape), torch.zeros(feats[1].shape), torch.randn(feats[2].shape, generator=g), torch.randn(feats[3].shape, generator=g)]
     sum((f * w).sum() for f, w in zip(feats, ws)).backward()
     eng = m._engine(gpu_device)
-    eng.train_workspace(1).fill_(0xA5)     # garbage (NaN bit patterns): every region the step reads must be initialised by the library itself
+    eng.train_workspace(1).fill_(0xFF)     # garbage (0xFF bytes: NaN as f32, bf16, fp16 and x3): every region the step reads must be initialised by the library itself
     m.train_forward(x.to(gpu_device))
     eng.train_backward_encoder(1, [_nhwc(w).to(gpu_device) for w in ws])
     torch.cuda.synchronize()
