@@ -40,8 +40,10 @@ extern "C" {
  *   8 (per-frame occupancy grids: soccdpt_voxelise_frames, soccdpt_occ_expand_frames and soccdpt_forward_frames are new; nothing that existed
  *     changed, soccdpt_config keeps its size);
  *   9 (soccdpt_train_layer_bwd_args, soccdpt_op_train_layer_bwd_scratch_bytes and soccdpt_op_train_layer_bwd are new -- a test entry into the
- *     training step's layer backward routines; soccdpt_sizeof(5); nothing that existed changed). */
-#define SOCCDPT_ABI_VERSION 9
+ *     training step's layer backward routines; soccdpt_sizeof(5); nothing that existed changed);
+ *   10 (soccdpt_train_aux_args, soccdpt_op_train_aux_scratch_bytes and soccdpt_op_train_aux are new -- a stateless test entry into the training
+ *     step's non-GEMM launchers; soccdpt_sizeof(6); nothing that existed changed). */
+#define SOCCDPT_ABI_VERSION 10
 
 /* backbone ids: model/loader.py:65-77 (model_type switch), model/blocks.py:59-78 */
 #define SOCCDPT_BACKBONE_SWIN2T16_256 0 /* dpt_swin2_tiny_256 */
@@ -100,7 +102,8 @@ void soccdpt_destroy(void* handle);
 const char* soccdpt_last_error(void* handle); /* handle may be NULL: last create error */
 int soccdpt_abi_version(void);
 /* sizeof of the public structs as the LIBRARY was compiled (a binding checks its own layout against these): which = 0 soccdpt_config,
- * 1 soccdpt_igemm_args, 2 soccdpt_kernel_stat, 3 soccdpt_calib_report, 4 soccdpt_calib_options, 5 soccdpt_train_layer_bwd_args; unknown -> 0 */
+ * 1 soccdpt_igemm_args, 2 soccdpt_kernel_stat, 3 soccdpt_calib_report, 4 soccdpt_calib_options, 5 soccdpt_train_layer_bwd_args,
+ * 6 soccdpt_train_aux_args; unknown -> 0 */
 size_t soccdpt_sizeof(int which);
 
 /* ---- precision map (SOCCDPT_PREC_MIXED handles only) ----
@@ -608,6 +611,75 @@ typedef struct soccdpt_train_layer_bwd_args {
 } soccdpt_train_layer_bwd_args;
 size_t soccdpt_op_train_layer_bwd_scratch_bytes(const soccdpt_train_layer_bwd_args* args);
 int soccdpt_op_train_layer_bwd(void* handle, const soccdpt_train_layer_bwd_args* args, void* dev_scratch, size_t scratch_bytes, uint32_t* path_out, void* stream);
+
+/* Test entry into the training step's launchers that are neither a GEMM nor attention (csrc/train.hip tr_*, csrc/train_hybrid.hip th_*): ONE operation on
+ * caller-supplied device tensors, through the host launchers the step itself calls and in the step's composition.  No handle (the launchers take none), no
+ * allocation, no synchronisation; errors through soccdpt_last_error(NULL).  All tensors are f32 unless noted, rows are NHWC pixels.  "opt" = may be NULL.
+ * Slots not named by a kind are ignored.  dim[], f[] and flags per kind:
+ *   LN_BWD         out = LN(y) g + b backward (train_step.cpp ln_bwd: tr_ln_bwd, then tr_colsum2 / tr_colsum over dout and xhat).  dim {M, C}; f[0] = eps.
+ *                  in {y [M][C], g [C], dout [M][C]}; out {dy [M][C], xhat [M][C] opt, dgamma [C] opt, dbeta [C] opt}.  dy may be dout itself, but only without
+ *                  dgamma / dbeta (their sums read dout after dy is written); dgamma needs xhat.
+ *   COLSUM         tr_colsum.  dim {M, N}; flags bit 0 = accumulate onto out.  in {a [M][N], b [M][N] opt}; out {out [N] = sum_m a (* b)}.
+ *   COLSUM2        tr_colsum2.  dim {M, N}.  in {a, b opt}; out {out_ab [N] = sum_m a (* b), out_a [N] = sum_m a}.
+ *   BN_FWD         train-mode BatchNorm2d + ReLU + Dropout (tr_bn_stats, tr_bn_relu_dropout_fwd).  dim {M, C}; f[0] = eps, f[1] = momentum, f[2] = dropout p;
+ *                  seed.  in {x [M][C], gamma [C], beta [C]}; out {stats [C][2] = mean, 1/std; running_mean [C] opt (read and updated), running_var [C]
+ *                  (with running_mean), y [M][C], keep [M][C] uint8}.
+ *   BN_BWD         its backward (tr_bn_relu_dropout_bwd_pre, tr_bn_xhat, tr_colsum twice, tr_bn_bwd).  dim {M, C}; f[2] = p.
+ *                  in {dout [M][C], y (BN_FWD's), keep, x, stats, gamma}; out {dbeta [C], dgamma [C], dx [M][C]}.  dz and xhat live in the scratch.
+ *   GN_BWD         th_gn_bwd.  dim {B, HW, C, cpg}; flags bit 0 = relu (the mask is recomputed).  in {dout [B*HW][C], x, stats [B][C/cpg][2] = mean, rstd,
+ *                  gamma [C], beta [C]}; out {dx opt (may be dout itself), dgamma [C] opt, dbeta [C] opt}, at least one.  C <= 1024, C % cpg == 0.
+ *   WS_BWD         th_ws_bwd.  dim {Cout, Cin, k, Kpad}; f[0] = eps.  in {dwh [Cout][Kpad] tap-major (tap * Cin + ci), wh [Cout][Kpad] alike, w [Cout][Cin][k][k]};
+ *                  out {dw [Cout][Cin][k][k]}.  Kpad >= Cin k k.
+ *   BILINEAR_BWD   tr_bilinear_bwd (align_corners = True).  dim {B, h, w, H, W, C}; flags bit 0 = accumulate onto dlo.  in {dhi [B][H][W][C]}; out {dlo [B][h][w][C]}.
+ *                  C % 4 == 0 takes the four-channel kernel: both tensors 16-byte aligned then.
+ *   MAXPOOL_BWD    th_maxpool_bwd: 3x3 / 2 max-pool, TF 'SAME' padding of an EVEN side, over relu(GN(raw)).  dim {B, Hi, C, cpg}.  in {dpool [B][Hi/2][Hi/2][C],
+ *                  raw [B][Hi][Hi][C], stats, gamma, beta}; out {idx [B][Hi/2][Hi/2][C] uint8 = 3 ky + kx of the maximum, dA [B][Hi][Hi][C]}.  Odd Hi is
+ *                  refused: 'SAME' would pad on the left too.
+ *   DEPTH_TAIL     tr_depth_tail_fwd, then tr_depth_tail_bwd.  dim {M, K}.  in {e [M][K], w4 [K], b4 [1], dinv [M]}; out {inv [M], de [M][K], rowterm [M][K+1]}.
+ *                  K == 32 takes the float4 kernels: e, w4 and de 16-byte aligned then.
+ *   SMALLK         tr_smallk_dgrad and / or tr_smallk_wgrad.  dim {M, C, K}, K <= 4.  in {dl [M][K], w [K][C] (for dx), x [M][C] (for dw)}; out {dx [M][C] opt, dw [K][C] opt}.
+ *   GELU_BWD       dim {n}.  in {dy, pre}; out {dx} (may be dy itself).
+ *   RELU_BWD       dim {n}.  in {dy, ref, add opt}; out {dx}.
+ *   RELU_BWD_HALO  dim {B, H, W, C}.  in {dy [B][H][W][C], ref [B][H+2][W+2][C], add opt}; out {dx}.
+ *   SEG_ACT_BWD    dim {B, K, S}; flags bit 0 = sigmoid (else ScaledTanh).  in {dseg [B][K][S][S], seg alike}; out {dup [B][S][S][K]}.
+ *   MERGE_SCATTER  dim {B, R, C}, R even.  in {dg [B][R/2][R/2][4C]}; out {dx [B][R][R][C]}.
+ *   SCALE_ROWS     dim {M, C, rows_per_scale}, C % 4 == 0, 16-byte aligned.  in {in [M][C], scale [ceil(M / rows_per_scale)]}; out {out [M][C]}.
+ *   UNSCALE_CHECK  dim {n}; f[0] = inv_scale.  out {g [n] (scaled in place), found int32 [1] (set to 1 when a value is not finite; the caller clears it)}.
+ *   DROP_PATH_FILL dim {B, stream_id}; f[0] = p; seed.  out {out [B]}.
+ * scratch: soccdpt_op_train_aux_scratch_bytes(args) bytes (never 0 for good arguments; 0 = bad arguments, nothing is launched), 256-byte aligned; its contents
+ * on entry do not matter.  It holds what the launchers' own comments ask for: COLSUM chunks N floats, COLSUM2 / LN_BWD chunks 2N, BN_FWD (128 C + C) doubles,
+ * BN_BWD 2 M C + chunks C floats, GN_BWD B chunks 2C + B (C / cpg) 2, SMALLK 256 K C. */
+#define SOCCDPT_AUX_LN_BWD 0
+#define SOCCDPT_AUX_COLSUM 1
+#define SOCCDPT_AUX_COLSUM2 2
+#define SOCCDPT_AUX_BN_FWD 3
+#define SOCCDPT_AUX_BN_BWD 4
+#define SOCCDPT_AUX_GN_BWD 5
+#define SOCCDPT_AUX_WS_BWD 6
+#define SOCCDPT_AUX_BILINEAR_BWD 7
+#define SOCCDPT_AUX_MAXPOOL_BWD 8
+#define SOCCDPT_AUX_DEPTH_TAIL 9
+#define SOCCDPT_AUX_SMALLK 10
+#define SOCCDPT_AUX_GELU_BWD 11
+#define SOCCDPT_AUX_RELU_BWD 12
+#define SOCCDPT_AUX_RELU_BWD_HALO 13
+#define SOCCDPT_AUX_SEG_ACT_BWD 14
+#define SOCCDPT_AUX_MERGE_SCATTER 15
+#define SOCCDPT_AUX_SCALE_ROWS 16
+#define SOCCDPT_AUX_UNSCALE_CHECK 17
+#define SOCCDPT_AUX_DROP_PATH_FILL 18
+#define SOCCDPT_AUX_KINDS 19
+typedef struct soccdpt_train_aux_args {
+    int32_t kind;                 /* SOCCDPT_AUX_* */
+    int32_t flags;
+    int64_t dim[6];
+    float f[3];
+    uint32_t seed;
+    const void* in[6];
+    void* out[6];
+} soccdpt_train_aux_args;
+size_t soccdpt_op_train_aux_scratch_bytes(const soccdpt_train_aux_args* args);
+int soccdpt_op_train_aux(const soccdpt_train_aux_args* args, void* dev_scratch, size_t scratch_bytes, void* stream);
 
 /* Swin-V2 cosine window attention of one block (timm WindowAttention + shift/partition/reverse):
  * qkv [B*res*res][3*heads*32] -> out [B*res*res][heads*32], elements bf16 / f32 / fp16 by `precision` (SOCCDPT_PREC_*).  cpb_table [(2ws-1)^2][heads] f32 is

@@ -110,6 +110,7 @@ size_t soccdpt_sizeof(int which) {
         case 3: return sizeof(soccdpt_calib_report);
         case 4: return sizeof(soccdpt_calib_options);
         case 5: return sizeof(soccdpt_train_layer_bwd_args);
+        case 6: return sizeof(soccdpt_train_aux_args);
         default: return 0;
     }
 }
@@ -770,6 +771,19 @@ int soccdpt_op_train_layer_bwd(void* handle, const soccdpt_train_layer_bwd_args*
     unsigned path = 0;
     if (train_layer_bwd(*h, *args, dev_scratch, scratch_bytes, &path, (hipStream_t)stream, h->err)) return 1;
     if (path_out) *path_out = path;
+    return 0;
+}
+
+size_t soccdpt_op_train_aux_scratch_bytes(const soccdpt_train_aux_args* args) {
+    std::string err;
+    const size_t n = args ? train_aux_scratch_bytes(*args, err) : 0;
+    if (!n) fail(nullptr, args ? err : "soccdpt_op_train_aux_scratch_bytes: null args");
+    return n;
+}
+int soccdpt_op_train_aux(const soccdpt_train_aux_args* args, void* dev_scratch, size_t scratch_bytes, void* stream) {
+    std::string err;
+    if (!args) return fail(nullptr, "soccdpt_op_train_aux: null args");
+    if (train_aux(*args, dev_scratch, scratch_bytes, (hipStream_t)stream, err)) return fail(nullptr, err);
     return 0;
 }
 

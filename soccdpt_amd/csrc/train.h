@@ -38,6 +38,7 @@ int tr_to_halo(const float* in, float* out, int B, int H, int W, int C, hipStrea
 int tr_to_halo_full(const float* in, void* out, OpFmt fmt, int B, int H, int W, int C, hipStream_t st, std::string& err);   // whole image incl. a zero border
 // f32 -> bf16 / IEEE fp16 / x3 of two tensors, one launch.  Element counts: multiples of 4 (x3: of 16).
 int tr_cvt_pair(const float* in0, void* out0, size_t n0, const float* in1, void* out1, size_t n1, OpFmt fmt, hipStream_t st, std::string& err);
+int tr_colsum_chunks(size_t M, int N);   // row chunks of tr_colsum / tr_colsum2: their scratch is chunks * N (colsum2: 2N) floats
 int tr_colsum(const float* a, const float* b, float* out, float* scratch, size_t M, int N, int accumulate, hipStream_t st, std::string& err);
 int tr_colsum2(const float* a, const float* b, float* out_ab, float* out_a, float* scratch, size_t M, int N, hipStream_t st, std::string& err);   // sum a*b and sum a in one pass
 int tr_axpy(float* y, const float* x, size_t n, hipStream_t st, std::string& err);
@@ -86,6 +87,7 @@ int tr_unscale_check(float* g, size_t n, float inv_scale, int* found, hipStream_
 int tr_qv_bias_grad(const float* dqkv_bias, float* dq, float* dv, int C, hipStream_t st, std::string& err);
 
 // train_hybrid.hip: ViT-hybrid encoder (ResNetV2 stem and stages, ViT-B blocks, readout)
+int th_gn_bwd_chunks(int B, int HW, int C);   // pixel chunks per sample: th_gn_bwd's scratch is B * chunks * 2C + B * (C / cpg) * 2 floats
 int th_gn_bwd(const float* dout, const float* x, const float* stats, const float* gamma, const float* beta, float* dx, float* dgamma, float* dbeta, float* scratch, int B,
               int HW, int C, int cpg, int relu, hipStream_t st, std::string& err);
 int th_ws_bwd(const float* dwh, const float* wh, const float* w, float* dw, int Cout, int Cin, int k, int Kpad, float eps, hipStream_t st, std::string& err);
@@ -111,5 +113,9 @@ int train_backward(Handle& h, const float* x, int B, const float* d_inv, const f
 // One call of linear_bwd / conv3_bwd / conv_gen_bwd on caller-supplied tensors (soccdpt_op_train_layer_bwd, include/soccdpt_hip.h: tests); *path_out: SOCCDPT_ROUTE_* bits
 size_t train_layer_bwd_scratch_bytes(const soccdpt_train_layer_bwd_args& a, std::string& err);   // 0: bad arguments
 int train_layer_bwd(Handle& h, const soccdpt_train_layer_bwd_args& a, void* scratch, size_t scratch_bytes, unsigned* path_out, hipStream_t st, std::string& err);
+
+// One non-GEMM launcher (or the step's composition of a few) on caller-supplied tensors (soccdpt_op_train_aux, include/soccdpt_hip.h: tests)
+size_t train_aux_scratch_bytes(const soccdpt_train_aux_args& a, std::string& err);   // 0: bad arguments
+int train_aux(const soccdpt_train_aux_args& a, void* scratch, size_t scratch_bytes, hipStream_t st, std::string& err);
 
 }  // namespace soccdpt

@@ -918,22 +918,23 @@ int tr_to_halo(const float* in, float* out, int B, int H, int W, int C, hipStrea
     SOCCDPT_LAUNCH(to_halo_kernel<float>, dim3(gs_blocks((size_t)B * H * W * C)), dim3(256), 0, st, in, out, B, H, W, C);
     TK("to_halo");
 }
-// scratch: up to 65536 + N floats
-int tr_colsum(const float* a, const float* b, float* out, float* scratch, size_t M, int N, int accumulate, hipStream_t st, std::string& err) {
+// row chunks of the first stage of tr_colsum / tr_colsum2: at most 512 workgroups, at least 16 rows per chunk
+int tr_colsum_chunks(size_t M, int N) {
     const int cb = (N + 63) / 64;
     int chunks = 512 / cb;
     if ((size_t)chunks > (M + 15) / 16) chunks = (int)((M + 15) / 16);
-    if (chunks < 1) chunks = 1;
+    return chunks < 1 ? 1 : chunks;
+}
+// scratch: tr_colsum_chunks(M, N) * N floats (up to 65536 + N)
+int tr_colsum(const float* a, const float* b, float* out, float* scratch, size_t M, int N, int accumulate, hipStream_t st, std::string& err) {
+    const int cb = (N + 63) / 64, chunks = tr_colsum_chunks(M, N);
     SOCCDPT_LAUNCH(colsum_part_kernel<false>, dim3(cb, chunks), dim3(256), 0, st, a, b, scratch, M, N, chunks);
     SOCCDPT_LAUNCH(colsum_final_kernel, dim3(cb), dim3(1024), 0, st, scratch, out, static_cast<float*>(nullptr), N, N, chunks, accumulate);
     TK("colsum");
 }
-// out_ab[n] = sum_m a b, out_a[n] = sum_m a from ONE pass over a (LayerNorm gamma / beta gradients).  scratch: up to 131072 + 2N floats
+// out_ab[n] = sum_m a b, out_a[n] = sum_m a from ONE pass over a (LayerNorm gamma / beta gradients).  scratch: tr_colsum_chunks(M, N) * 2N floats (up to 131072 + 2N)
 int tr_colsum2(const float* a, const float* b, float* out_ab, float* out_a, float* scratch, size_t M, int N, hipStream_t st, std::string& err) {
-    const int cb = (N + 63) / 64;
-    int chunks = 512 / cb;
-    if ((size_t)chunks > (M + 15) / 16) chunks = (int)((M + 15) / 16);
-    if (chunks < 1) chunks = 1;
+    const int cb = (N + 63) / 64, chunks = tr_colsum_chunks(M, N);
     SOCCDPT_LAUNCH(colsum_part_kernel<true>, dim3(cb, chunks), dim3(256), 0, st, a, b, scratch, M, N, chunks);
     SOCCDPT_LAUNCH(colsum_final_kernel, dim3((2 * N + 63) / 64), dim3(1024), 0, st, scratch, out_ab, out_a, N, 2 * N, chunks, 0);
     TK("colsum2");

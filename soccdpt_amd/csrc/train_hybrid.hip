@@ -346,13 +346,17 @@ __global__ void tokens_to_patches_kernel(const float* __restrict__ dtok, float* 
 
 #define TK(name) return check_launch(name, err)
 
-// scratch: B * chunks * 2 * C + B * (C / cpg) * 2 floats.  dx may alias dout.
+// pixel chunks per sample of th_gn_bwd's first stage: at most 512 workgroups (0 for large C * B: one chunk), at least 16 pixels per chunk
+int th_gn_bwd_chunks(int B, int HW, int C) {
+    int chunks = 512 / (((C + 63) / 64) * B);
+    if (chunks > (HW + 15) / 16) chunks = (HW + 15) / 16;
+    return chunks < 1 ? 1 : chunks;
+}
+// scratch: B * chunks * 2 * C + B * (C / cpg) * 2 floats, chunks = th_gn_bwd_chunks(B, HW, C).  dx may alias dout.
 int th_gn_bwd(const float* dout, const float* x, const float* stats, const float* gamma, const float* beta, float* dx, float* dgamma, float* dbeta, float* scratch, int B,
               int HW, int C, int cpg, int relu, hipStream_t st, std::string& err) {
     if (C > 1024 || C % cpg) { err = "gn_bwd: bad channel count"; return 1; }
-    int chunks = 512 / (((C + 63) / 64) * B);
-    if (chunks > (HW + 15) / 16) chunks = (HW + 15) / 16;
-    if (chunks < 1) chunks = 1;
+    const int chunks = th_gn_bwd_chunks(B, HW, C);
     float* part = scratch;
     float* gm = scratch + (size_t)B * chunks * 2 * C;
     SOCCDPT_LAUNCH(gn_bwd_part_kernel, dim3((C + 63) / 64, chunks, B), dim3(256), 0, st, dout, x, stats, gamma, beta, part, HW, C, cpg, chunks, relu);
@@ -386,7 +390,10 @@ int th_stride_scatter_add(const float* dg, float* dx, int B, int Hi, int Ho, int
 }
 int th_maxpool_bwd(const float* dpool, const float* raw, const float* stats, const float* gamma, const float* beta, uint8_t* idx, float* dA, int B, int Hi, int C, int cpg,
                    hipStream_t st, std::string& err) {
-    const int Ho = (Hi + 1) / 2;
+    // the kernels' windows start at 2 o with the one pad row / column behind the image: TF 'SAME' for an even side only (an odd one pads in front too)
+    if (Hi < 2 || (Hi & 1)) { err = "maxpool_bwd: the input side must be even"; return 1; }
+    if (C % cpg) { err = "maxpool_bwd: bad channel count"; return 1; }
+    const int Ho = Hi / 2;
     SOCCDPT_LAUNCH(maxpool_argmax_kernel, dim3(gs_blocks((size_t)B * Ho * Ho * C)), dim3(256), 0, st, raw, stats, gamma, beta, idx, B, Hi, Ho, C, cpg);
     SOCCDPT_LAUNCH(maxpool_bwd_kernel, dim3(gs_blocks((size_t)B * Hi * Hi * C)), dim3(256), 0, st, dpool, idx, dA, B, Hi, Ho, C);
     TK("maxpool_bwd");

@@ -145,6 +145,9 @@ int conv3_dgrad_s1(Ctx& c, const void* Wrot, int r, int N, int C, OpFmt fmt, flo
 // weight gradient from S_halo and Xhalo as stored (train_wgrad_tn.hip): tap-major into `out`, or -- param_layout -- [N][C][3][3] by this pass's batched sum
 int conv3_wgrad_tn(Ctx& c, const float* Xhalo, int r, int N, int C, OpFmt fmt, bool reuse_xt, float* out, float* bias, bool param_layout);
 int ln_bwd(Ctx& c, const float* y, const float* g, const float* dout, float* dy, float* xhat, size_t M, int C, float* dg, float* dbeta, float eps = 1e-5f);
+// the same over an explicit column-sum scratch, stream and error string (soccdpt_op_train_aux has no Ctx)
+int ln_bwd_on(float* s_col, hipStream_t st, std::string& err, const float* y, const float* g, const float* dout, float* dy, float* xhat, size_t M, int C, float* dg,
+              float* dbeta, float eps);
 IgemmDesc conv_desc(const void* X, int Cin, const void* Wt, int N, int r, int B);
 bool any_grad(const Handle& h, const std::string& prefix);
 

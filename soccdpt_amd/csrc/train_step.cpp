@@ -477,12 +477,16 @@ int conv3_bwd(Ctx& c, const float* dY, const float* Xhalo, const float* W, int r
 }
 
 // out = LN(y) g + b backward: d y -> dy; gamma / beta gradients
-int ln_bwd(Ctx& c, const float* y, const float* g, const float* dout, float* dy, float* xhat, size_t M, int C, float* dg, float* dbeta, float eps) {
-    TRY(tr_ln_bwd(y, g, dout, dy, xhat, (int)M, C, eps, c.st, c.err));
-    if (dg && dbeta) return tr_colsum2(dout, xhat, dg, dbeta, c.T.S_col, M, C, c.st, c.err);   // one pass over dout for both (same addition order as the single forms)
-    if (dg) TRY(tr_colsum(dout, xhat, dg, c.T.S_col, M, C, 0, c.st, c.err));
-    if (dbeta) TRY(tr_colsum(dout, nullptr, dbeta, c.T.S_col, M, C, 0, c.st, c.err));
+int ln_bwd_on(float* s_col, hipStream_t st, std::string& err, const float* y, const float* g, const float* dout, float* dy, float* xhat, size_t M, int C, float* dg,
+              float* dbeta, float eps) {
+    TRY(tr_ln_bwd(y, g, dout, dy, xhat, (int)M, C, eps, st, err));
+    if (dg && dbeta) return tr_colsum2(dout, xhat, dg, dbeta, s_col, M, C, st, err);   // one pass over dout for both (same addition order as the single forms)
+    if (dg) TRY(tr_colsum(dout, xhat, dg, s_col, M, C, 0, st, err));
+    if (dbeta) TRY(tr_colsum(dout, nullptr, dbeta, s_col, M, C, 0, st, err));
     return 0;
+}
+int ln_bwd(Ctx& c, const float* y, const float* g, const float* dout, float* dy, float* xhat, size_t M, int C, float* dg, float* dbeta, float eps) {
+    return ln_bwd_on(c.T.S_col, c.st, c.err, y, g, dout, dy, xhat, M, C, dg, dbeta, eps);
 }
 
 IgemmDesc conv_desc(const void* X, int Cin, const void* Wt, int N, int r, int B) {

@@ -15,7 +15,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SOCCDPT_LIB_PATH") or os.path.join(_HERE, "libsoccdpt_hip.so")   # override: A/B of two builds in one GPU call (tools/ab_bench.sh)
 
-ABI_VERSION = 9
+ABI_VERSION = 10
 BACKBONE_IDS = {"swin2t16_256": 0, "swin2b24_384": 1, "vitb_rn50_384": 2}
 PREC_BF16 = 0
 PREC_F32 = 1
@@ -109,6 +109,19 @@ class TrainLayerBwdArgs(ctypes.Structure):
         ("dX", ctypes.c_void_p), ("dW", ctypes.c_void_p), ("db", ctypes.c_void_p),
     ]
 
+
+class TrainAuxArgs(ctypes.Structure):
+    """soccdpt_train_aux_args (include/soccdpt_hip.h): what dim / f / in / out mean is listed there per kind."""
+    _fields_ = [
+        ("kind", ctypes.c_int32), ("flags", ctypes.c_int32), ("dim", ctypes.c_int64 * 6), ("f", ctypes.c_float * 3), ("seed", ctypes.c_uint32),
+        ("inp", ctypes.c_void_p * 6), ("out", ctypes.c_void_p * 6),
+    ]
+
+
+# SOCCDPT_AUX_* (include/soccdpt_hip.h), in the header's order
+AUX_KINDS = ("ln_bwd", "colsum", "colsum2", "bn_fwd", "bn_bwd", "gn_bwd", "ws_bwd", "bilinear_bwd", "maxpool_bwd", "depth_tail", "smallk", "gelu_bwd", "relu_bwd",
+             "relu_bwd_halo", "seg_act_bwd", "merge_scatter", "scale_rows", "unscale_check", "drop_path_fill")
+AUX = {name: i for i, name in enumerate(AUX_KINDS)}
 
 LAYER_LINEAR, LAYER_CONV3, LAYER_CONV_GEN = 0, 1, 2
 # SOCCDPT_ROUTE_* (include/soccdpt_hip.h): which way one layer backward went
@@ -227,6 +240,8 @@ def _prototypes() -> dict:
         "soccdpt_op_wgrad_tn": (ci, [vp, ctypes.c_long, vp, ctypes.c_long, cs, ci, ci, ci, ci, ci, vp, cs, vp, vp]),
         "soccdpt_op_train_layer_bwd_scratch_bytes": (cs, [P(TrainLayerBwdArgs)]),
         "soccdpt_op_train_layer_bwd": (ci, [vp, P(TrainLayerBwdArgs), vp, cs, P(ctypes.c_uint32), vp]),
+        "soccdpt_op_train_aux_scratch_bytes": (cs, [P(TrainAuxArgs)]),
+        "soccdpt_op_train_aux": (ci, [P(TrainAuxArgs), vp, cs, vp]),
         "soccdpt_op_window_attention": (ci, [vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, vp]),
         "soccdpt_op_window_attention_qkv": (ci, [vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, vp, vp]),
         "soccdpt_op_wino_weights": (ci, [vp, vp, vp, ci, ci, ci, vp]),
@@ -284,7 +299,7 @@ def load_library() -> ctypes.CDLL:
     if L.soccdpt_abi_version() != ABI_VERSION:
         raise RuntimeError("libsoccdpt_hip.so ABI version mismatch; rebuild the library")
     # the ctypes mirrors of the public structs must have the layout the library was compiled with (include/soccdpt_hip.h)
-    for which, cls in ((0, SoccdptConfig), (1, IgemmArgs), (2, KernelStat), (3, CalibReport), (4, CalibOptions), (5, TrainLayerBwdArgs)):
+    for which, cls in ((0, SoccdptConfig), (1, IgemmArgs), (2, KernelStat), (3, CalibReport), (4, CalibOptions), (5, TrainLayerBwdArgs), (6, TrainAuxArgs)):
         if L.soccdpt_sizeof(which) != ctypes.sizeof(cls):
             raise RuntimeError(f"libsoccdpt_hip.so: sizeof mismatch for {cls.__name__}: library {L.soccdpt_sizeof(which)}, binding {ctypes.sizeof(cls)}")
     _lib = L
@@ -811,6 +826,21 @@ def op_train_layer_bwd(engine: "Engine", args: TrainLayerBwdArgs, scratch: torch
     path = ctypes.c_uint32(0)
     engine._call("soccdpt_op_train_layer_bwd", ctypes.byref(args), scratch.data_ptr(), scratch.numel() * scratch.element_size(), ctypes.byref(path), stream=True)
     return int(path.value)
+
+
+def op_train_aux_scratch_bytes(args: TrainAuxArgs) -> int:
+    """Bytes of scratch soccdpt_op_train_aux needs for `args`; bad arguments raise.  Launches nothing."""
+    L = load_library()
+    n = L.soccdpt_op_train_aux_scratch_bytes(ctypes.byref(args))
+    if n == 0:
+        raise RuntimeError(f"soccdpt_op_train_aux_scratch_bytes failed: {L.soccdpt_last_error(None).decode()}")
+    return n
+
+
+def op_train_aux(args: TrainAuxArgs, scratch: torch.Tensor) -> None:
+    """Kernel-level entry (tests): one non-GEMM launcher of the training step (or the step's composition of a few) on caller-supplied tensors, on the current
+    stream of the scratch's device (include/soccdpt_hip.h soccdpt_op_train_aux)."""
+    _call("soccdpt_op_train_aux", ctypes.byref(args), scratch.data_ptr(), scratch.numel() * scratch.element_size(), device=scratch.device, guard=False)
 
 
 def op_window_attention(qkv, cpb_table, scale, out, B, res, ws, shift, heads, precision=PREC_BF16):
