@@ -4,13 +4,10 @@
 #include <vector>
 #include "internal.h"
 #include "kernels.h"
+#include "train_plan.h"
 
 namespace soccdpt {
 
-// Format of a gradient GEMM's staged operands.  The values are soccdpt_train_set_amp's codes: Handle::train_amp converts with a cast.
-enum class OpFmt : int { F32 = 0, BF16 = 1, F16 = 2, X3 = 3 };   // exact f32, bf16, IEEE fp16, x3 split-fp16 pairs (half16.h: 4 bytes per element)
-constexpr bool op_is16(OpFmt f) { return f == OpFmt::BF16 || f == OpFmt::F16; }
-constexpr size_t op_size(OpFmt f) { return op_is16(f) ? 2 : 4; }                                      // bytes per element
 constexpr int op_cvt_hf(OpFmt f) { return f == OpFmt::X3 ? 3 : f == OpFmt::F16 ? 5 : 0; }             // launch_cvt_bf16's `hf` (kernels.h); F32 has no conversion
 constexpr int op_igemm_f16(OpFmt f) { return f == OpFmt::F16 ? 1 : 0; }                                // IgemmDesc::f16
 
@@ -65,8 +62,8 @@ int tr_pad_cols(const float* in, float* out, int N, int cin, int cout, hipStream
 int tr_attention_bwd_mfma(const float* qkv, const float* attn_out, const float* dO, const float* table, const float* scale, float* dS, float* rowstat,
                           float* dscale_part, float* dqkv, int B, int res, int ws, int shift, int heads, hipStream_t st, std::string& err, OpFmt fmt);   // fmt: F32, BF16 or F16 products
 int tr_attention_bwd_mfma_slots(int ws);
-// Weight gradient from operands as stored (train_wgrad_tn.hip): out[Nout][taps * C] = sum_k A[k][n] B[k + shift(tap)][c], 16-bit or x3 operands
-bool tr_wgrad_tn_ok(size_t K, int Nout, int C, int taps);
+// Weight gradient from operands as stored (train_wgrad_tn.hip): out[Nout][taps * C] = sum_k A[k][n] B[k + shift(tap)][c], 16-bit or x3 operands; shapes:
+// tr_wgrad_tn_ok (train_plan.h)
 // Deferred reduction of the weight-gradient partials (round 6): every tr_wgrad_tn call used to be followed by its own tn_reduce launch -- 74 launches of ~14 us per
 // bf16-amp step whose work is a few hundred KB each.  With a TnDefer the partials of successive calls stay in an arena (bump allocation, flushed when full) and ONE
 // batched launch per <= 48 gradients sums them -- in split order, like tn_reduce_kernel: the same bits -- at the end of the backward pass (tn_flush).  perm_C > 0: the

@@ -46,9 +46,11 @@ int conv_gen_bwd(Ctx& c, const float* dY, const float* Xhalo, const float* Wtap,
     // 16-bit amp modes, un-strided convolutions of the wide stages (N, C multiples of 128): the path the decoder convolutions take in conv3_bwd -- dgrad on the
     // 16-bit igemm over the zero-bordered dY image, weight gradient from the operands as stored in halo pixel order (train_wgrad_tn.hip) -- with the tap-major
     // standardised weights of this encoder on both ends.  Everything else takes the f32 path below.
-    const OpFmt fmt = amp_fmt(c);
-    if (op_is16(fmt) && stride == 1 && pad == 1 && Hi == Ho && tr_wgrad_tn_ok(conv3_tn_rows(B, Ho), N, C, 9)) {
-        c.path |= route_fmt_bit(fmt);
+    const ConvPlan p = plan_conv_gen(B, Hi, Ho, N, C, stride, pad, amp_fmt(c), PlanReq{dX_out != nullptr, dWtap_out != nullptr, false, false});
+    TRY(check_fit(c, "conv_gen_bwd", with_dw_target(T, p.need, dWtap_out, (size_t)9 * N * C)));
+    const OpFmt fmt = p.fmt;
+    c.path |= route_fmt_bit(fmt) | route_wgrad_bit(p.wgrad);
+    if (fmt != OpFmt::F32) {
         TRY(conv3_dy_halo(c, dY, Ho, N, fmt));
         if (dX_out) {
             c.path |= SOCCDPT_ROUTE_W_FALLBACK;
@@ -57,18 +59,16 @@ int conv_gen_bwd(Ctx& c, const float* dY, const float* Xhalo, const float* Wtap,
             TRY(conv3_dgrad_s1(c, T.S_wt, Ho, N, C, fmt, dX_out, nullptr));
         }
         if (dWtap_out) {
-            c.path |= SOCCDPT_ROUTE_WGRAD_TN | SOCCDPT_ROUTE_SUM_IMMEDIATE;
-            TRY(conv3_wgrad_tn(c, Xhalo, Ho, N, C, fmt, false, dWtap_out, nullptr, false));
+            c.path |= SOCCDPT_ROUTE_SUM_IMMEDIATE;
+            TRY(conv3_wgrad_tn(c, p, Xhalo, N, C, false, dWtap_out, nullptr, false));
         }
         if (db) TRY(tr_colsum(dY, nullptr, db, T.S_col, Mo, N, 0, c.st, c.err));
         return 0;
     }
-    c.path |= SOCCDPT_ROUTE_FMT_F32;
     if (dX_out) {
         c.path |= SOCCDPT_ROUTE_W_FALLBACK;
-        if (stride == 1 && pad == 1) {
-            const size_t hb = (size_t)B * (Ho + 2) * (Ho + 2) * N * sizeof(float);
-            hipError_t e = hipMemsetAsync(T.S_halo, 0, hb, c.st);
+        if (!p.col2im) {
+            hipError_t e = hipMemsetAsync(T.S_halo, 0, p.Kh * N * sizeof(float), c.st);
             if (e != hipSuccess) { c.err = std::string("conv_gen_bwd memset: ") + hipGetErrorString(e); return 1; }
             TRY(tr_to_halo(dY, T.S_halo, B, Ho, Ho, N, c.st, c.err));
             TRY(th_conv_w_dgrad_tap(Wtap, T.S_wt, N, C, c.st, c.err));
@@ -82,8 +82,7 @@ int conv_gen_bwd(Ctx& c, const float* dY, const float* Xhalo, const float* Wtap,
         }
     }
     if (dWtap_out) {
-        c.path |= SOCCDPT_ROUTE_WGRAD_IM2COLT;
-        const int Mp = (int)((Mo + 31) / 32 * 32);
+        const int Mp = p.Mp;
         TRY(tr_transpose(dY, T.S_T1, OpFmt::F32, (int)Mo, N, Mp, c.st, c.err));
         TRY(th_im2colT_gen(Xhalo, T.S_T2, B, Hi, Ho, C, stride, pad, (size_t)Mp, c.st, c.err));
         IgemmDesc d;

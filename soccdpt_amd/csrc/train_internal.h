@@ -89,7 +89,7 @@ struct Tape {
     float *dS, *rowstat, *dscale_part, *dtable, *dt, *S_cpb;
     float* sk_part;
     float* tn_arena;
-    size_t S_dw_n = 0;   // floats of S_dw (a weight gradient written THERE is post-processed at once by its caller: never deferred)
+    ScratchNeed S_cap;   // floats of S_T1, S_T2, S_halo, S_wt and S_dw (carve / carve_layer): every helper holds its plan's need against them (check_fit)
     unsigned* sk_count;
     // dgrad weight operands of the whole backward pass, staged by stage_weights() in a few batched launches (4 bytes per element reserved per weight)
     float* WT = nullptr;
@@ -119,6 +119,22 @@ struct Ctx {
 inline unsigned route_fmt_bit(OpFmt f) {
     return f == OpFmt::F32 ? SOCCDPT_ROUTE_FMT_F32 : f == OpFmt::BF16 ? SOCCDPT_ROUTE_FMT_BF16 : f == OpFmt::F16 ? SOCCDPT_ROUTE_FMT_F16 : SOCCDPT_ROUTE_FMT_X3;
 }
+inline unsigned route_wgrad_bit(WgradPath p) {
+    return p == WgradPath::TN ? SOCCDPT_ROUTE_WGRAD_TN : p == WgradPath::Transpose ? SOCCDPT_ROUTE_WGRAD_TRANSPOSE : p == WgradPath::X3Shift ? SOCCDPT_ROUTE_WGRAD_X3SHIFT :
+           p == WgradPath::HaloShift ? SOCCDPT_ROUTE_WGRAD_HALOSHIFT : p == WgradPath::None ? 0u : SOCCDPT_ROUTE_WGRAD_IM2COLT;
+}
+// A helper's first step: what its plan (train_plan.h) may touch of the shared scratch regions must fit what carve() reserved.  Nothing is launched otherwise.
+inline int check_fit(Ctx& c, const char* who, const ScratchNeed& need) {
+    if (need.fits(c.T.S_cap)) return 0;
+    c.err = std::string(who) + ": scratch region too small: " + need.misfit(c.T.S_cap);
+    return 1;
+}
+// A weight gradient its caller wants INSIDE S_dw (derived weights: standardised ResNetV2 kernels, the padded patch embedding at kPeGradOffset) counts towards
+// the need of the helper that writes it
+inline ScratchNeed with_dw_target(const Tape& T, ScratchNeed need, const float* dW, size_t n) {
+    if (dW && dW >= T.S_dw && dW < T.S_dw + T.S_cap.dw) need.dw = std::max(need.dw, (size_t)(dW - T.S_dw) + n);
+    return need;
+}
 inline OpFmt amp_fmt(const Ctx& c) { return static_cast<OpFmt>(c.h.train_amp); }   // the operand format soccdpt_train_set_amp selected
 int gemm(Ctx& c, IgemmDesc d, OpFmt fmt = OpFmt::F32);   // operands of format fmt, f32 outputs
 // a GEMM of the train-mode FORWARD: exact f32, or -- any train amp mode -- its operands converted to x3 into scratch first (outputs stay f32)
@@ -139,11 +155,11 @@ int linear_bwd(Ctx& c, const float* dY, const float* X, const float* W, size_t M
 int conv3_bwd(Ctx& c, const float* dY, const float* Xhalo, const float* W, int r, int N, int C, float* dX_out, const float* dX_res, float* dW, float* db,
               bool reuse_xt = false);   // reuse_xt: the im2col^T of Xhalo is still in S_T2 from the previous call
 // The 3x3 staging conv3_bwd shares with the ViT-hybrid encoder's conv_gen_bwd (stride 1 / pad 1; the callers differ in the weight layout and the output permute)
-inline size_t conv3_tn_rows(int B, int r) { return ((size_t)B * (r + 2) * (r + 2) + 63) / 64 * 64; }   // K of conv3_wgrad_tn: halo pixels, padded to a k-tile
 int conv3_dy_halo(Ctx& c, const float* dY, int r, int N, OpFmt fmt);   // dY as a zero-bordered image of format fmt in S_halo
 int conv3_dgrad_s1(Ctx& c, const void* Wrot, int r, int N, int C, OpFmt fmt, float* dX_out, const float* dX_res);   // over S_halo and the rotated filter [C][9][N]
-// weight gradient from S_halo and Xhalo as stored (train_wgrad_tn.hip): tap-major into `out`, or -- param_layout -- [N][C][3][3] by this pass's batched sum
-int conv3_wgrad_tn(Ctx& c, const float* Xhalo, int r, int N, int C, OpFmt fmt, bool reuse_xt, float* out, float* bias, bool param_layout);
+// weight gradient from S_halo and Xhalo as stored (train_wgrad_tn.hip) in the layout of the caller's plan p (already checked): tap-major into `out`, or --
+// param_layout -- [N][C][3][3] by this pass's batched sum
+int conv3_wgrad_tn(Ctx& c, const ConvPlan& p, const float* Xhalo, int N, int C, bool reuse_xt, float* out, float* bias, bool param_layout);
 int ln_bwd(Ctx& c, const float* y, const float* g, const float* dout, float* dy, float* xhat, size_t M, int C, float* dg, float* dbeta, float eps = 1e-5f);
 // the same over an explicit column-sum scratch, stream and error string (soccdpt_op_train_aux has no Ctx)
 int ln_bwd_on(float* s_col, hipStream_t st, std::string& err, const float* y, const float* g, const float* dout, float* dy, float* xhat, size_t M, int C, float* dg,

@@ -121,14 +121,18 @@ void carve(const Handle& h, int B, TArena& ar, Tape& T) {
     T.GP = ar.f(M1 * F);
     T.DOC = ar.f((size_t)B * a.fres(0) * a.fres(0) * F);
     for (int l = 0; l < 4; ++l) T.DF[l] = ar.f((size_t)B * a.fres(l) * a.fres(l) * a.fdim(l));
-    T.S_T1 = ar.f(maxAct + 128 * 4 * Cmax0);
-    T.S_T2 = ar.f(std::max(std::max(M1 * 9 * F, M0p * 9 * (size_t)(F / 2)), maxAct) + 128 * 9 * Cmax0);
-    T.S_halo = ar.f(std::max((size_t)B * (r1 + 2) * (r1 + 2) * F, (size_t)B * (r0 + 2) * (r0 + 2) * (size_t)(F / 2)) + 64 * (size_t)F);   // + the k-tile padding rows of train_wgrad_tn.hip
     const size_t Cmax = a.hybrid ? 1024 : a.dim(3);
     const size_t wmax = std::max(std::max((size_t)9 * F * F, 4 * Cmax * Cmax), a.hybrid ? (size_t)9 * 768 * 768 : 0);
-    T.S_wt = ar.f(wmax);
-    T.S_dw = ar.f(wmax);
-    T.S_dw_n = wmax;
+    ScratchNeed& cap = T.S_cap;   // hand-derived maxima over the network's layers; every helper checks its plan against them (check_fit)
+    cap.t1 = maxAct + 128 * 4 * Cmax0;
+    cap.t2 = std::max(std::max(M1 * 9 * F, M0p * 9 * (size_t)(F / 2)), maxAct) + 128 * 9 * Cmax0;
+    cap.halo = std::max((size_t)B * (r1 + 2) * (r1 + 2) * F, (size_t)B * (r0 + 2) * (r0 + 2) * (size_t)(F / 2)) + 64 * (size_t)F;   // + the k-tile padding rows of train_wgrad_tn.hip
+    cap.wt = cap.dw = wmax;
+    T.S_T1 = ar.f(cap.t1);
+    T.S_T2 = ar.f(cap.t2);
+    T.S_halo = ar.f(cap.halo);
+    T.S_wt = ar.f(cap.wt);
+    T.S_dw = ar.f(cap.dw);
     T.S_col = ar.f((size_t)1 << 20);
     {   // slots of the staged dgrad weight operands (stage_weights): Linear [N][K] and 1x1 conv weights with N, K multiples of 32 and K > 32, 3x3 conv weights with N, C multiples of 32
         T.wt_off.assign(h.weights.size(), -1);
@@ -186,9 +190,10 @@ int cvt_op(Ctx& c, const float* in, void* out, size_t n, OpFmt fmt) {
 // writes stays f32 (out_f32, and out_op as an f32 tensor: out_op_f32), so the tape and the backward are unchanged.  x_elems / w_elems: elements of
 // the X buffer (a halo image counts its border) and of the weight matrix.
 int gemm_fwd(Ctx& c, IgemmDesc d, size_t x_elems, size_t w_elems) {
-    const bool x3 = amp_fmt(c) != OpFmt::F32 && d.Cin % 32 == 0 && (d.taps == 9 || d.ldx % 16 == 0) && x_elems % 16 == 0 && w_elems % 16 == 0 && !d.ln_g &&
-                    !d.grp_rows && !d.gather1 && d.stride == 1 && d.pad == 1 && d.in_halo == 1;
-    if (!x3) return gemm(c, d);
+    const FwdPlan p = plan_gemm_fwd(x_elems, w_elems, amp_fmt(c), d.Cin % 32 == 0 && (d.taps == 9 || d.ldx % 16 == 0) && !d.ln_g && !d.grp_rows && !d.gather1 &&
+                                                                      d.stride == 1 && d.pad == 1 && d.in_halo == 1);
+    if (!p.x3) return gemm(c, d);
+    TRY(check_fit(c, "gemm_fwd", p.need));
     TRY(tr_cvt_pair(static_cast<const float*>(d.X), c.T.S_T2, x_elems, static_cast<const float*>(d.Wt), c.T.S_wt, w_elems, OpFmt::X3, c.st, c.err));
     d.X = c.T.S_T2; d.Wt = c.T.S_wt; d.out_op_f32 = 1;
     return gemm(c, d, OpFmt::X3);
@@ -290,16 +295,15 @@ const void* staged_wt(const Ctx& c, const float* W) {
 // y = x W^T + b backward.  dY [M][N], X [M][K], W [N][K].  dX_out = dY W (+ dX_res); dW = dY^T X; db = colsum(dY).
 int linear_bwd(Ctx& c, const float* dY, const float* X, const float* W, size_t M, int N, int K, float* dX_out, const float* dX_res, float* dW, float* db) {
     Tape& T = c.T;
-    // The operand format of the layer's two gradient GEMMs: the amp mode's where the shapes permit it (x3: f32-grade, 4 bytes per element), exact f32 otherwise
-    const OpFmt mode = amp_fmt(c);
-    const bool fits = mode == OpFmt::X3 ? N % 32 == 0 && K % 32 == 0 && K > 32 : N % 32 == 0 && K % 4 == 0 && K > 32;
-    const OpFmt fmt = fits ? mode : OpFmt::F32;
-    const size_t es = op_size(fmt);
-    c.path |= route_fmt_bit(fmt);
-    // Weight gradient from the operands as stored (train_wgrad_tn.hip): no transposes.  Token counts that are not a k-tile multiple (577-token ViT
-    // sequences) get zero rows appended to both operands (zero bytes are x3 zeros too).
-    const size_t Mtn = (M + 63) / 64 * 64;
-    const bool tn = fmt != OpFmt::F32 && dW && tr_wgrad_tn_ok(Mtn, N, K, 1);
+    // The operand format of the layer's two gradient GEMMs: the amp mode's where the shapes permit it (x3: f32-grade, 4 bytes per element), exact f32 otherwise.
+    // Weight gradient from the operands as stored (train_wgrad_tn.hip) where it can be: no transposes.  Token counts that are not a k-tile multiple (577-token
+    // ViT sequences) get zero rows appended to both operands (zero bytes are x3 zeros too).
+    const LinearPlan p = plan_linear(M, N, K, amp_fmt(c), PlanReq{dX_out != nullptr, dW != nullptr, staged_wt(c, W) != nullptr, false});
+    TRY(check_fit(c, "linear_bwd", with_dw_target(T, p.need, dW, (size_t)N * K)));
+    const OpFmt fmt = p.fmt;
+    const size_t es = op_size(fmt), Mtn = p.Mtn;
+    const bool tn = p.wgrad == WgradPath::TN;
+    c.path |= route_fmt_bit(fmt) | route_wgrad_bit(p.wgrad);
     // Both operand conversions of the layer go in ONE launch then: dY for the two gradient GEMMs, X for the weight gradient (round 5; two launches of a
     // scalar kernel per layer before).  tr_wgrad_tn_ok's N, K % 32 == 0 give tr_cvt_pair the element counts it needs.
     char* const yS = reinterpret_cast<char*>(T.S_T1);   // dY and X in the launch format
@@ -318,7 +322,7 @@ int linear_bwd(Ctx& c, const float* dY, const float* X, const float* W, size_t M
         TRY(gemm(c, d, fmt));
     }
     if (tn) {
-        c.path |= SOCCDPT_ROUTE_WGRAD_TN | (df ? SOCCDPT_ROUTE_SUM_DEFERRED : SOCCDPT_ROUTE_SUM_IMMEDIATE);
+        c.path |= df ? SOCCDPT_ROUTE_SUM_DEFERRED : SOCCDPT_ROUTE_SUM_IMMEDIATE;
         if (Mtn > M) {
             hipError_t e = hipMemsetAsync(yS + M * N * es, 0, (Mtn - M) * N * es, c.st);
             if (e == hipSuccess) e = hipMemsetAsync(xS + M * K * es, 0, (Mtn - M) * K * es, c.st);
@@ -328,8 +332,7 @@ int linear_bwd(Ctx& c, const float* dY, const float* X, const float* W, size_t M
         TRY(tr_wgrad_tn(yS, N, xS, K, Mtn, N, K, 1, 0, fmt, T.sk_part, kTrainSkPartFloats, dW, c.st, c.err, db, df));
         db = nullptr;
     } else if (dW) {
-        c.path |= SOCCDPT_ROUTE_WGRAD_TRANSPOSE;
-        const int Mp = (int)(op_is16(fmt) ? (M + 127) / 128 * 128 : (M + 31) / 32 * 32);   // k-tile multiple; the padding rows are zero
+        const int Mp = p.Mp;   // k-tile multiple; the padding rows are zero
         TRY(tr_transpose(dY, yS, fmt, (int)M, N, Mp, c.st, c.err));   // [N][Mp]
         TRY(tr_transpose(X, xS, fmt, (int)M, K, Mp, c.st, c.err));    // [K][Mp]
         IgemmDesc d;
@@ -357,17 +360,17 @@ int conv3_dgrad_s1(Ctx& c, const void* Wrot, int r, int N, int C, OpFmt fmt, flo
 
 // Weight gradient of a stride-1 / pad-1 3x3 convolution from the operands as stored, in halo pixel order (train_wgrad_tn.hip; shapes: tr_wgrad_tn_ok over
 // conv3_tn_rows): A = the dY image of conv3_dy_halo in S_halo, B = the input's halo image converted to the operand format into S_T2; tap (ky, kx) reads B
-// (ky - 1)(r + 2) + (kx - 1) rows further on.  K is padded to a k-tile with zero rows of A; B gets zero margins of r + 3 rows on both sides (border pixels of A
-// are zero, but 0 * NaN is not).  reuse_xt: B is left as it is when S_T2 still holds Xhalo's copy (Tape::xt_tn_src).  bias: the column sums of dY ride in the
+// (ky - 1)(r + 2) + (kx - 1) rows further on.  K is padded to a k-tile with zero rows of A; B gets zero margins of ConvPlan::mrg rows on both sides (border
+// pixels of A are zero, but 0 * NaN is not).  reuse_xt: B is left as it is when S_T2 still holds Xhalo's copy (Tape::xt_tn_src).  bias: the column sums of dY ride in the
 // launch (its zero border adds nothing).  param_layout: `out` is a bound gradient [N][C][3][3] that the batched sum of this pass writes (Ctx::may_defer holds);
 // otherwise `out` receives the kernel's tap-major [N][9][C] at once.
-int conv3_wgrad_tn(Ctx& c, const float* Xhalo, int r, int N, int C, OpFmt fmt, bool reuse_xt, float* out, float* bias, bool param_layout) {
+int conv3_wgrad_tn(Ctx& c, const ConvPlan& p, const float* Xhalo, int N, int C, bool reuse_xt, float* out, float* bias, bool param_layout) {
     Tape& T = c.T;
+    const OpFmt fmt = p.fmt;
     const size_t es = op_size(fmt);
     char* const hS = reinterpret_cast<char*>(T.S_halo);
     char* const xS = reinterpret_cast<char*>(T.S_T2);
-    const int rp = r + 2;
-    const size_t Kh = (size_t)c.B * rp * rp, Kp = conv3_tn_rows(c.B, r), mrg = (size_t)rp + 1;
+    const size_t Kh = p.Kh, Kp = p.Kp, mrg = p.mrg;
     hipError_t e = Kp > Kh ? hipMemsetAsync(hS + Kh * N * es, 0, (Kp - Kh) * N * es, c.st) : hipSuccess;
     if (!reuse_xt || T.xt_tn_src != Xhalo) {
         T.xt_tn_src = Xhalo;
@@ -376,7 +379,7 @@ int conv3_wgrad_tn(Ctx& c, const float* Xhalo, int r, int N, int C, OpFmt fmt, b
         if (e == hipSuccess) TRY(cvt_op(c, Xhalo, xS + mrg * C * es, Kh * C, fmt));
     }
     if (e != hipSuccess) { c.err = std::string("conv3_wgrad_tn memset: ") + hipGetErrorString(e); return 1; }
-    return tr_wgrad_tn(hS, N, xS + mrg * C * es, C, Kp, N, C, 9, rp, fmt, T.sk_part, kTrainSkPartFloats, out, c.st, c.err, bias, param_layout ? &c.tn : nullptr,
+    return tr_wgrad_tn(hS, N, xS + mrg * C * es, C, Kp, N, C, 9, p.rp, fmt, T.sk_part, kTrainSkPartFloats, out, c.st, c.err, bias, param_layout ? &c.tn : nullptr,
                        param_layout ? C : 0);
 }
 
@@ -386,10 +389,13 @@ int conv3_bwd(Ctx& c, const float* dY, const float* Xhalo, const float* W, int r
     Tape& T = c.T;
     const int B = c.B;
     const size_t M = (size_t)B * r * r;
-    const OpFmt fmt = N % 32 == 0 && C % 32 == 0 ? amp_fmt(c) : OpFmt::F32;   // the amp mode's operand format where the shapes permit it
-    const bool x3 = fmt == OpFmt::X3, amp = op_is16(fmt);
+    const bool defer = c.may_defer(dW, db);
+    const ConvPlan p = plan_conv3(B, r, N, C, amp_fmt(c), PlanReq{dX_out != nullptr, dW != nullptr, staged_wt(c, W) != nullptr, defer});
+    TRY(check_fit(c, "conv3_bwd", p.need));
+    const OpFmt fmt = p.fmt;   // the amp mode's operand format where the shapes permit it
+    const bool amp = op_is16(fmt);
     const size_t es = op_size(fmt);
-    c.path |= route_fmt_bit(fmt);
+    c.path |= route_fmt_bit(fmt) | route_wgrad_bit(p.wgrad);
     char* const yS = reinterpret_cast<char*>(T.S_T1);
     char* const xS = reinterpret_cast<char*>(T.S_T2);
     if (dX_out) {
@@ -399,77 +405,48 @@ int conv3_bwd(Ctx& c, const float* dY, const float* Xhalo, const float* W, int r
         if (!Wrot) { TRY(tr_conv_w_dgrad(W, T.S_wt, fmt, N, C, c.st, c.err)); Wrot = T.S_wt; }   // [C][9][N], rotated
         TRY(conv3_dgrad_s1(c, Wrot, r, N, C, fmt, dX_out, dX_res));
     }
-    if (dW && fmt != OpFmt::F32 && tr_wgrad_tn_ok(conv3_tn_rows(B, r), N, C, 9)) {
+    if (p.wgrad == WgradPath::TN) {
         if (!dX_out) TRY(conv3_dy_halo(c, dY, r, N, fmt));   // (otherwise the image the dgrad launch staged)
-        c.path |= SOCCDPT_ROUTE_WGRAD_TN | (c.may_defer(dW, db) ? SOCCDPT_ROUTE_SUM_DEFERRED : SOCCDPT_ROUTE_SUM_IMMEDIATE);
-        if (c.may_defer(dW, db)) {   // deferred: the batched sum writes the parameter layout itself
-            TRY(conv3_wgrad_tn(c, Xhalo, r, N, C, fmt, reuse_xt, dW, db, true));
+        c.path |= defer ? SOCCDPT_ROUTE_SUM_DEFERRED : SOCCDPT_ROUTE_SUM_IMMEDIATE;
+        if (defer) {   // the batched sum writes the parameter layout itself
+            TRY(conv3_wgrad_tn(c, p, Xhalo, N, C, reuse_xt, dW, db, true));
         } else {
-            TRY(conv3_wgrad_tn(c, Xhalo, r, N, C, fmt, reuse_xt, T.S_dw, db, false));
+            TRY(conv3_wgrad_tn(c, p, Xhalo, N, C, reuse_xt, T.S_dw, db, false));
             TRY(tr_wgrad_permute(T.S_dw, dW, N, C, c.st, c.err));
         }
         db = nullptr;
-    } else if (dW && x3 && C % 64 == 0) {
-        // x3 only, no im2col: like the shifted views below, but an x3 tensor is cut in 8-element units, so the views must start at multiples of 16 elements:
-        // the pixel order pads every halo row to rpp = roundup(r + 2, 16) pixels (vertical taps = +- rpp) and the horizontal taps read three copies
-        // of the transposed image pre-shifted by -1 / 0 / +1 pixel (x_halo_T_kernel).  9 views of 3 copies instead of a 9-fold im2col^T.
-        c.path |= SOCCDPT_ROUTE_WGRAD_X3SHIFT;
-        const int rp = r + 2, rpp = (rp + 15) / 16 * 16, Mh = B * rp * rpp, margin = rpp + 16;
-        const int ld = (2 * margin + Mh + 31) / 32 * 32;
-        const size_t head = (size_t)rpp + 16;                        // zeroed elements in front of and behind each copy (the +- rpp views)
-        const size_t copy_elems = (size_t)C * ld + 2 * head;
-        TRY(tr_dy_halo_T(dY, yS, fmt, B, r, N, margin, ld, c.st, c.err, rpp));
-        if (!reuse_xt || T.xt_tn_src) {
-            T.xt_tn_src = nullptr;
-            for (int kx = 0; kx < 3; ++kx) {
-                char* base = xS + (size_t)kx * copy_elems * es;
-                hipError_t e = hipMemsetAsync(base, 0, head * es, c.st);
-                if (e == hipSuccess) e = hipMemsetAsync(base + (head + (size_t)C * ld) * es, 0, head * es, c.st);
-                if (e != hipSuccess) { c.err = std::string("conv3_bwd memset: ") + hipGetErrorString(e); return 1; }
-                TRY(tr_x_halo_T_x3(Xhalo, base + head * es, B, r, C, margin - (kx - 1), ld, rpp, c.st, c.err));
-            }
-        }
+    } else if (p.wgrad == WgradPath::Im2colT) {   // (layer1_rn of tiny_256, C = 96: a weight tile would straddle two taps) explicit im2col^T
+        TRY(tr_transpose(dY, yS, fmt, (int)M, N, p.Mp, c.st, c.err));             // [N][Mp]
+        TRY(tr_im2colT(Xhalo, xS, fmt, B, r, r, C, (size_t)p.Mp, c.st, c.err));   // [9C][Mp]
         IgemmDesc d;
-        d.X = yS; d.Wt = xS; d.M = N; d.N = 9 * C; d.Cin = ld; d.ldx = ld; d.out_f32 = T.S_dw;
-        d.wt_grp_rows = C; d.wt_rp = rpp; d.wt_base = (int)head; d.wt_kx = (int)copy_elems;
-        TRY(gemm_wgrad(c, d, fmt));
-        TRY(tr_wgrad_permute(T.S_dw, dW, N, C, c.st, c.err));
-    } else if (dW && (C % 64 != 0 || x3)) {   // (layer1_rn of tiny_256, C = 96: a weight tile would straddle two taps) explicit im2col^T
-        c.path |= SOCCDPT_ROUTE_WGRAD_IM2COLT;
-        const int Mp = (int)(amp ? (M + 127) / 128 * 128 : (M + 31) / 32 * 32);
-        TRY(tr_transpose(dY, yS, fmt, (int)M, N, Mp, c.st, c.err));             // [N][Mp]
-        TRY(tr_im2colT(Xhalo, xS, fmt, B, r, r, C, (size_t)Mp, c.st, c.err));   // [9C][Mp]
-        IgemmDesc d;
-        d.X = yS; d.Wt = xS; d.M = N; d.N = 9 * C; d.Cin = Mp; d.ldx = Mp; d.out_f32 = T.S_dw;
+        d.X = yS; d.Wt = xS; d.M = N; d.N = 9 * C; d.Cin = p.Mp; d.ldx = p.Mp; d.out_f32 = T.S_dw;
         TRY(gemm_wgrad(c, d, fmt));
         TRY(tr_wgrad_permute(T.S_dw, dW, N, C, c.st, c.err));
     } else if (dW) {
-        // f32 and 16-bit, no im2col: both operands transposed in halo pixel order, tap (ky, kx) = the plain GEMM over a shifted view of the ONE transposed halo
-        // image (train.hip: dy_halo_T_kernel).  Margins of r + 3 zero columns on both sides of every row absorb the shifts.
-        c.path |= SOCCDPT_ROUTE_WGRAD_HALOSHIFT;
-        const int rp = r + 2, Mh = B * rp * rp, margin = r + 3;
-        const int ld = (2 * margin + Mh + 127) / 128 * 128;
-        const size_t head = (size_t)(margin + 13) / 8 * 8;     // zeroed elements in FRONT of each copy: the most negative shift reads base - (r + 4)
-        const size_t copy_bytes = ((size_t)(C + 1) * ld + 64 + head) * es;
-        char* const xT = xS + head * es;                       // 16-bit only: two copies, shifted by 0 / 1 element, so that every tap's base stays 4-byte aligned
-        TRY(tr_dy_halo_T(dY, yS, fmt, B, r, N, margin, ld, c.st, c.err));
+        // No im2col: both operands transposed in halo pixel order, tap (ky, kx) = the plain GEMM over a shifted view of the transposed halo image (train.hip:
+        // dy_halo_T_kernel), ONE GEMM with M = N out-channels, N = 9 groups of C rows of the weight operand (one view per tap), K = ld halo-order pixels.
+        // HaloShift (f32 and 16-bit): element shifts into one image, 16-bit a second copy for the odd ones.  X3Shift: pixel rows pitched to rpp and three
+        // copies pre-shifted by -1 / 0 / +1 pixel (x_halo_T_kernel).  The layouts and their contracts: train_plan.h.
+        const bool x3 = p.wgrad == WgradPath::X3Shift;
+        TRY(tr_dy_halo_T(dY, yS, fmt, B, r, N, p.margin, p.ld, c.st, c.err, p.rpp));
         if (!reuse_xt || T.xt_tn_src) {
             T.xt_tn_src = nullptr;
-            for (int cp = 0; cp < (amp ? 2 : 1); ++cp) {
-                char* base = xT + cp * copy_bytes;
-                // headroom + the first row's left margin; every other gap is the zero tail of a row (tr_transpose pads rows up to ld)
-                hipError_t e = hipMemsetAsync(base - head * es, 0, (head + margin) * es, c.st);
+            for (int cp = 0; cp < p.ncopies; ++cp) {
+                char* base = xS + cp * p.copy * es;
+                // the headroom (HaloShift: + the first row's left margin; every other gap is the zero tail of a row) and, X3Shift, the same behind the copy
+                hipError_t e = hipMemsetAsync(base, 0, (p.head + (x3 ? 0 : p.margin)) * es, c.st);
+                if (e == hipSuccess && x3) e = hipMemsetAsync(base + (p.head + (size_t)C * p.ld) * es, 0, p.head * es, c.st);
                 if (e != hipSuccess) { c.err = std::string("conv3_bwd memset: ") + hipGetErrorString(e); return 1; }
-                TRY(tr_transpose(Xhalo, base + (margin - cp) * es, fmt, Mh, C, ld, c.st, c.err));
+                if (x3) TRY(tr_x_halo_T_x3(Xhalo, base + p.head * es, B, r, C, p.margin - (cp - 1), p.ld, p.rpp, c.st, c.err));
+                else TRY(tr_transpose(Xhalo, base + (p.head + p.margin - cp) * es, fmt, p.Mh, C, p.ld, c.st, c.err));
             }
         }
-        {   // ONE GEMM: M = N out-channels, N = 9 groups of C rows of the weight operand (one shifted view per tap), K = ld halo-order pixels
-            IgemmDesc d;
-            d.X = yS; d.Wt = xS; d.M = N; d.N = 9 * C; d.Cin = ld; d.ldx = ld; d.out_f32 = T.S_dw;
-            d.wt_grp_rows = C; d.wt_rp = rp; d.wt_base = (int)head;
-            d.wt_odd = amp ? (int)(copy_bytes / es) - 1 : 0;   // 16-bit: taps with kx != 1 read copy 1 (x[k + 1] at k) so that every base stays 4-byte aligned
-            TRY(gemm_wgrad(c, d, fmt));
-        }
+        IgemmDesc d;
+        d.X = yS; d.Wt = xS; d.M = N; d.N = 9 * C; d.Cin = p.ld; d.ldx = p.ld; d.out_f32 = T.S_dw;
+        d.wt_grp_rows = C; d.wt_base = (int)p.head;
+        if (x3) { d.wt_rp = p.rpp; d.wt_kx = (int)p.copy; }
+        else { d.wt_rp = p.rp; d.wt_odd = amp ? (int)p.copy - 1 : 0; }   // 16-bit: taps with kx != 1 read copy 1 (x[k + 1] at k) so that every base stays 4-byte aligned
+        TRY(gemm_wgrad(c, d, fmt));
         TRY(tr_wgrad_permute(T.S_dw, dW, N, C, c.st, c.err));
     }
     if (db) TRY(tr_colsum(dY, nullptr, db, T.S_col, M, N, 0, c.st, c.err));
@@ -516,8 +493,10 @@ int check_train(Handle& h, int B, const void* ws, size_t ws_bytes, std::string& 
 // ---- one layer backward on caller-supplied tensors (soccdpt_op_train_layer_bwd: tests) ----
 namespace {
 
-// floats of every backward-scratch region one call may touch: what carve() reserves for the whole network, from this layer's shapes, with carve()'s slack terms
-struct LayerGeom { size_t t1 = 0, t2 = 0, halo = 0, wt = 0, dw = 0, slot = 0, arena = 0; };
+// the scratch of one call: the five regions carve() reserves for the whole network sized by this call's plan, merged over the operand formats (so the size does
+// not depend on the amp mode) and kLayerSlackFloats each; the weight slot; the arena of deferred sums
+struct LayerGeom { ScratchNeed s; size_t slot = 0, arena = 0; };
+constexpr size_t kLayerSlackFloats = 64;
 // what survives between calls on one handle: the Tape (Tape::xt_tn_src: whose staged copy S_T2 holds) and what the copy was staged for
 struct LayerState {
     Tape T;
@@ -527,8 +506,6 @@ struct LayerState {
     bool valid = false;
 };
 
-size_t up(size_t v, size_t m) { return (v + m - 1) / m * m; }
-
 int layer_geom(const soccdpt_train_layer_bwd_args& a, LayerGeom& g, std::string& err) {
     auto bad = [&](const char* m) { err = std::string("soccdpt_op_train_layer_bwd: ") + m; return 1; };
     if (a.kind != SOCCDPT_LAYER_LINEAR && a.kind != SOCCDPT_LAYER_CONV3 && a.kind != SOCCDPT_LAYER_CONV_GEN) return bad("kind is SOCCDPT_LAYER_LINEAR, _CONV3 or _CONV_GEN");
@@ -537,22 +514,11 @@ int layer_geom(const soccdpt_train_layer_bwd_args& a, LayerGeom& g, std::string&
     if (!a.dX && !a.dW && !a.db) return bad("no output requested");
     if (a.dX_res && !a.dX) return bad("dX_res without dX");
     if (a.dX && a.N % 32) return bad("dX needs N % 32 == 0 (the dgrad GEMM's K)");
-    const size_t N = a.N, C = a.C;
-    size_t krows;   // K of the TN weight-gradient kernel
-    int taps = 9;
+    int r = a.r;
     if (a.kind == SOCCDPT_LAYER_LINEAR) {
         if (a.M <= 0 || a.M > (1 << 22)) return bad("M must be positive (at most 2^22)");
         if (a.reuse_xt) return bad("reuse_xt is a SOCCDPT_LAYER_CONV3 flag");
-        taps = 1;
-        krows = up((size_t)a.M, 64);
-        const size_t rows = std::max(krows, up((size_t)a.M, 128)) + 128;   // zero rows up to a k-tile; + the rows an M tile / the TN kernel's column tiles may read past the end
-        g.t1 = rows * N + 256;
-        g.t2 = rows * C + 256;
-        g.halo = 64;
-        g.wt = N * C + 256;
-        g.dw = 64;
     } else {
-        int r = a.r;
         if (a.kind == SOCCDPT_LAYER_CONV_GEN) {
             if (a.reuse_xt || a.dX_res) return bad("SOCCDPT_LAYER_CONV_GEN takes no reuse_xt and no dX_res");
             if (a.N % 32 || a.C % 32) return bad("SOCCDPT_LAYER_CONV_GEN needs N, C % 32 == 0");
@@ -564,40 +530,34 @@ int layer_geom(const soccdpt_train_layer_bwd_args& a, LayerGeom& g, std::string&
             r = a.Ho;
         } else if (a.r <= 0 || a.r > 1024) return bad("r must be positive (at most 1024)");
         if (a.B <= 0 || a.B > 64) return bad("B must be positive (at most 64)");
-        const size_t B = a.B, rp = r + 2, Kh = B * rp * rp, Kp = conv3_tn_rows(a.B, r), Mo = B * r * r, Mp = up(Mo, 128);
-        krows = Kp;
-        const size_t rpp = up(rp, 16), ld_x3 = up(2 * (rpp + 16) + B * rp * rpp, 32), head_x3 = rpp + 16;          // conv3_bwd's x3 three-copy layout
-        const size_t ld_hs = up(2 * (size_t)(r + 3) + Kh, 128), head_hs = (size_t)(r + 3 + 13) / 8 * 8;            // ... its halo-shift layout (two copies)
-        size_t x = (2 * (rp + 1) + Kp) * C;                                   // conv3_wgrad_tn: margins + halo pixels padded to a k-tile
-        x = std::max(x, 3 * (C * ld_x3 + 2 * head_x3));
-        x = std::max(x, 9 * C * Mp);                                          // im2col^T
-        x = std::max(x, head_hs + 2 * ((C + 1) * ld_hs + 64 + head_hs));
-        x = std::max(x, (Mo + 128) * 9 * C);                                  // conv_gen_bwd's dcol
-        g.t2 = x + 128 * 9 * C;
-        g.t1 = (N + 128) * std::max(std::max(ld_x3, ld_hs), Mp) + 256;
-        g.halo = (Kp + 64) * N + 256;
-        g.wt = 9 * N * C + 256;
-        g.dw = 9 * N * C + 256;
     }
+    const bool linear = a.kind == SOCCDPT_LAYER_LINEAR;
+    const size_t N = a.N, C = a.C, taps = linear ? 1 : 9;
+    const size_t krows = linear ? roundup((size_t)a.M, 64) : conv3_tn_rows(a.B, r);   // K of the TN weight-gradient kernel
     if (a.stage_weight && a.kind != SOCCDPT_LAYER_CONV_GEN) {   // (conv_gen_bwd's tap-major weights are derived ones: never staged)
         const int64_t sh[4] = {a.N, a.C, 3, 3};
-        if (wt_slot_kind(sh, a.kind == SOCCDPT_LAYER_LINEAR ? 2 : 4) >= 0) g.slot = up(N * C * taps, 64);
+        if (wt_slot_kind(sh, linear ? 2 : 4) >= 0) g.slot = roundup(N * C * taps, 64);
     }
     if (a.defer) {   // the TN kernel's splits: at most 64, at most one per two k-tiles of at least 32 rows, partials within kTrainSkPartFloats (tr_wgrad_tn)
         const size_t smax = std::min<size_t>(64, std::max<size_t>(1, krows / 64));
-        g.arena = std::min(smax * (N * taps * C + up(N, 4)), kTrainSkPartFloats) + 64;
+        g.arena = std::min(smax * (N * taps * C + roundup(N, 4)), kTrainSkPartFloats) + 64;
     }
+    const PlanReq q{a.dX != nullptr, a.dW != nullptr, g.slot != 0, a.defer != 0};
+    for (OpFmt f : {OpFmt::F32, OpFmt::BF16, OpFmt::F16, OpFmt::X3})
+        g.s.merge(linear ? plan_linear((size_t)a.M, a.N, a.C, f, q).need
+                         : a.kind == SOCCDPT_LAYER_CONV3 ? plan_conv3(a.B, a.r, a.N, a.C, f, q).need : plan_conv_gen(a.B, a.Hi, a.Ho, a.N, a.C, a.stride, a.pad, f, q).need);
+    for (auto r : kRegion) g.s.*r += kLayerSlackFloats;
     return 0;
 }
 
 void carve_layer(const LayerGeom& g, TArena& ar, Tape& T) {
-    T.S_T2 = ar.f(g.t2);   // first: at the same place whatever N is (reuse_xt)
+    T.S_cap = g.s;
+    T.S_T2 = ar.f(g.s.t2);   // first: at the same place whatever N is (reuse_xt)
     T.sk_count = reinterpret_cast<unsigned*>(ar.f(kTrainSkCountWords));
-    T.S_T1 = ar.f(g.t1);
-    T.S_halo = ar.f(g.halo);
-    T.S_wt = ar.f(g.wt);
-    T.S_dw = ar.f(g.dw);
-    T.S_dw_n = g.dw;
+    T.S_T1 = ar.f(g.s.t1);
+    T.S_halo = ar.f(g.s.halo);
+    T.S_wt = ar.f(g.s.wt);
+    T.S_dw = ar.f(g.s.dw);
     T.S_col = ar.f((size_t)1 << 20);
     T.WT = g.slot ? ar.f(g.slot) : nullptr;
     T.sk_part = ar.f(kTrainSkPartFloats);
@@ -981,8 +941,8 @@ static int encoder_backward(Ctx& c) {
             const int C0 = a.embed;
             TRY(ln_bwd(c, T.pe_pre, c.W(ENC + "patch_embed.norm.weight"), T.GX, G[0], G[1], M, C0, c.Gd(ENC + "patch_embed.norm.weight"), c.Gd(ENC + "patch_embed.norm.bias")));
             float* dw = c.Gd(ENC + "patch_embed.proj.weight");
-            TRY(linear_bwd(c, G[0], T.patches, T.pe_wpad, M, C0, 64, nullptr, nullptr, dw ? T.S_dw + 65536 : nullptr, c.Gd(ENC + "patch_embed.proj.bias")));
-            if (dw) TRY(tr_pad_cols(T.S_dw + 65536, dw, C0, 64, 48, st, err));
+            TRY(linear_bwd(c, G[0], T.patches, T.pe_wpad, M, C0, 64, nullptr, nullptr, dw ? T.S_dw + kPeGradOffset : nullptr, c.Gd(ENC + "patch_embed.proj.bias")));
+            if (dw) TRY(tr_pad_cols(T.S_dw + kPeGradOffset, dw, C0, 64, 48, st, err));
         }
     }
     return 0;

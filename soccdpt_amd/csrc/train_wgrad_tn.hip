@@ -352,13 +352,6 @@ int tn_flush(TnDefer& d, hipStream_t st, std::string& err) {
     return 0;
 }
 
-// Shapes the kernel takes (the caller falls back to the transposing path otherwise)
-bool tr_wgrad_tn_ok(size_t K, int Nout, int C, int taps) {
-    if (K % 64 != 0 || K < 256) return false;
-    if (taps == 9) return Nout % 128 == 0 && C % 128 == 0;   // a column tile must not straddle two taps
-    return taps == 1 && Nout % 32 == 0 && C % 32 == 0;         // edge tiles are masked (the operands are over-read by up to 127 columns: callers keep them inside scratch)
-}
-
 // out [Nout][taps * C] f32 (tap-major for taps == 9).  A = dY [K][ldA] and B = X [K][ldB] are bf16, fp16 or x3 tensors (fmt); for taps == 9 both are
 // in halo pixel order with pitch rp and B must be readable (finite) from row -(rp + 1) to row K + rp: zero margins.  part: at least
 // splits * Nout * taps * C floats.  Returns the number of splits used through *splits_out.

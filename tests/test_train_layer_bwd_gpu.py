@@ -15,7 +15,8 @@ second call gives the same bits.  test_every_route_was_reached closes the module
 
 Case tables: the shapes of the issue this module answers, with two adjustments the sources require.  conv3 case h (N = 12) cannot take dX -- the dgrad
 GEMM's K is N and the igemm needs K % 32 == 0 -- so it runs dW / db only, and case h2 (1, 5, 32, 48) adds the f32 fallback with all outputs (C % 32 != 0).
-Linear (300, 96, 64) runs "full" with every output and "bare" like the patch embedding: no dX, unstaged W.
+Linear (300, 96, 64) runs "full" with every output and "bare" like the patch embedding: no dX, unstaged W.  conv3 case i (odd r, C % 64 == 0) holds the
+16-bit modes to the im2col^T route the alignment rule of csrc/train_plan.h sends them on; it came after the table below was measured and is held to the same bounds.
 
 Measured on MI355X: the worst relative L2 over every output, slice and variant of a case, per mode, and torch's CPU f32 error on the f32 mode's
 inputs (3 x it stays under the 2e-6 floor everywhere, so every layer that runs in f32 is held to 2e-6).  Bounds: f32 2e-6, x3 2e-6, bf16 / f16
@@ -85,7 +86,8 @@ def _per_fmt(f32, x3, bf16, f16=None, fallback=()):
 ALL_AMP = ("x3", "bf16", "f16")
 
 # conv3: (B, r, N, C).  fmt = the amp mode's when N, C % 32 == 0.  TN: fmt != f32, halo pixels padded to 64 >= 256, N, C % 128 == 0.  Otherwise x3 with
-# C % 64 == 0: three-copy shift; C % 64 != 0 (or x3): im2col^T; else halo-shift.  gemm_wgrad: big = M, N % 128 == 0, K % 64 == 0, >= 8 big tiles, C % 128 == 0;
+# C % 64 == 0: three-copy shift; C % 64 != 0 (or x3, or 16-bit with an odd r: the vertical taps of the halo-shift would sit on 2-byte boundaries): im2col^T;
+# else halo-shift.  gemm_wgrad: big = M, N % 128 == 0, K % 64 == 0, >= 8 big tiles, C % 128 == 0;
 # splits S = min(512 / tiles, nk / 8 (16-bit: nk / 2)), sk_defer with big and S > 1.  gemm (dgrad, f32 / x3 only): split when tiles <= 96 and 9 N / 32 >= 48.
 CONV3 = {
     # 392 halo pixels padded to 448.  f32: ld = 512, 9 big tiles, nk = 16 -> S = 2
@@ -104,6 +106,8 @@ CONV3 = {
     "g": ((2, 6, 256, 256), _per_fmt(_r("haloshift", dsplit=True), _r("x3shift", dsplit=True), _r("haloshift", big=True, skd=True))),
     "h": ((1, 5, 12, 32), _per_fmt(_r("im2colT"), _r("im2colT"), _r("im2colT"), fallback=ALL_AMP)),
     "h2": ((1, 5, 32, 48), _per_fmt(_r("im2colT"), _r("im2colT"), _r("im2colT"), fallback=ALL_AMP)),
+    # odd r with C % 64 == 0: f32 shifts by elements of 4 bytes, x3 pitches the rows to 16; the 16-bit modes take im2col^T (M = 25 -> 128).  No splits anywhere
+    "i": ((1, 5, 32, 64), _per_fmt(_r("haloshift"), _r("x3shift"), _r("im2colT"))),
 }
 CONV3_NO_DX = {"h"}
 CONV3_EXTRA = {"a", "c", "e"}      # also dW-only and dX-only
