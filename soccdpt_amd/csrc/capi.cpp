@@ -11,7 +11,9 @@
 #include "kernels.h"
 #include "occ_eval.h"
 #include "visualise.h"
+#include "batch_targets.h"
 #include "../../include/soccdpt_vis.h"
+#include "../../include/soccdpt_data.h"
 
 using namespace soccdpt;
 
@@ -930,6 +932,24 @@ int soccdpt_vis_half_size(int H, int W, int32_t* Hd, int32_t* Wd) {
 int soccdpt_vis_shrink_half(const uint8_t* dev_src, int B, int H, int W, int swap_rb, uint8_t* dev_dst, void* stream) {
     std::string err;
     if (launch_vis_shrink_half(dev_src, B, H, W, swap_rb, dev_dst, (hipStream_t)stream, err)) return fail(nullptr, "soccdpt_" + err);
+    return 0;
+}
+
+// ---- batch targets (include/soccdpt_data.h; csrc/batch_targets.hip) ----
+int soccdpt_data_targets(const uint8_t* dev_seg, const uint8_t* dev_colors, int C, const void* dev_disp, int disp_dtype, int B, int H, int W, int flip,
+                         float* dev_onehot, int32_t* dev_class_map, float* dev_y_disp, uint64_t* dev_unmatched, void* stream) {
+    std::string err;
+    static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "the unmatched counters are 64-bit");
+    if (launch_data_targets(dev_seg, dev_colors, C, dev_disp, disp_dtype, B, H, W, flip, dev_onehot, dev_class_map, dev_y_disp,
+                            reinterpret_cast<unsigned long long*>(dev_unmatched), (hipStream_t)stream, err))
+        return fail(nullptr, "soccdpt_" + err);
+    return 0;
+}
+
+int soccdpt_data_resize_u8c1(const uint8_t* dev_src, int B, int Hs, int Ws, const int32_t* dev_ytaps, const int32_t* dev_xtaps, int Hd, int Wd,
+                             uint8_t* dev_dst, void* stream) {
+    std::string err;
+    if (launch_data_resize_u8c1(dev_src, B, Hs, Ws, dev_ytaps, dev_xtaps, Hd, Wd, dev_dst, (hipStream_t)stream, err)) return fail(nullptr, "soccdpt_" + err);
     return 0;
 }
 

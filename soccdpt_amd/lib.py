@@ -282,6 +282,21 @@ def _vis_prototypes() -> dict:
 VIS_PROTOTYPES = _vis_prototypes()
 
 
+def _data_prototypes() -> dict:
+    """The same table for include/soccdpt_data.h (the targets of a batch, csrc/batch_targets.hip), in that header's order; tests/test_bdd_dataset_cpu.py
+    holds it against the header.  A third header and a third table: soccdpt_hip.h and its ABI version do not change for these."""
+    vp, ci = ctypes.c_void_p, ctypes.c_int
+    return {
+        "soccdpt_data_targets": (ci, [vp, vp, ci, vp, ci, ci, ci, ci, ci, vp, vp, vp, vp, vp]),
+        "soccdpt_data_resize_u8c1": (ci, [vp, ci, ci, ci, vp, vp, ci, ci, vp, vp]),
+    }
+
+
+DATA_PROTOTYPES = _data_prototypes()
+DATA_U8, DATA_U16, DATA_F32 = 0, 1, 2   # SOCCDPT_DATA_* (include/soccdpt_data.h)
+DATA_MAX_CLASSES = 8
+
+
 def load_library() -> ctypes.CDLL:
     """Load libsoccdpt_hip.so; fail loudly when it has not been built."""
     global _lib
@@ -292,7 +307,7 @@ def load_library() -> ctypes.CDLL:
             f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "(make -C soccdpt_amd/csrc).  The SOccDPT MI355X path has no CPU fallback.")
     L = ctypes.CDLL(LIB_PATH)
-    for table in (PROTOTYPES, VIS_PROTOTYPES):
+    for table in (PROTOTYPES, VIS_PROTOTYPES, DATA_PROTOTYPES):
         for symbol, (restype, argtypes) in table.items():
             fn = getattr(L, symbol)
             fn.restype, fn.argtypes = restype, argtypes
@@ -790,6 +805,46 @@ def op_input_transform_u8(frames: torch.Tensor, Hd: int, Wd: int, mean=(0.5, 0.5
     out = torch.empty((B, 3, Hd, Wd), dtype=torch.float32, device=frames.device)
     m, s = (ctypes.c_double * 3)(*mean), (ctypes.c_double * 3)(*std)
     _call("soccdpt_input_transform_u8", _ptr(frames), B, Hs, Ws, Hd, Wd, m, s, _ptr(out), device=frames.device)
+    return out
+
+
+_DATA_DTYPES = {torch.uint8: DATA_U8, torch.uint16: DATA_U16, torch.float32: DATA_F32}
+
+
+def op_data_targets(seg: torch.Tensor, colors: torch.Tensor, disp: Optional[torch.Tensor] = None, flip: bool = False, want_onehot: bool = True,
+                    want_class_map: bool = False, want_y_disp: Optional[bool] = None, want_unmatched: bool = True) -> dict:
+    """uint8 [B,H,W,3] label frames + uint8 [C,3] class colours (+ [B,H,W] uint8 / uint16 / float32 disparity), all cuda -> the requested ones of
+    onehot f32 [B,C,H,W], class_map i32 [B,H,W], y_disp f32 [B,H,W], unmatched int64 [B] in one launch on the current stream (soccdpt_data_targets)."""
+    assert seg.is_cuda and seg.dtype == torch.uint8 and seg.dim() == 4 and seg.shape[3] == 3, "seg must be a cuda uint8 [B,H,W,3] tensor"
+    assert colors.is_cuda and colors.dtype == torch.uint8 and colors.dim() == 2 and colors.shape[1] == 3, "colors must be a cuda uint8 [C,3] tensor"
+    B, H, W, _ = seg.shape
+    C = colors.shape[0]
+    dev = seg.device
+    dtype = 0
+    if disp is not None:
+        assert disp.is_cuda and tuple(disp.shape) == (B, H, W), "disp must be a cuda [B,H,W] tensor"
+        if disp.dtype not in _DATA_DTYPES:
+            raise TypeError(f"op_data_targets: disparity of dtype {disp.dtype} (uint8, uint16 or float32)")
+        dtype = _DATA_DTYPES[disp.dtype]
+    if want_y_disp is None:
+        want_y_disp = disp is not None
+    out = dict(
+        onehot=torch.empty((B, C, H, W), dtype=torch.float32, device=dev) if want_onehot else None,
+        class_map=torch.empty((B, H, W), dtype=torch.int32, device=dev) if want_class_map else None,
+        y_disp=torch.empty((B, H, W), dtype=torch.float32, device=dev) if want_y_disp else None,
+        unmatched=torch.empty((B,), dtype=torch.int64, device=dev) if want_unmatched else None)     # u64 counts below 2^63
+    _call("soccdpt_data_targets", _ptr(seg), _ptr(colors), C, _ptr(disp), dtype, B, H, W, 1 if flip else 0, _ptr(out["onehot"]), _ptr(out["class_map"]),
+          _ptr(out["y_disp"]), _ptr(out["unmatched"]), device=dev)
+    return out
+
+
+def op_data_resize_u8c1(src: torch.Tensor, Hd: int, Wd: int, ytaps: Optional[torch.Tensor] = None, xtaps: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """uint8 [B,Hs,Ws] (cuda) -> [B,Hd,Wd]: the integer bilinear of soccdpt_vis_resize for one channel (soccdpt_data_resize_u8c1) on the current stream;
+    ytaps / xtaps: int32 [Hd,3] / [Wd,3] device tables of soccdpt_vis_resize_taps (not needed when the size stays)."""
+    assert src.is_cuda and src.dtype == torch.uint8 and src.dim() == 3, "src must be a cuda uint8 [B,H,W] tensor"
+    B = src.shape[0]
+    out = torch.empty((B, int(Hd), int(Wd)), dtype=torch.uint8, device=src.device)
+    _call("soccdpt_data_resize_u8c1", _ptr(src), B, src.shape[1], src.shape[2], _ptr(ytaps), _ptr(xtaps), int(Hd), int(Wd), _ptr(out), device=src.device)
     return out
 
 

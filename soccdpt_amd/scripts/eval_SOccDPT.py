@@ -3,7 +3,11 @@ invoked by `scripts/eval.sh:3-13` as `python -m SOccDPT.scripts.eval_SOccDPT -v 
 same flags, same protocol — load the model through `load_model`, run the FPS loop (50 forwards,
 eval_SOccDPT.py:246-259), then `evaluate_seg` / `evaluate_depth` on the validation subset and print the same lines.
 
-Differences, all forced by what exists on a GPU box: the datasets (and cv2) are not there, so when `--base_path`
+An existing `--base_path` evaluates the reference's ten-frame subset of the Bengaluru recordings under it (`random_split(dataset, [10, n - 10])`
+with generator seed 0, eval_SOccDPT.py:126-135) through soccdpt_amd/datasets/: uint8 frames uploaded, targets and the ground-truth class map built on the
+GPU (csrc/batch_targets.hip).
+
+Differences, all forced by what exists on a GPU box: when `--base_path`
 does not exist the 10-image validation subset is synthetic (seeded frames, ground truth = a smooth perturbation of
 the CPU-free model output, so the numbers are meaningful only as a smoke/regression signal); the PNG visual dumps of
 eval_SOccDPT.py:136-243 are opt-in (`--visuals [DIR]`, default off; see write_visuals); the FPS loop synchronises the stream before stopping the clock (the reference does
@@ -39,6 +43,7 @@ def build_parser() -> argparse.ArgumentParser:
     parser.add_argument("-ld", "--load_depth", default=None, help="Which depth checkpoint to load")
     parser.add_argument("-ls", "--load_seg", default=None, help="Which seg checkpoint to load")
     parser.add_argument("--camera_intrinsics_yaml", default=None, help="calibration file (default: the synthetic 1920x1080 camera of SURVEY.md 8d)")
+    parser.add_argument("--recordings", nargs="*", default=None, help="recording ids under --base_path (default: the reference's six)")
     parser.add_argument("--occupancy", action="store_true", help="also evaluate the semantic occupancy grid on the GPU: 3-D IoU against the ground-truth "
                         "grid of OccupancyProcessor and the mean length of the occupancy point list (prints IOU_3D / OCC_POINTS)")
     parser.add_argument("--occupancy-per-frame", dest="occupancy_per_frame", action="store_true", help="implies --occupancy, with the model built with "
@@ -115,16 +120,39 @@ def synthetic_val_set(net, device, img: int, n: int = 10):
     return out
 
 
+def recorded_val_set(base_path: str, transforms, calib: str, device, n: int = 10, recordings=None, want_class_maps: bool = False):
+    """The reference's evaluation subset of the recordings under base_path (eval_SOccDPT.py:126-135): random_split(dataset, [n, len - n]) with generator
+    seed 0 -> (n items in the datasets' layout, each a batch of one; their ground-truth class maps [1,H,W] int32 from soccdpt_data_targets when asked
+    for, else None; the (recording id, frame index) of every item).  The n frames are decoded concurrently, then assembled one by one."""
+    from ..datasets.bengaluru_driving_dataset import BDD_Depth_Segmentation, get_bdd_dataset, resolve_index, submit_decode
+    full = get_bdd_dataset(BDD_Depth_Segmentation, transforms, base_path, recordings=recordings, settings_doc=calib, device=device)
+    assert len(full) >= n, f"{base_path}: {len(full)} frames, the evaluation subset needs {n}"
+    subset, _ = torch.utils.data.random_split(full, [n, len(full) - n], generator=torch.Generator().manual_seed(0))
+    pending = [submit_decode(subset, [i]) for i in range(n)]
+    items, class_maps = [], []
+    for head, futures in pending:
+        head.keep_class_map = want_class_maps
+        items.append(head.assemble([f.result() for f in futures]))
+        class_maps.append(head.last_class_map)
+    picked = [(leaf.dataset_id, k) for leaf, k in (resolve_index(subset, i) for i in range(n))]
+    return items, (class_maps if want_class_maps else None), picked
+
+
 @torch.no_grad()
 def main(args) -> dict:
     print(f"Model: SOccDPT_V{str(args.version)}_{args.model_type}")
     SOccDPT = SOccDPT_versions[args.version]
     device = torch.device(args.device)
-    _, net_w, net_h = load_transforms(model_type=args.model_type)
-    if "idd" in args.dataset:   # the class count comes from the IDD label tables (datasets/anue_labels.py), dataset code outside the hot path
-        raise NotImplementedError("-dt idd needs the IDD label tables; only the 3-class bdd layout (eval_SOccDPT.py:72-77) is built")
+    transforms, net_w, net_h = load_transforms(model_type=args.model_type)
+    if "idd" in args.dataset:
+        from ..datasets import IDD_UNSUPPORTED
+        raise NotImplementedError(IDD_UNSUPPORTED)
     num_classes = 3
-    calib = args.camera_intrinsics_yaml or write_synth_calib(os.path.join(tempfile.mkdtemp(), "calib.yaml"))
+    real_data = os.path.isdir(os.path.expanduser(args.base_path))
+    calib = args.camera_intrinsics_yaml
+    if calib is None and real_data and os.path.isfile(os.path.join(os.path.expanduser(args.base_path), "calibration", "pocoX3", "calib.yaml")):
+        calib = os.path.join(os.path.expanduser(args.base_path), "calibration", "pocoX3", "calib.yaml")
+    calib = calib or write_synth_calib(os.path.join(tempfile.mkdtemp(), "calib.yaml"))
     model_kwargs = dict(num_classes=num_classes, camera_intrinsics_yaml=calib)
     per_frame = bool(getattr(args, "occupancy_per_frame", False))
     occupancy = bool(getattr(args, "occupancy", False)) or per_frame
@@ -155,10 +183,13 @@ def main(args) -> dict:
     random.seed(0)
     np.random.seed(0)
     torch.manual_seed(0)
-    if os.path.isdir(args.base_path):
-        raise NotImplementedError("dataset readers (cv2, csv) are outside the hot path and not part of this build; "
-                                  "pass a --base_path that does not exist to evaluate on the synthetic subset")
-    dataset = synthetic_val_set(net, device, net_w, n=10)
+    class_maps = None
+    if real_data:
+        transforms.device = device
+        dataset, class_maps, picked = recorded_val_set(os.path.expanduser(args.base_path), transforms, calib, device, n=10,
+                                                       recordings=getattr(args, "recordings", None), want_class_maps=occupancy)
+    else:
+        dataset = synthetic_val_set(net, device, net_w, n=10)
     x = dataset[-1][0].to(device=device, dtype=torch.float32)
 
     frame_count = 50          # eval_SOccDPT.py:246-259
@@ -185,19 +216,21 @@ def main(args) -> dict:
     print(f"A3: {a3:.4f}")
     result = dict(fps=fps, iou=iou, abs_rel=abs_rel, sq_rel=sq_rel, rmse=rmse, rmse_log=rmse_log, a1=a1, a2=a2, a3=a3)
     if occupancy:
-        result.update(evaluate_occupancy_set(net, dataset, device))
+        result.update(evaluate_occupancy_set(net, dataset, device, class_maps=class_maps))
         print(f"IOU_3D: {result['iou_3D']:.4f}")
         print(f"OCC_POINTS: {result['occ_points']:.1f}")
     if getattr(args, "visuals", None):
         result["visuals"] = write_visuals(net, dataset, device, os.path.join(args.visuals, f"{args.model_type}_{args.dataset}_{args.version}"))
         print(f"VISUALS: {result['visuals']}")
+    if real_data:
+        result["frames"] = picked
     print("=" * 20)
     return result
 
 
-def evaluate_occupancy_set(net, dataset, device, point_count_threshold: float = 10.0) -> dict:
+def evaluate_occupancy_set(net, dataset, device, point_count_threshold: float = 10.0, class_maps=None) -> dict:
     """Mean 3-D IoU of the model's occupancy grid (packed bits of each forward) against the ground-truth grid OccupancyProcessor builds from the
-    sample's (y_disp, argmax y_seg), and the mean length of the model's occupancy point list -- everything on the GPU.  A model built with
+    sample's (y_disp, class ids: class_maps[i] when given -- the recordings' class maps from soccdpt_data_targets --, else argmax y_seg), and the mean length of the model's occupancy point list -- everything on the GPU.  A model built with
     occupancy_per_frame=True is scored row by row: frame b's own grid (net.last_occ_frame_bits[b]) against ground-truth row b, and the list length
     is the mean over the frames; otherwise the one union grid of each forward is scored against every ground-truth row of its batch."""
     from ..utils.gt_occupancy import OccupancyProcessor
@@ -206,10 +239,11 @@ def evaluate_occupancy_set(net, dataset, device, point_count_threshold: float = 
                               pc_scale=net.pc_scale, pc_shift=net.pc_shift, point_count_threshold=point_count_threshold, num_classes=net.num_classes,
                               correction_angle=net.correction_angle)
     ious, lengths = [], []
-    for batch in dataset:
+    for i, batch in enumerate(dataset):
         x, y_disp, y_seg = batch[0], batch[3], batch[-1]
         x = x.to(device=device, dtype=torch.float32)
-        gt = proc.process(y_disp.to(device=device, dtype=torch.float32), y_seg.to(device).argmax(dim=1), want_points=False, want_depth=False)
+        seg_class = class_maps[i] if class_maps is not None else y_seg.to(device).argmax(dim=1)
+        gt = proc.process(y_disp.to(device=device, dtype=torch.float32), seg_class, want_points=False, want_depth=False)
         net(x)
         if getattr(net, "occupancy_per_frame", False):
             rows = net.last_occ_frame_bits

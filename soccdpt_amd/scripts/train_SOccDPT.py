@@ -15,9 +15,14 @@ gradient bound and its weight-gradient GEMM is skipped.  `--forward_only` walks 
 the product.
 
 Differences forced by the GPU box: wandb is absent -> the sweep is sampled locally (`method: random` with random.seed(0), `count` runs)
-and logging goes to stdout; the datasets are absent -> when `--base_path` does not exist a seeded synthetic set in the datasets' layout
+and logging goes to stdout; when `--base_path` does not exist a seeded synthetic set in the datasets' layout
 (bengaluru_driving_dataset.py:104-137: `[x, x_raw, mask_disp, y_disp, mask_seg, y_seg]`, ground truth at 1920 x 1080) is used; `--model_type`
 is forwarded into the model (the reference only uses it for the transform and the project name).
+
+An existing `--base_path` with `-dt bdd` trains on the Bengaluru recordings under it (soccdpt_amd/datasets/): `get_bdd_dataset(BDD_Depth_Segmentation, ..)`,
+the reference's dataset_percentage / val_percent splits with the same seeded generators (:206-231) and its batch ranges; the batches come from the
+datasets' fast path (uint8 frames uploaded, targets built on the GPU) through a prefetcher.  The camera is `--camera_intrinsics_yaml` if given, else
+`<base_path>/calibration/pocoX3/calib.yaml` if present, else the synthetic file.  `-dt idd` / `idd+bdd` are refused: more than three classes.
 
     python -m soccdpt_amd.scripts.train_SOccDPT -v 3 -dt bdd -t dpt_swin2_tiny_256 -d cuda:0 \\
         --sweep_json config/SOccDPT_V3_dpt_swin2_tiny_256_Aug_22.json [--forward_only] [--max_steps N]
@@ -123,7 +128,7 @@ class ReduceLROnPlateau:
 
 
 def train_net(SOccDPT_version=3, device="cuda:0", model_type="dpt_swin2_tiny_256", checkpoint_dir="checkpoints", dataset="bdd", base_path="",
-              forward_only=False, max_steps=0, run_id="dummy_run", n_synthetic=12, camera_intrinsics_yaml=None, **cfg):
+              forward_only=False, max_steps=0, run_id="dummy_run", n_synthetic=12, camera_intrinsics_yaml=None, recordings=None, on_batch=None, **cfg):
     p = dict(SWEEP_DEFAULTS)
     unknown = [k for k in cfg if k not in p]
     assert not unknown, f"unknown sweep parameters: {unknown}"
@@ -148,10 +153,22 @@ def train_net(SOccDPT_version=3, device="cuda:0", model_type="dpt_swin2_tiny_256
     torch.use_deterministic_algorithms(True, warn_only=True)
 
     transforms, net_w, net_h = load_transforms(model_type=model_type)
-    if base_path and os.path.isdir(os.path.expanduser(base_path)):
-        raise RuntimeError("dataset readers (cv2 / pandas pipelines of SOccDPT/datasets) are outside the hot-path scope (SURVEY.md 2); "
-                           "point --base_path at a non-existing directory to train on the synthetic set")
-    full = SyntheticDepthSegDataset(n_synthetic, net_w)
+    real_data = bool(base_path) and os.path.isdir(os.path.expanduser(base_path))
+    if real_data:
+        from ..datasets import IDD_UNSUPPORTED
+        from ..datasets.bengaluru_driving_dataset import BDD_Depth_Segmentation, BatchPrefetcher, batch_indices, get_bdd_dataset, resolve_index
+        if "idd" in dataset:
+            raise RuntimeError(IDD_UNSUPPORTED)
+        base = os.path.expanduser(base_path)
+        local_calib = os.path.join(base, "calibration", "pocoX3", "calib.yaml")
+        if camera_intrinsics_yaml is None and os.path.isfile(local_calib):
+            camera_intrinsics_yaml = local_calib
+    calib = camera_intrinsics_yaml or write_synth_calib(os.path.join(tempfile.mkdtemp(), "calib.yaml"))
+    if real_data:
+        transforms.device = device
+        full = get_bdd_dataset(BDD_Depth_Segmentation, transforms, base, recordings=recordings, settings_doc=calib, device=device)
+    else:
+        full = SyntheticDepthSegDataset(n_synthetic, net_w)
     num_classes = 3
     total_use = int(round(len(full) * p["dataset_percentage"]))
     used, _ = torch.utils.data.random_split(full, [total_use, len(full) - total_use], generator=torch.Generator().manual_seed(0))
@@ -168,7 +185,6 @@ def train_net(SOccDPT_version=3, device="cuda:0", model_type="dpt_swin2_tiny_256
         model_kwargs["load_depth"] = p["load_depth"]
         assert p["load_seg"] is False, "V3 does not support loading seg"
         model_kwargs["sigmoid"] = p["sigmoid"]
-    calib = camera_intrinsics_yaml or write_synth_calib(os.path.join(tempfile.mkdtemp(), "calib.yaml"))
     model_kwargs["camera_intrinsics_yaml"] = calib
     if not forward_only:
         from ..lib import PREC_F32
@@ -198,9 +214,15 @@ def train_net(SOccDPT_version=3, device="cuda:0", model_type="dpt_swin2_tiny_256
     for epoch in range(1, p["epochs"] + 1):
         net.train()
         epoch_loss = 0.0
+        lo, hi = sdist.shard_range(batch_size, rank, world) if world > 1 else (0, batch_size)      # this rank's contiguous shard of every batch
+        if real_data:      # the same index ranges as get_batch below, through the datasets' fast path, the next batches prepared while this one trains
+            prefetch = BatchPrefetcher(train_set, (list(batch_indices(i, batch_size))[lo:hi] for i in range(batch_size, len(train_set), batch_size)))
         for batch_index in range(batch_size, len(train_set), batch_size):   # the reference's range (scripts/train_SOccDPT.py:350): a trailing full batch is NOT run
-            if world > 1:      # this rank's contiguous shard of the batch
-                lo, hi = sdist.shard_range(batch_size, rank, world)
+            if real_data:
+                x, _, mask_disp, y_disp, mask_seg, y_seg = next(prefetch)
+                if on_batch is not None:      # opt-in: the (recording id, frame index) of the items this step consumed
+                    on_batch([(leaf.dataset_id, k) for leaf, k in (resolve_index(train_set, i) for i in list(batch_indices(batch_index, batch_size))[lo:hi])])
+            elif world > 1:
                 x, _, mask_disp, y_disp, mask_seg, y_seg = get_batch(train_set, batch_index - batch_size + hi, hi - lo)
             else:
                 x, _, mask_disp, y_disp, mask_seg, y_seg = get_batch(train_set, batch_index, batch_size)
@@ -271,6 +293,9 @@ def build_parser() -> argparse.ArgumentParser:
     parser.add_argument("--sweep_json", required=True, help="Path to checkpoint to sweep json")
     parser.add_argument("--forward_only", action="store_true", help="walk the schedule with the eval-mode forward + criterion only (no backward / optimizer)")
     parser.add_argument("--max_steps", default=0, type=int, help="stop every run after this many batches (0 = all)")
+    parser.add_argument("--camera_intrinsics_yaml", default=None, help="calibration file (default: <base_path>/calibration/pocoX3/calib.yaml if present, "
+                        "else the synthetic 1920x1080 camera)")
+    parser.add_argument("--recordings", nargs="*", default=None, help="recording ids under --base_path (default: the reference's six)")
     return parser
 
 
@@ -284,7 +309,8 @@ def main(args):
         print(f"run {i}: {run}")
         out.append(train_net(SOccDPT_version=args.version, device=args.device, model_type=args.model_type, checkpoint_dir=args.checkpoint_dir,
                              dataset=args.dataset, base_path=args.base_path, forward_only=args.forward_only, max_steps=args.max_steps,
-                             run_id=f"local_run_{i}", **run))
+                             run_id=f"local_run_{i}", camera_intrinsics_yaml=getattr(args, "camera_intrinsics_yaml", None),
+                             recordings=getattr(args, "recordings", None), **run))
     return out
 
 

@@ -3,8 +3,10 @@
 numpy on the host (2 M points, ~0.5 s per 1080p frame); here a batch of disparity frames and class maps that already sit in HBM
 becomes depth, the rotated point cloud and the thresholded counting grid in two launches (csrc/gt_occ.hip).
 
-What stays on the host, outside this boundary: decoding images, `rgb_seg_to_class` (colour -> class id LUT, :10-25) and the
-colourised point cloud used for visualisation (:491-521).  The `occupancy_points` list of transform_points_to_occupancy_grid_vect (:339-355)
+What stays on the host, outside this boundary: decoding images (soccdpt_amd/datasets/bdd_helper.py) and the colourised point cloud used for
+visualisation (:491-521).  `rgb_seg_to_class` (colour -> class id, :10-25) is a kernel too: the `class_map` output of soccdpt_data_targets
+(csrc/batch_targets.hip, include/soccdpt_data.h) builds `seg_class` from the uint8 label frames of a batch, which is where `eval_SOccDPT --occupancy`
+takes it from on real recordings.  The `occupancy_points` list of transform_points_to_occupancy_grid_vect (:339-355)
 is available on request (`want_occupancy_points`, csrc/occ_eval.hip); the un-rotation / un-shift / un-scale that process_frame applies to it
 afterwards for drawing (:500-528, numpy matmuls on the host) is not."""
 from __future__ import annotations
