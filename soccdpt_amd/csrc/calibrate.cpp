@@ -112,14 +112,12 @@ size_t calib_scratch_bytes(Handle& h, int B) {
 // sum over four tensors of (2 i + 1) x (64-bit sum of the tensor's f32 bit patterns): tells one checkpoint from another (not a hash of everything:
 // four tensors spread over decoder, heads and encoder).  -> 0 and *out, 1 when one of the tensors is not bound, < 0 on error
 int calib_fingerprint(Handle& h, unsigned long long* tmp, hipStream_t st, unsigned long long* out, std::string& err) {
-    const bool hyb = h.arch.hybrid;
-    const char* keys[4] = {"depth_net.scratch.layer1_rn.weight", "depth_net.scratch.refinenet1.out_conv.weight", "seg_head.0.weight",
-                           hyb ? "depth_net.pretrained.model.blocks.0.attn.qkv.weight" : "depth_net.pretrained.model.layers.0.blocks.0.attn.qkv.weight"};
+    const ModelP& P = h.params;
+    const PRef refs[4] = {P.layer_rn[0], P.refine[0].out_conv.w, P.seg.c0_w, h.arch.hybrid ? P.hy.vit[0].qkv.w : P.swin.blk[0][0].qkv_w};
     if (hipMemsetAsync(tmp, 0, 8, st) != hipSuccess) { err = "soccdpt_prepare: fingerprint memset failed"; return -1; }
     for (int i = 0; i < 4; ++i) {
-        auto it = h.index.find(keys[i]);
-        if (it == h.index.end() || !h.weights[it->second].ptr) return 1;
-        const WeightSlot& w = h.weights[it->second];
+        if (!h.W(refs[i])) return 1;   // not bound, or a backbone without this tensor
+        const WeightSlot& w = h.weights[refs[i].i];
         if (launch_calib_fingerprint(w.ptr, w.numel(), (unsigned long long)(2 * i + 1), tmp, st, err)) return -1;
     }
     unsigned long long got = 0;

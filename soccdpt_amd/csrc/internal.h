@@ -10,45 +10,9 @@
 
 #include "../../include/soccdpt_hip.h"
 #include "launch.h"
+#include "params.h"
 
 namespace soccdpt {
-
-// Swin-V2 geometry (timm swinv2_* as created by /root/reference/SOccDPT/model/backbones/swin2.py:15-30;
-// hooks from /root/reference/SOccDPT/model/dpt.py:67-72).
-struct Arch {
-    int img = 256, patch = 4, embed = 96, window = 16;
-    int depths[4] = {2, 2, 6, 2};
-    int heads[4] = {3, 6, 12, 24};
-    int pretrained_window[4] = {0, 0, 0, 0};
-    int hooks[4] = {1, 1, 5, 1};
-    // ViT-hybrid (vitb_rn50_384; /root/reference/SOccDPT/model/backbones/vit.py:147-258, model/blocks.py:103-112): ResNetV2 (3, 4, 9) stem +
-    // 12 ViT-B blocks; the reassembled pyramid is [256, 512, 768, 768] channels at 1/4, 1/8, 1/16, 1/32 of the input
-    bool hybrid = false;
-    int vit_depth = 12, vit_heads = 12, vit_dim = 768, stem_ch = 64;
-    int rn_layers[3] = {3, 4, 9};
-    int vit_hooks[2] = {8, 11};
-    int grid() const { return img / patch; }
-    int dim(int s) const { return embed << s; }
-    int res(int s) const { return grid() >> s; }
-    // feature pyramid handed to scratch.layerN_rn (level l = 0 finest)
-    int fdim(int l) const { return hybrid ? (l == 0 ? 256 : l == 1 ? 512 : 768) : dim(l); }
-    int fres(int l) const { return hybrid ? (img / 4) >> l : res(l); }
-    int out_res() const { return img; }   // network output resolution (4 * fres(0))
-    int ws(int s) const { return res(s) < window ? res(s) : window; }
-    int shift(int s, int j) const { return (j % 2 == 0 || res(s) <= window) ? 0 : window / 2; }
-};
-
-struct WeightSlot {
-    std::string key;
-    std::vector<int64_t> shape;
-    const float* ptr = nullptr;
-    float* grad = nullptr;   // gradient destination of the training step (soccdpt_bind_grad); nullptr = frozen
-    size_t numel() const {
-        size_t n = 1;
-        for (auto d : shape) n *= (size_t)d;
-        return n;
-    }
-};
 
 struct Prepared;  // model.cpp
 
@@ -118,8 +82,11 @@ struct Handle {
     int prec_source = -1;   // soccdpt_prec_map_source: -1 unknown (not prepared), 0 shipped map on its own weights, 1 calibrated, 2 edited, 3 shipped map on other weights
     unsigned long long calib_fp = 0;   // fingerprint (calibrate.h) of the weights the calibrated map (prec_source 1) was derived on
     bool calib_fp_valid = false;
-    std::vector<WeightSlot> weights;
-    std::unordered_map<std::string, int> index;
+    std::vector<WeightSlot> weights;                      // params.h build_params: the consumed state-dict tensors in registration order
+    ModelP params;                                        // ... and the typed references every launch site reads them through
+    const float* W(PRef r) const { return r.i < 0 ? nullptr : weights[r.i].ptr; }
+    float* G(PRef r) const { return r.i < 0 ? nullptr : weights[r.i].grad; }
+    std::unordered_map<std::string, int> index;           // key -> slot, for the by-name entry points only (soccdpt_bind_weight, soccdpt_bind_grad)
     size_t prepared_bytes = 0;
     Prepared* prep = nullptr;
     bool is_prepared = false;

@@ -18,55 +18,35 @@
 
 namespace soccdpt {
 
+// What soccdpt_prepare PRODUCES (the bound tensors themselves are read through Handle::params at launch time): operand-format copies of the GEMM /
+// convolution weights -- or the bound f32 tensors in SOCCDPT_PREC_F32 -- and the small derived tensors.
 struct BlockW {
-    const void *qkv_w, *proj_w, *fc1_w, *fc2_w;  // bf16 copies, or the bound f32 tensors in SOCCDPT_PREC_F32
-    float *qkv_bias, *scale, *table, *bias_acc;
-    const float *proj_b, *n1_g, *n1_b, *fc1_b, *fc2_b, *n2_g, *n2_b;
-};
-struct MergeW {
-    const void* red_w;
-    const float *g, *b;
-};
-struct RcuW {
-    const void *w1, *w2;
-    const float *b1, *b2;
-};
-// ViT-hybrid encoder (dpt_hybrid_384): ResNetV2 bottleneck, ViT block
-struct RnBlockW {
-    const void *ds_w = nullptr, *c1_w = nullptr, *c2_w = nullptr, *c3_w = nullptr;   // weight-standardised, tap-major, operand type
-    const float *ds_g = nullptr, *ds_b = nullptr, *n1_g = nullptr, *n1_b = nullptr, *n2_g = nullptr, *n2_b = nullptr, *n3_g = nullptr, *n3_b = nullptr;
-    int cin = 0, cout = 0, mid = 0, stride = 1;
-    bool proj = false;
-};
-struct VitBlockW {
     const void *qkv_w, *proj_w, *fc1_w, *fc2_w;
-    const float *qkv_b, *proj_b, *fc1_b, *fc2_b, *n1_g, *n1_b, *n2_g, *n2_b;
+    float *qkv_bias, *scale, *table, *bias_acc;
 };
+struct RcuW { const void *w1, *w2; };
+// ViT-hybrid encoder (dpt_hybrid_384): ResNetV2 bottleneck (weight-standardised, tap-major), ViT block
+struct RnBlockW { const void *ds_w = nullptr, *c1_w = nullptr, *c2_w = nullptr, *c3_w = nullptr; };
+struct VitBlockW { const void *qkv_w, *proj_w, *fc1_w, *fc2_w; };
 struct HybridW {
     const void* stem_w = nullptr;          // [64][160]
-    const float *stem_g = nullptr, *stem_b = nullptr;
-    std::vector<std::vector<RnBlockW>> stages;
+    std::vector<RnBlockW> rn;              // as HybridP::rn
     const void* pe_w = nullptr;
-    const float *pe_b = nullptr, *cls = nullptr;
     float* pos = nullptr;                  // position embedding at the run-time grid ([1 + g*g][768])
     std::vector<VitBlockW> blocks;
     const void *ro_w[2] = {nullptr, nullptr}, *pp_w[2] = {nullptr, nullptr}, *pp4_w = nullptr;
-    const float *ro_b[2] = {nullptr, nullptr}, *pp_b[2] = {nullptr, nullptr}, *pp4_b = nullptr;
 };
 struct Prepared {
     HybridW hy;
-    std::vector<std::vector<BlockW>> blocks;  // [stage][block]
-    MergeW merge[3];
+    std::vector<BlockW> blocks[4];  // [stage][block]
+    const void* merge_w[3];
     const void* layer_rn[4];
     RcuW rcu[4][2];  // [refinenet-1][unit-1]
     const void* oc_w[4];
-    const float* oc_b[4];
     const void *d0_w, *d2_w;
-    const float *d0_b, *d2_b, *d4_w;
     float d4_b = 0.f;
     const void* s0_w;
     float *bn_scale, *bn_shift;
-    const float *s4_w, *s4_b;
     float* patch_wT = nullptr;  // [48][128]
     std::unordered_set<const void*> x2w;   // prepared weights of x2w groups (x3 pairs read beside fp16 activations): gemm() picks the x2w tiles for them
 };
@@ -123,60 +103,48 @@ struct Arena {
     }
 };
 
-void add_w(Handle& h, const std::string& key, std::vector<int64_t> shape) {
-    h.index[key] = (int)h.weights.size();
-    h.weights.push_back(WeightSlot{key, std::move(shape), nullptr});
-}
-
-const std::string ENC = "depth_net.pretrained.model.";
-const std::string HYB = "depth_net.pretrained.";
-std::string rnblk(int s, int j) { return ENC + "patch_embed.backbone.stages." + std::to_string(s) + ".blocks." + std::to_string(j) + "."; }
-std::string vitblk(int i) { return ENC + "blocks." + std::to_string(i) + "."; }
-const std::string SCR = "depth_net.scratch.";
-
-std::string blk(int s, int j) { return ENC + "layers." + std::to_string(s) + ".blocks." + std::to_string(j) + "."; }
-
 // Walks the prepared-weights arena; with base == nullptr it only measures.  When `st` runs
 // (base != nullptr) it also launches the conversion kernels.
-int lay_out(Handle& h, Arena& ar, Prepared* P, hipStream_t st, std::string& err) {
+int lay_out(Handle& h, Arena& ar, Prepared& P, hipStream_t st, std::string& err) {
     const Arch& a = h.arch;
+    const ModelP& M = h.params;
     const bool run = ar.base != nullptr;
-    auto W = [&](const std::string& key) -> const float* { return h.weights[h.index.at(key)].ptr; };
+    auto W = [&](PRef r) { return h.W(r); };
     // SOCCDPT_PREC_MIXED: every weight copy gets 4 bytes per element whatever its group's format, so the arena layout (and
     // soccdpt_prepared_bytes) does not depend on the precision map
     const bool MIX = h.cfg.precision == SOCCDPT_PREC_MIXED;
     // WEIGHT format code of a group: 0 bf16, 1 fp16, 2 f32, 3 x3 (half16.h); + 0x100 when the group is x2w (x3 weights beside fp16 activations)
     auto GF = [&](const std::string& g) { return group_x2w(h, g) ? (3 | 0x100) : group_fmt(h, g); };
-    auto reg = [&](int& fmt, const void* p) { if ((fmt & 0x100) && run && P && p) P->x2w.insert(p); };
     static const char kNoCopy = 0;  // non-null placeholder while measuring
-    auto cvt = [&](const std::string& key, size_t n, int fmt_) -> const void* {
-        const int fmt = fmt_ & 0xff;
-        if (fmt == 2) return run ? static_cast<const void*>(W(key)) : static_cast<const void*>(&kNoCopy);  // [N][K] f32 as bound
-        bf16_t* p = (fmt == 3 || MIX) ? reinterpret_cast<bf16_t*>(ar.take<float>(n)) : ar.take<bf16_t>(n);
-        if (run && launch_cvt_bf16(W(key), p, n, fmt, st, err)) return nullptr;
-        reg(fmt_, p);
-        return run ? static_cast<const void*>(p) : static_cast<const void*>(&kNoCopy);
+    // what a copy helper hands back: the copy (registered as an x2w weight where its group is one), the placeholder while measuring, nullptr after a failed launch
+    auto made = [&](int fmt_, const void* p, int launch_rc) -> const void* {
+        if (!run) return &kNoCopy;
+        if (launch_rc) return nullptr;
+        if ((fmt_ & 0x100) && p) P.x2w.insert(p);
+        return p;
     };
-    auto convw = [&](const std::string& key, int Cout, int Cin, const float* scale, int fmt_) -> const void* {
+    auto cvt = [&](PRef w, size_t n, int fmt_) -> const void* {
+        const int fmt = fmt_ & 0xff;
+        if (fmt == 2) return run ? static_cast<const void*>(W(w)) : static_cast<const void*>(&kNoCopy);  // [N][K] f32 as bound
+        bf16_t* p = (fmt == 3 || MIX) ? reinterpret_cast<bf16_t*>(ar.take<float>(n)) : ar.take<bf16_t>(n);
+        return made(fmt_, p, run ? launch_cvt_bf16(W(w), p, n, fmt, st, err) : 0);
+    };
+    auto convw = [&](PRef w, int Cout, int Cin, const float* scale, int fmt_) -> const void* {
         const int fmt = fmt_ & 0xff;
         const size_t n = (size_t)Cout * Cin * 9;
         void* p = (fmt >= 2 || MIX) ? static_cast<void*>(ar.take<float>(n)) : static_cast<void*>(ar.take<bf16_t>(n));
-        if (run && launch_conv_w(W(key), scale, p, fmt == 2 ? 1 : 0, fmt == 2 ? 0 : fmt, Cout, Cin, st, err)) return nullptr;
-        reg(fmt_, p);
-        return run ? static_cast<const void*>(p) : static_cast<const void*>(&kNoCopy);
+        return made(fmt_, p, run ? launch_conv_w(W(w), scale, p, fmt == 2 ? 1 : 0, fmt == 2 ? 0 : fmt, Cout, Cin, st, err) : 0);
     };
     // weight-standardised convolution weight (timm StdConv2dSame, eps 1e-8), tap-major [Cout][Kpad]; fmt = operand format code of hybrid.hip
-    auto wsw = [&](const std::string& key, int Cout, int Cin, int k, int Kpad, int fmt_) -> const void* {
+    auto wsw = [&](PRef w, int Cout, int Cin, int k, int Kpad, int fmt_) -> const void* {
         const int fmt = fmt_ & 0xff;
         const size_t n = (size_t)Cout * Kpad;
         void* p = (fmt >= 2 || MIX) ? static_cast<void*>(ar.take<float>(n)) : static_cast<void*>(ar.take<bf16_t>(n));
-        if (run && launch_ws_conv_w(W(key), p, fmt, Cout, Cin, k, Kpad, 1e-8f, st, err)) return nullptr;
-        reg(fmt_, p);
-        return run ? static_cast<const void*>(p) : static_cast<const void*>(&kNoCopy);
+        return made(fmt_, p, run ? launch_ws_conv_w(W(w), p, fmt, Cout, Cin, k, Kpad, 1e-8f, st, err) : 0);
     };
     if (a.hybrid) {
-        HybridW hw;
-        const std::string bb = ENC + "patch_embed.backbone.";
+        const HybridP& Y = M.hy;
+        HybridW& hw = P.hy;
         {   // The stem runs f32-grade in EVERY precision mode: weight standardisation makes each filter zero-mean, so the large DC level
             // of the reference's un-normalised inputs (pixel values up to 509, SURVEY.md 3.4: no /255) cancels exactly in f32 and only the
             // small pixel-to-pixel variation survives -- 16-bit operand rounding of either side (absolute error ~1 on the pixels, a
@@ -184,159 +152,99 @@ int lay_out(Handle& h, Arena& ar, Prepared* P, hipStream_t st, std::string& err)
             // Exact f32 operands in SOCCDPT_PREC_F32; x3 pairs (22 bits: the DC level cancels to 1e-4 absolute) everywhere else since round 5 --
             // the f32 MFMA ran this one GEMM at 27 TFLOP/s, 103 us of the 4.7 ms forward.
             float* p = ar.take<float>((size_t)a.stem_ch * 160);
-            if (run && launch_ws_conv_w(W(bb + "stem.conv.weight"), p, stem_fmt(h), a.stem_ch, 3, 7, 160, 1e-8f, st, err)) return 1;
-            hw.stem_w = run ? static_cast<const void*>(p) : static_cast<const void*>(&kNoCopy);
+            hw.stem_w = made(0, p, run ? launch_ws_conv_w(W(Y.stem_w), p, stem_fmt(h), a.stem_ch, 3, 7, 160, 1e-8f, st, err) : 0);
+            if (!hw.stem_w) return 1;
         }
-        if (run) { if (!hw.stem_w) return 1; hw.stem_g = W(bb + "stem.norm.weight"); hw.stem_b = W(bb + "stem.norm.bias"); }
-        int prev = a.stem_ch;
-        hw.stages.assign(3, {});
-        for (int s3 = 0; s3 < 3; ++s3) {
-            const int cout = 256 << s3, mid = cout / 4;
-            for (int j = 0; j < a.rn_layers[s3]; ++j) {
-                const std::string b = rnblk(s3, j);
-                RnBlockW bw;
-                const int f1 = GF(grn(s3, 1)), f2 = GF(grn(s3, 2)), f3 = GF(grn(s3, 3));
-                bw.cin = prev; bw.cout = cout; bw.mid = mid; bw.proj = (j == 0); bw.stride = (j == 0 && s3 > 0) ? 2 : 1;
-                if (bw.proj) bw.ds_w = wsw(b + "downsample.conv.weight", cout, prev, 1, prev, f1);   // reads the block input like conv1: same group
-                bw.c1_w = wsw(b + "conv1.weight", mid, prev, 1, prev, f1);
-                bw.c2_w = wsw(b + "conv2.weight", mid, mid, 3, 9 * mid, f2);
-                bw.c3_w = wsw(b + "conv3.weight", cout, mid, 1, mid, f3);
-                if (run) {
-                    if ((bw.proj && !bw.ds_w) || !bw.c1_w || !bw.c2_w || !bw.c3_w) return 1;
-                    if (bw.proj) { bw.ds_g = W(b + "downsample.norm.weight"); bw.ds_b = W(b + "downsample.norm.bias"); }
-                    bw.n1_g = W(b + "norm1.weight"); bw.n1_b = W(b + "norm1.bias");
-                    bw.n2_g = W(b + "norm2.weight"); bw.n2_b = W(b + "norm2.bias");
-                    bw.n3_g = W(b + "norm3.weight"); bw.n3_b = W(b + "norm3.bias");
-                }
-                hw.stages[s3].push_back(bw);
-                prev = cout;
-            }
+        int s3 = 0, left = a.rn_layers[0];
+        for (const RnBlockP& b : Y.rn) {
+            RnBlockW bw;
+            const int f1 = GF(grn(s3, 1)), f2 = GF(grn(s3, 2)), f3 = GF(grn(s3, 3));
+            if (b.proj) bw.ds_w = wsw(b.ds_w, b.cout, b.cin, 1, b.cin, f1);   // reads the block input like conv1: same group
+            bw.c1_w = wsw(b.c1_w, b.mid, b.cin, 1, b.cin, f1);
+            bw.c2_w = wsw(b.c2_w, b.mid, b.mid, 3, 9 * b.mid, f2);
+            bw.c3_w = wsw(b.c3_w, b.cout, b.mid, 1, b.mid, f3);
+            if ((b.proj && !bw.ds_w) || !bw.c1_w || !bw.c2_w || !bw.c3_w) return 1;
+            hw.rn.push_back(bw);
+            if (--left == 0 && s3 < 2) left = a.rn_layers[++s3];
         }
         const int E = a.vit_dim, g = a.grid();
-        hw.pe_w = cvt(ENC + "patch_embed.proj.weight", (size_t)E * prev, GF("pe"));
+        hw.pe_w = cvt(Y.pe.w, (size_t)E * Y.rn.back().cout, GF("pe"));
         hw.pos = ar.take<float>((size_t)(1 + g * g) * E);
-        if (run) {
-            if (!hw.pe_w) return 1;
-            hw.pe_b = W(ENC + "patch_embed.proj.bias");
-            hw.cls = W(ENC + "cls_token");
-            const int g0 = 24;   // vit_base_resnet50_384: pos_embed is [1, 1 + 24*24, 768]
-            if (launch_pos_embed_resize(W(ENC + "pos_embed"), hw.pos, g0, g, E, st, err)) return 1;
-        }
+        if (!hw.pe_w) return 1;
+        const int g0 = 24;   // vit_base_resnet50_384: pos_embed is [1, 1 + 24*24, 768]
+        if (run && launch_pos_embed_resize(W(Y.pos), hw.pos, g0, g, E, st, err)) return 1;
         for (int i = 0; i < a.vit_depth; ++i) {
-            const std::string b = vitblk(i);
+            const VitBlockP& b = Y.vit[i];
             VitBlockW vb{};
-            vb.qkv_w = cvt(b + "attn.qkv.weight", (size_t)3 * E * E, GF(gvit(i, "qkv")));
-            vb.proj_w = cvt(b + "attn.proj.weight", (size_t)E * E, GF(gvit(i, "proj")));
-            vb.fc1_w = cvt(b + "mlp.fc1.weight", (size_t)4 * E * E, GF(gvit(i, "fc1")));
-            vb.fc2_w = cvt(b + "mlp.fc2.weight", (size_t)4 * E * E, GF(gvit(i, "fc2")));
-            if (run) {
-                if (!vb.qkv_w || !vb.proj_w || !vb.fc1_w || !vb.fc2_w) return 1;
-                vb.qkv_b = W(b + "attn.qkv.bias"); vb.proj_b = W(b + "attn.proj.bias");
-                vb.fc1_b = W(b + "mlp.fc1.bias"); vb.fc2_b = W(b + "mlp.fc2.bias");
-                vb.n1_g = W(b + "norm1.weight"); vb.n1_b = W(b + "norm1.bias");
-                vb.n2_g = W(b + "norm2.weight"); vb.n2_b = W(b + "norm2.bias");
-            }
+            vb.qkv_w = cvt(b.qkv.w, (size_t)3 * E * E, GF(gvit(i, "qkv")));
+            vb.proj_w = cvt(b.proj.w, (size_t)E * E, GF(gvit(i, "proj")));
+            vb.fc1_w = cvt(b.fc1.w, (size_t)4 * E * E, GF(gvit(i, "fc1")));
+            vb.fc2_w = cvt(b.fc2.w, (size_t)4 * E * E, GF(gvit(i, "fc2")));
+            if (!vb.qkv_w || !vb.proj_w || !vb.fc1_w || !vb.fc2_w) return 1;
             hw.blocks.push_back(vb);
         }
         for (int k = 0; k < 2; ++k) {
-            const std::string ap = HYB + "act_postprocess" + std::to_string(3 + k) + ".";
-            hw.ro_w[k] = cvt(ap + "0.project.0.weight", (size_t)E * 2 * E, GF(gname("ro", k)));
-            hw.pp_w[k] = cvt(ap + "3.weight", (size_t)a.fdim(2 + k) * E, GF(gname("ro", k)));
-            if (run) {
-                if (!hw.ro_w[k] || !hw.pp_w[k]) return 1;
-                hw.ro_b[k] = W(ap + "0.project.0.bias");
-                hw.pp_b[k] = W(ap + "3.bias");
-            }
+            hw.ro_w[k] = cvt(Y.ro[k].project.w, (size_t)E * 2 * E, GF(gname("ro", k)));
+            hw.pp_w[k] = cvt(Y.ro[k].conv.w, (size_t)a.fdim(2 + k) * E, GF(gname("ro", k)));
+            if (!hw.ro_w[k] || !hw.pp_w[k]) return 1;
         }
-        hw.pp4_w = convw(HYB + "act_postprocess4.4.weight", a.fdim(3), a.fdim(3), nullptr, GF("pp4"));
-        if (run) {
-            if (!hw.pp4_w) return 1;
-            hw.pp4_b = W(HYB + "act_postprocess4.4.bias");
-            P->hy = hw;
-        }
+        hw.pp4_w = convw(Y.pp4.w, a.fdim(3), a.fdim(3), nullptr, GF("pp4"));
+        if (!hw.pp4_w) return 1;
     } else {
-        float* pw = ar.take<float>(48 * 128);
-        if (run) {
-            if (launch_patch_w(W(ENC + "patch_embed.proj.weight"), pw, a.embed, st, err)) return 1;
-            P->patch_wT = pw;
-        }
+        P.patch_wT = ar.take<float>(48 * 128);
+        if (run && launch_patch_w(W(M.swin.patch.w), P.patch_wT, a.embed, st, err)) return 1;
     }
-    if (run) P->blocks.assign(4, {});
     for (int s = 0; s < 4 && !a.hybrid; ++s) {
         const int C = a.dim(s), H = a.heads[s], ws = a.ws(s);
         for (int j = 0; j < a.depths[s]; ++j) {
-            const std::string b = blk(s, j);
+            const SwinBlockP& b = M.swin.blk[s][j];
             BlockW bw{};
-            bw.qkv_w = cvt(b + "attn.qkv.weight", (size_t)3 * C * C, GF(gblk(s, j, "qkv")));
-            bw.proj_w = cvt(b + "attn.proj.weight", (size_t)C * C, GF(gblk(s, j, "proj")));
-            bw.fc1_w = cvt(b + "mlp.fc1.weight", (size_t)4 * C * C, GF(gblk(s, j, "fc1")));
-            bw.fc2_w = cvt(b + "mlp.fc2.weight", (size_t)4 * C * C, GF(gblk(s, j, "fc2")));
+            bw.qkv_w = cvt(b.qkv_w, (size_t)3 * C * C, GF(gblk(s, j, "qkv")));
+            bw.proj_w = cvt(b.proj.w, (size_t)C * C, GF(gblk(s, j, "proj")));
+            bw.fc1_w = cvt(b.fc1.w, (size_t)4 * C * C, GF(gblk(s, j, "fc1")));
+            bw.fc2_w = cvt(b.fc2.w, (size_t)4 * C * C, GF(gblk(s, j, "fc2")));
             bw.qkv_bias = ar.take<float>(3 * C);
             bw.scale = ar.take<float>(H);
             bw.table = ar.take<float>((size_t)(2 * ws - 1) * (2 * ws - 1) * H);
             bw.bias_acc = ar.take<float>(attn_bias_elems(ws, H));
+            if (!bw.qkv_w || !bw.proj_w || !bw.fc1_w || !bw.fc2_w) return 1;
             if (run) {
-                if (!bw.qkv_w || !bw.proj_w || !bw.fc1_w || !bw.fc2_w) return 1;
-                if (launch_qkv_bias(W(b + "attn.q_bias"), W(b + "attn.v_bias"), bw.qkv_bias, C, st, err)) return 1;
-                if (launch_logit_scale(W(b + "attn.logit_scale"), bw.scale, H, st, err)) return 1;
-                if (launch_cpb_table(W(b + "attn.cpb_mlp.0.weight"), W(b + "attn.cpb_mlp.0.bias"), W(b + "attn.cpb_mlp.2.weight"), bw.table,
-                                     ws, a.pretrained_window[s], H, st, err))
-                    return 1;
+                if (launch_qkv_bias(W(b.q_bias), W(b.v_bias), bw.qkv_bias, C, st, err)) return 1;
+                if (launch_logit_scale(W(b.logit_scale), bw.scale, H, st, err)) return 1;
+                if (launch_cpb_table(W(b.cpb0_w), W(b.cpb0_b), W(b.cpb2_w), bw.table, ws, a.pretrained_window[s], H, st, err)) return 1;
                 if (launch_attn_bias(bw.table, bw.bias_acc, ws, H, st, err)) return 1;
-                bw.proj_b = W(b + "attn.proj.bias");
-                bw.n1_g = W(b + "norm1.weight"); bw.n1_b = W(b + "norm1.bias");
-                bw.fc1_b = W(b + "mlp.fc1.bias"); bw.fc2_b = W(b + "mlp.fc2.bias");
-                bw.n2_g = W(b + "norm2.weight"); bw.n2_b = W(b + "norm2.bias");
-                P->blocks[s].push_back(bw);
             }
+            P.blocks[s].push_back(bw);
         }
         if (s < 3) {
-            const std::string d = ENC + "layers." + std::to_string(s) + ".downsample.";
-            const void* rw = cvt(d + "reduction.weight", (size_t)8 * C * C, GF(gname("merge", s)));
-            if (run) {
-                if (!rw) return 1;
-                P->merge[s] = MergeW{rw, W(d + "norm.weight"), W(d + "norm.bias")};
-            }
+            P.merge_w[s] = cvt(M.swin.merge[s].red_w, (size_t)8 * C * C, GF(gname("merge", s)));
+            if (!P.merge_w[s]) return 1;
         }
     }
     const int F = h.cfg.features;
     for (int i = 0; i < 4; ++i) {
-        const void* p = convw(SCR + "layer" + std::to_string(i + 1) + "_rn.weight", F, a.fdim(i), nullptr, GF(gname("lrn", i)));
-        if (run) { if (!p) return 1; P->layer_rn[i] = p; }
+        P.layer_rn[i] = convw(M.layer_rn[i], F, a.fdim(i), nullptr, GF(gname("lrn", i)));
+        if (!P.layer_rn[i]) return 1;
     }
-    for (int r = 1; r <= 4; ++r) {
-        const std::string b = SCR + "refinenet" + std::to_string(r) + ".";
-        const void* ocw = cvt(b + "out_conv.weight", (size_t)F * F, GF(gname("oc", r - 1)));
-        if (run) { if (!ocw) return 1; P->oc_w[r - 1] = ocw; P->oc_b[r - 1] = W(b + "out_conv.bias"); }
-        for (int u = 1; u <= 2; ++u) {
-            if (r == 4 && u == 1) continue;
-            const std::string ub = b + "resConfUnit" + std::to_string(u) + ".";
-            const void* w1 = convw(ub + "conv1.weight", F, F, nullptr, GF(gname("ref", r - 1)));
-            const void* w2 = convw(ub + "conv2.weight", F, F, nullptr, GF(gname("ref", r - 1)));
-            if (run) {
-                if (!w1 || !w2) return 1;
-                P->rcu[r - 1][u - 1] = RcuW{w1, w2, W(ub + "conv1.bias"), W(ub + "conv2.bias")};
-            }
+    for (int l = 0; l < 4; ++l) {
+        const RefineP& R = M.refine[l];
+        P.oc_w[l] = cvt(R.out_conv.w, (size_t)F * F, GF(gname("oc", l)));
+        if (!P.oc_w[l]) return 1;
+        for (int u = 0; u < 2; ++u) {
+            if (l == 3 && u == 0) continue;
+            const void* w1 = convw(R.rcu[u].c1.w, F, F, nullptr, GF(gname("ref", l)));
+            const void* w2 = convw(R.rcu[u].c2.w, F, F, nullptr, GF(gname("ref", l)));
+            if (!w1 || !w2) return 1;
+            P.rcu[l][u] = RcuW{w1, w2};
         }
     }
-    {
-        const void* d0 = convw(SCR + "output_conv.0.weight", F / 2, F, nullptr, GF("head"));
-        const void* d2 = convw(SCR + "output_conv.2.weight", 32, F / 2, nullptr, GF("head.d2"));
-        float* bscale = ar.take<float>(F);
-        float* bshift = ar.take<float>(F);
-        if (run && launch_bn_fold(W("seg_head.1.weight"), W("seg_head.1.bias"), W("seg_head.1.running_mean"), W("seg_head.1.running_var"),
-                                  bscale, bshift, F, st, err))
-            return 1;
-        const void* s0 = convw("seg_head.0.weight", F, F, bscale, GF("head"));
-        if (run) {
-            if (!d0 || !d2 || !s0) return 1;
-            P->d0_w = d0; P->d2_w = d2; P->s0_w = s0;
-            P->d0_b = W(SCR + "output_conv.0.bias"); P->d2_b = W(SCR + "output_conv.2.bias");
-            P->d4_w = W(SCR + "output_conv.4.weight");
-            P->bn_scale = bscale; P->bn_shift = bshift;
-            P->s4_w = W("seg_head.4.weight"); P->s4_b = W("seg_head.4.bias");
-        }
-    }
+    P.d0_w = convw(M.depth.c0.w, F / 2, F, nullptr, GF("head"));
+    P.d2_w = convw(M.depth.c2.w, 32, F / 2, nullptr, GF("head.d2"));
+    P.bn_scale = ar.take<float>(F);
+    P.bn_shift = ar.take<float>(F);
+    if (run && launch_bn_fold(W(M.seg.bn.g), W(M.seg.bn.b), W(M.seg.bn_mean), W(M.seg.bn_var), P.bn_scale, P.bn_shift, F, st, err)) return 1;
+    P.s0_w = convw(M.seg.c0_w, F, F, P.bn_scale, GF("head"));
+    if (!P.d0_w || !P.d2_w || !P.s0_w) return 1;
     return 0;
 }
 
@@ -435,145 +343,20 @@ static void carve_all(const Handle& h, int B, Arena& ar, std::vector<Workspace>&
 static void chunk_range(int B, int n, int i, int& lo, int& hi);
 
 int model_init(Handle& h, std::string& err) {
-    Arch a;
-    if (h.cfg.backbone == SOCCDPT_BACKBONE_SWIN2T16_256) {
-        // defaults
-    } else if (h.cfg.backbone == SOCCDPT_BACKBONE_SWIN2B24_384) {
-        a.img = 384; a.embed = 128; a.window = 24;
-        int d[4] = {2, 2, 18, 2}, hd[4] = {4, 8, 16, 32}, pw[4] = {12, 12, 12, 6}, hk[4] = {1, 1, 17, 1};
-        for (int i = 0; i < 4; ++i) { a.depths[i] = d[i]; a.heads[i] = hd[i]; a.pretrained_window[i] = pw[i]; a.hooks[i] = hk[i]; }
-    } else if (h.cfg.backbone == SOCCDPT_BACKBONE_VITB_RN50_384) {
-        a.hybrid = true; a.img = 384; a.patch = 16;
-    } else {
-        err = "soccdpt_create: backbone not implemented on the HIP path";
-        return 1;
+    switch (h.cfg.backbone) {
+        case SOCCDPT_BACKBONE_SWIN2T16_256: h.arch = arch_swin2t16_256(); break;
+        case SOCCDPT_BACKBONE_SWIN2B24_384: h.arch = arch_swin2b24_384(); break;
+        case SOCCDPT_BACKBONE_VITB_RN50_384: h.arch = arch_vitb_rn50_384(); break;
+        default: err = "soccdpt_create: backbone not implemented on the HIP path"; return 1;
     }
-    h.arch = a;
-    h.img = a.img;
+    h.img = h.arch.img;
     if (h.cfg.precision == SOCCDPT_PREC_MIXED) model_prec_default(h);
-    const int64_t C0 = a.embed;
-    if (a.hybrid) {
-        // timm 0.6.12 vit_base_resnet50_384 + the reference's act_postprocess3/4 (backbones/vit.py:183-229): SURVEY.md 8a row a4-H
-        const int64_t E = a.vit_dim, NT = (int64_t)a.grid() * a.grid() + 1;
-        add_w(h, ENC + "cls_token", {1, 1, E});
-        add_w(h, ENC + "pos_embed", {1, NT, E});
-        const std::string bb = ENC + "patch_embed.backbone.";
-        add_w(h, bb + "stem.conv.weight", {a.stem_ch, 3, 7, 7});
-        add_w(h, bb + "stem.norm.weight", {a.stem_ch});
-        add_w(h, bb + "stem.norm.bias", {a.stem_ch});
-        int64_t prev = a.stem_ch;
-        for (int s3 = 0; s3 < 3; ++s3) {
-            const int64_t cout = 256 << s3, mid = cout / 4;
-            for (int j = 0; j < a.rn_layers[s3]; ++j) {
-                const std::string b = rnblk(s3, j);
-                if (j == 0) {
-                    add_w(h, b + "downsample.conv.weight", {cout, prev, 1, 1});
-                    add_w(h, b + "downsample.norm.weight", {cout});
-                    add_w(h, b + "downsample.norm.bias", {cout});
-                }
-                add_w(h, b + "conv1.weight", {mid, prev, 1, 1});
-                add_w(h, b + "norm1.weight", {mid});
-                add_w(h, b + "norm1.bias", {mid});
-                add_w(h, b + "conv2.weight", {mid, mid, 3, 3});
-                add_w(h, b + "norm2.weight", {mid});
-                add_w(h, b + "norm2.bias", {mid});
-                add_w(h, b + "conv3.weight", {cout, mid, 1, 1});
-                add_w(h, b + "norm3.weight", {cout});
-                add_w(h, b + "norm3.bias", {cout});
-                prev = cout;
-            }
-        }
-        add_w(h, ENC + "patch_embed.proj.weight", {E, prev, 1, 1});
-        add_w(h, ENC + "patch_embed.proj.bias", {E});
-        for (int i = 0; i < a.vit_depth; ++i) {
-            const std::string b = vitblk(i);
-            add_w(h, b + "norm1.weight", {E});
-            add_w(h, b + "norm1.bias", {E});
-            add_w(h, b + "attn.qkv.weight", {3 * E, E});
-            add_w(h, b + "attn.qkv.bias", {3 * E});
-            add_w(h, b + "attn.proj.weight", {E, E});
-            add_w(h, b + "attn.proj.bias", {E});
-            add_w(h, b + "norm2.weight", {E});
-            add_w(h, b + "norm2.bias", {E});
-            add_w(h, b + "mlp.fc1.weight", {4 * E, E});
-            add_w(h, b + "mlp.fc1.bias", {4 * E});
-            add_w(h, b + "mlp.fc2.weight", {E, 4 * E});
-            add_w(h, b + "mlp.fc2.bias", {E});
-        }
-        for (int k = 0; k < 2; ++k) {
-            const std::string ap = HYB + "act_postprocess" + std::to_string(3 + k) + ".";
-            add_w(h, ap + "0.project.0.weight", {E, 2 * E});
-            add_w(h, ap + "0.project.0.bias", {E});
-            add_w(h, ap + "3.weight", {a.fdim(2 + k), E, 1, 1});
-            add_w(h, ap + "3.bias", {a.fdim(2 + k)});
-        }
-        add_w(h, HYB + "act_postprocess4.4.weight", {a.fdim(3), a.fdim(3), 3, 3});
-        add_w(h, HYB + "act_postprocess4.4.bias", {a.fdim(3)});
-    } else {
-    add_w(h, ENC + "patch_embed.proj.weight", {C0, 3, a.patch, a.patch});
-    add_w(h, ENC + "patch_embed.proj.bias", {C0});
-    add_w(h, ENC + "patch_embed.norm.weight", {C0});
-    add_w(h, ENC + "patch_embed.norm.bias", {C0});
-    }
-    for (int s = 0; s < 4 && !a.hybrid; ++s) {
-        const int64_t C = a.dim(s), H = a.heads[s];
-        for (int j = 0; j < a.depths[s]; ++j) {
-            const std::string b = blk(s, j);
-            add_w(h, b + "attn.logit_scale", {H, 1, 1});
-            add_w(h, b + "attn.q_bias", {C});
-            add_w(h, b + "attn.v_bias", {C});
-            add_w(h, b + "attn.cpb_mlp.0.weight", {512, 2});
-            add_w(h, b + "attn.cpb_mlp.0.bias", {512});
-            add_w(h, b + "attn.cpb_mlp.2.weight", {H, 512});
-            add_w(h, b + "attn.qkv.weight", {3 * C, C});
-            add_w(h, b + "attn.proj.weight", {C, C});
-            add_w(h, b + "attn.proj.bias", {C});
-            add_w(h, b + "norm1.weight", {C});
-            add_w(h, b + "norm1.bias", {C});
-            add_w(h, b + "mlp.fc1.weight", {4 * C, C});
-            add_w(h, b + "mlp.fc1.bias", {4 * C});
-            add_w(h, b + "mlp.fc2.weight", {C, 4 * C});
-            add_w(h, b + "mlp.fc2.bias", {C});
-            add_w(h, b + "norm2.weight", {C});
-            add_w(h, b + "norm2.bias", {C});
-        }
-        if (s < 3) {
-            const std::string d = ENC + "layers." + std::to_string(s) + ".downsample.";
-            add_w(h, d + "reduction.weight", {2 * C, 4 * C});
-            add_w(h, d + "norm.weight", {2 * C});
-            add_w(h, d + "norm.bias", {2 * C});
-        }
-    }
-    const int64_t F = h.cfg.features;
-    for (int i = 0; i < 4; ++i) add_w(h, SCR + "layer" + std::to_string(i + 1) + "_rn.weight", {F, a.fdim(i), 3, 3});
-    for (int r = 1; r <= 4; ++r) {
-        const std::string b = SCR + "refinenet" + std::to_string(r) + ".";
-        add_w(h, b + "out_conv.weight", {F, F, 1, 1});
-        add_w(h, b + "out_conv.bias", {F});
-        for (int u = 1; u <= 2; ++u) {
-            if (r == 4 && u == 1) continue;  // refinenet4 gets one input: its RCU1 never runs (model/dpt.py:163-165)
-            for (int c = 1; c <= 2; ++c) {
-                add_w(h, b + "resConfUnit" + std::to_string(u) + ".conv" + std::to_string(c) + ".weight", {F, F, 3, 3});
-                add_w(h, b + "resConfUnit" + std::to_string(u) + ".conv" + std::to_string(c) + ".bias", {F});
-            }
-        }
-    }
-    add_w(h, SCR + "output_conv.0.weight", {F / 2, F, 3, 3});
-    add_w(h, SCR + "output_conv.0.bias", {F / 2});
-    add_w(h, SCR + "output_conv.2.weight", {32, F / 2, 3, 3});
-    add_w(h, SCR + "output_conv.2.bias", {32});
-    add_w(h, SCR + "output_conv.4.weight", {1, 32, 1, 1});
-    add_w(h, SCR + "output_conv.4.bias", {1});
-    add_w(h, "seg_head.0.weight", {F, F, 3, 3});
-    add_w(h, "seg_head.1.weight", {F});
-    add_w(h, "seg_head.1.bias", {F});
-    add_w(h, "seg_head.1.running_mean", {F});
-    add_w(h, "seg_head.1.running_var", {F});
-    add_w(h, "seg_head.4.weight", {h.cfg.num_classes, F, 1, 1});
-    add_w(h, "seg_head.4.bias", {h.cfg.num_classes});
+    h.params = build_params(h.arch, h.cfg.features, h.cfg.num_classes, h.weights);
+    for (size_t i = 0; i < h.weights.size(); ++i) h.index[h.weights[i].key] = (int)i;
 
     Arena measure(nullptr, 0);
-    if (lay_out(h, measure, nullptr, nullptr, err)) return 1;
+    Prepared unused;
+    if (lay_out(h, measure, unused, nullptr, err)) return 1;
     h.prepared_bytes = measure.off + 256;
     return 0;
 }
@@ -730,9 +513,9 @@ int model_prepare(Handle& h, void* prepared, size_t bytes, hipStream_t st, std::
     delete h.prep;
     h.prep = new Prepared();
     Arena ar(prepared, bytes);
-    if (lay_out(h, ar, h.prep, st, err)) return 1;
+    if (lay_out(h, ar, *h.prep, st, err)) return 1;
     // the depth head's last bias is a kernel argument: fetch the scalar (prepare may synchronise)
-    hipError_t e = hipMemcpyAsync(&h.prep->d4_b, h.weights[h.index.at(SCR + "output_conv.4.bias")].ptr, sizeof(float), hipMemcpyDeviceToHost, st);
+    hipError_t e = hipMemcpyAsync(&h.prep->d4_b, h.W(h.params.depth.c4.b), sizeof(float), hipMemcpyDeviceToHost, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
     if (e != hipSuccess) { err = std::string("soccdpt_prepare: ") + hipGetErrorString(e); return 1; }
     h.is_prepared = true;
@@ -787,12 +570,14 @@ static int run_chunk(Handle& h, const Workspace& w, const float* x, int B, float
         }
         PROF(pname, igemm_flops(d), 0.0); return launch_igemm(d, st, err); };
 
-    auto W = [&](const std::string& key) -> const float* { return h.weights[h.index.at(key)].ptr; };
+    const ModelP& MP = h.params;
+    auto W = [&](PRef r) { return h.W(r); };   // a bound tensor, as bound when this launch sequence is issued (a rebind asks for a new prepare first)
     if (a.hybrid) {
         // ---------------- ViT-hybrid encoder (dpt_hybrid_384) ----------------
         // forward_flex (/root/reference/SOccDPT/model/backbones/vit.py:44-85) + forward_adapted_unflatten (backbones/utils.py:84-133);
         // launch for launch what oracle/soccdpt_ref.py hybrid_encoder() states.
         const HybridW& Y = P.hy;
+        const HybridP& YP = MP.hy;
         const int S = a.img, H1 = S / 2, H2 = S / 4;
         // Per-group operand formats (uniform modes: one code everywhere): "rn.s<k>.c<1|2|3>" (a ResNetV2 stage's bottlenecks share the zero-halo images
         // of their 3x3 inputs, so a convolution TYPE of a stage is the unit), "pe", the ViT blocks' "vit.b<i>.qkv" / ".proj" / ".fc1" / ".fc2", "ro<k>", "pp4".
@@ -833,61 +618,62 @@ static int run_chunk(Handle& h, const Workspace& w, const float* x, int B, float
             RUN(gemm(d, stem_fmt(h)));
             { PROF("gn_relu_maxpool", 0.0, (double)B * H1 * H1 * a.stem_ch * 4.0 * 2.25 + (double)B * H2 * H2 * a.stem_ch * (fRn[0][0] >= 2 ? 4 : 2));
               RUN(launch_gn_finish(w.hy_part[0], w.hy_stats[0], B, H1 * H1 / bm_slot[0], 32, H1 * H1, a.stem_ch / 32, 1e-5f, st, err));
-              RUN(launch_gn_relu_maxpool(w.hy_r[0], w.hy_stats[0], Y.stem_g, Y.stem_b, w.hy_xop, fRn[0][0], B, H1, a.stem_ch, a.stem_ch / 32, st, err)); }
+              RUN(launch_gn_relu_maxpool(w.hy_r[0], w.hy_stats[0], W(YP.stem_n.g), W(YP.stem_n.b), w.hy_xop, fRn[0][0], B, H1, a.stem_ch, a.stem_ch / 32, st, err)); }
         }
-        int rcur = H2;
+        int rcur = H2, bi = 0;
         for (int s3 = 0; s3 < 3; ++s3) {
-            const int nb = (int)Y.stages[s3].size();
+            const int nb = a.rn_layers[s3];
             const int f1 = fRn[s3][0], f2 = fRn[s3][1], f3 = fRn[s3][2];
-            for (int j = 0; j < nb; ++j) {
-                const RnBlockW& bw = Y.stages[s3][j];
-                const int rin = rcur, rout = rin / bw.stride;
+            for (int j = 0; j < nb; ++j, ++bi) {
+                const RnBlockW& bw = Y.rn[bi];
+                const RnBlockP& bp = YP.rn[bi];
+                const int rin = rcur, rout = rin / bp.stride;
                 const int Min = B * rin * rin, Mout = B * rout * rout;
                 const int fnext = j + 1 < nb ? f1 : (s3 < 2 ? fRn[s3 + 1][0] : fPe);   // who reads this bottleneck's output
                 // zero-halo image for this (resolution, width): see carve()
                 const int ti = s3 == 0 ? 0 : (s3 == 1 ? (j == 0 ? 1 : 2) : (j == 0 ? 3 : 4));
-                if (bw.proj) {   // shortcut: GN(1x1 stride-s conv)
+                if (bp.proj) {   // shortcut: GN(1x1 stride-s conv)
                     IgemmDesc d;
-                    d.X = w.hy_xop; d.Wt = bw.ds_w; d.M = Mout; d.N = bw.cout; d.Cin = bw.cin; d.out_f32 = w.hy_r[3];
-                    if (bw.stride == 1) { d.ldx = bw.cin; }
-                    else { d.gather1 = 1; d.stride = bw.stride; d.pad = 0; d.in_halo = 0; d.Hi = rin; d.Wi = rin; d.H = rout; d.W = rout; }
-                    with_stats(d, 3, bw.cout, rout * rout);
+                    d.X = w.hy_xop; d.Wt = bw.ds_w; d.M = Mout; d.N = bp.cout; d.Cin = bp.cin; d.out_f32 = w.hy_r[3];
+                    if (bp.stride == 1) { d.ldx = bp.cin; }
+                    else { d.gather1 = 1; d.stride = bp.stride; d.pad = 0; d.in_halo = 0; d.Hi = rin; d.Wi = rin; d.H = rout; d.W = rout; }
+                    with_stats(d, 3, bp.cout, rout * rout);
                     RUN(gemm(d, f1));
                 }
                 {   // conv1 1x1 -> GN + ReLU -> halo image
                     IgemmDesc d;
-                    d.X = w.hy_xop; d.Wt = bw.c1_w; d.M = Min; d.N = bw.mid; d.Cin = bw.cin; d.ldx = bw.cin; d.out_f32 = w.hy_r[0];
-                    with_stats(d, 0, bw.mid, rin * rin);
+                    d.X = w.hy_xop; d.Wt = bw.c1_w; d.M = Min; d.N = bp.mid; d.Cin = bp.cin; d.ldx = bp.cin; d.out_f32 = w.hy_r[0];
+                    with_stats(d, 0, bp.mid, rin * rin);
                     RUN(gemm(d, f1));
                     GnApplyArgs g;
-                    g.raw = w.hy_r[0]; g.stats = w.hy_stats[0]; g.gamma = bw.n1_g; g.beta = bw.n1_b; g.out_halo = w.hy_t1[ti];
-                    g.M = (size_t)Min; g.HW = rin * rin; g.W = rin; g.C = bw.mid; g.cpg = bw.mid / 32;
+                    g.raw = w.hy_r[0]; g.stats = w.hy_stats[0]; g.gamma = W(bp.n1.g); g.beta = W(bp.n1.b); g.out_halo = w.hy_t1[ti];
+                    g.M = (size_t)Min; g.HW = rin * rin; g.W = rin; g.C = bp.mid; g.cpg = bp.mid / 32;
                     RUN(gn(g, f2, 0));   // written in the format of its reader, the 3x3
                 }
                 {   // conv2 3x3 (stride on this conv; 'SAME': pad 1 at stride 1, the extra pixel right / bottom at stride 2) -> GN + ReLU
                     IgemmDesc d;
-                    d.X = w.hy_t1[ti]; d.Wt = bw.c2_w; d.M = Mout; d.N = bw.mid; d.Cin = bw.mid; d.taps = 9; d.H = rout; d.W = rout; d.Hi = rin; d.Wi = rin;
-                    d.stride = bw.stride; d.pad = bw.stride == 1 ? 1 : 0; d.in_halo = 1; d.out_f32 = w.hy_r[1];
-                    with_stats(d, 1, bw.mid, rout * rout);
+                    d.X = w.hy_t1[ti]; d.Wt = bw.c2_w; d.M = Mout; d.N = bp.mid; d.Cin = bp.mid; d.taps = 9; d.H = rout; d.W = rout; d.Hi = rin; d.Wi = rin;
+                    d.stride = bp.stride; d.pad = bp.stride == 1 ? 1 : 0; d.in_halo = 1; d.out_f32 = w.hy_r[1];
+                    with_stats(d, 1, bp.mid, rout * rout);
                     RUN(gemm(d, f2));
                     GnApplyArgs g;
-                    g.raw = w.hy_r[1]; g.stats = w.hy_stats[1]; g.gamma = bw.n2_g; g.beta = bw.n2_b; g.out_op = w.hy_t2;
-                    g.M = (size_t)Mout; g.HW = rout * rout; g.W = rout; g.C = bw.mid; g.cpg = bw.mid / 32;
+                    g.raw = w.hy_r[1]; g.stats = w.hy_stats[1]; g.gamma = W(bp.n2.g); g.beta = W(bp.n2.b); g.out_op = w.hy_t2;
+                    g.M = (size_t)Mout; g.HW = rout * rout; g.W = rout; g.C = bp.mid; g.cpg = bp.mid / 32;
                     RUN(gn(g, f3, 1));
                 }
                 {   // conv3 1x1 -> GN, + shortcut, ReLU: the new residual stream (f32) and its operand copy; hooked stages also as a halo image
                     IgemmDesc d;
-                    d.X = w.hy_t2; d.Wt = bw.c3_w; d.M = Mout; d.N = bw.cout; d.Cin = bw.mid; d.ldx = bw.mid; d.out_f32 = w.hy_r[2];
-                    with_stats(d, 2, bw.cout, rout * rout);
+                    d.X = w.hy_t2; d.Wt = bw.c3_w; d.M = Mout; d.N = bp.cout; d.Cin = bp.mid; d.ldx = bp.mid; d.out_f32 = w.hy_r[2];
+                    with_stats(d, 2, bp.cout, rout * rout);
                     RUN(gemm(d, f3));
                     GnApplyArgs g;
-                    g.raw = w.hy_r[2]; g.stats = w.hy_stats[2]; g.gamma = bw.n3_g; g.beta = bw.n3_b;
-                    if (bw.proj) { g.raw2 = w.hy_r[3]; g.stats2 = w.hy_stats[3]; g.gamma2 = bw.ds_g; g.beta2 = bw.ds_b; }
+                    g.raw = w.hy_r[2]; g.stats = w.hy_stats[2]; g.gamma = W(bp.n3.g); g.beta = W(bp.n3.b);
+                    if (bp.proj) { g.raw2 = w.hy_r[3]; g.stats2 = w.hy_stats[3]; g.gamma2 = W(bp.ds_n.g); g.beta2 = W(bp.ds_n.b); }
                     else g.res = w.hy_xf;
                     g.out_f32 = w.hy_xf; g.out_op = w.hy_xop;
                     if (j == nb - 1 && s3 < 2) { g.out_halo = w.feat[s3]; g.halo_mode = GF(gname("lrn", s3)); }   // hooks on patch_embed.backbone.stages[0], [1] (vit.py:164-167)
-                    g.M = (size_t)Mout; g.HW = rout * rout; g.W = rout; g.C = bw.cout; g.cpg = bw.cout / 32;
-                    RUN(gn(g, fnext, 2, bw.proj ? 3 : -1));
+                    g.M = (size_t)Mout; g.HW = rout * rout; g.W = rout; g.C = bp.cout; g.cpg = bp.cout / 32;
+                    RUN(gn(g, fnext, 2, bp.proj ? 3 : -1));
                 }
                 rcur = rout;
             }
@@ -896,18 +682,19 @@ static int run_chunk(Handle& h, const Workspace& w, const float* x, int B, float
         const int E = a.vit_dim, G = a.grid(), NT = G * G + 1, Mt = B * NT, Mp = B * G * G;
         {
             IgemmDesc d;
-            d.X = w.hy_xop; d.Wt = Y.pe_w; d.M = Mp; d.N = E; d.Cin = 1024; d.ldx = 1024; d.bias = Y.pe_b; d.out_f32 = w.vt_y;
+            d.X = w.hy_xop; d.Wt = Y.pe_w; d.M = Mp; d.N = E; d.Cin = 1024; d.ldx = 1024; d.bias = W(YP.pe.b); d.out_f32 = w.vt_y;
             RUN(gemm(d, fPe));
             const int f0 = GF(gvit(0, "qkv"));
             PROF("vit_tokens_ln", 0.0, (double)Mt * E * (8.0 + 4.0 + (f0 >= 2 ? 4 : 2)));
-            RUN(launch_vit_tokens_ln(w.vt_y, Y.cls, Y.pos, w.vt_xf, Y.blocks[0].n1_g, Y.blocks[0].n1_b, w.vt_xb, f0, B, NT, E, 1e-6f, st, err));
+            RUN(launch_vit_tokens_ln(w.vt_y, W(YP.cls), Y.pos, w.vt_xf, W(YP.vit[0].n1.g), W(YP.vit[0].n1.b), w.vt_xb, f0, B, NT, E, 1e-6f, st, err));
         }
         for (int i = 0; i < a.vit_depth; ++i) {
             const VitBlockW& vb = Y.blocks[i];
+            const VitBlockP& vp = YP.vit[i];
             // one format per GEMM: fq (qkv), fp (proj), f1 (fc1), f2 (fc2); each producer writes for its reader
             const int fq = GF(gvit(i, "qkv")), fp = GF(gvit(i, "proj")), f1 = GF(gvit(i, "fc1")), f2 = GF(gvit(i, "fc2"));
             IgemmDesc d;
-            d.X = w.vt_xb; d.Wt = vb.qkv_w; d.M = Mt; d.N = 3 * E; d.Cin = E; d.ldx = E; d.bias = vb.qkv_b;
+            d.X = w.vt_xb; d.Wt = vb.qkv_w; d.M = Mt; d.N = 3 * E; d.Cin = E; d.ldx = E; d.bias = W(vp.qkv.b);
             if (MIX) { d.out_op = w.vt_qkv; d.out_fmt = 1; }   // mixed mode: fp16 q, k, v for the fp16 attention kernel
             else to_plain(d, w.vt_qkv, fq);
             RUN(gemm(d, fq));
@@ -915,39 +702,39 @@ static int run_chunk(Handle& h, const Workspace& w, const float* x, int B, float
               const int aprec = MIX ? SOCCDPT_PREC_F16 : h.cfg.precision;
               RUN(launch_vit_attention(w.vt_qkv, w.vt_attn, aprec, B, NT, a.vit_heads, st, err, (MIX && fp == 3) ? 1 : 0)); }
             d = IgemmDesc();
-            d.X = w.vt_attn; d.Wt = vb.proj_w; d.M = Mt; d.N = E; d.Cin = E; d.ldx = E; d.bias = vb.proj_b; d.res1 = w.vt_xf; d.out_f32 = w.vt_xf;   // x += attn (in place)
+            d.X = w.vt_attn; d.Wt = vb.proj_w; d.M = Mt; d.N = E; d.Cin = E; d.ldx = E; d.bias = W(vp.proj.b); d.res1 = w.vt_xf; d.out_f32 = w.vt_xf;   // x += attn (in place)
             RUN(gemm(d, fp));
             { PROF("ln_rows", 0.0, (double)Mt * E * (4.0 + (f1 >= 2 ? 4 : 2)));
-              RUN(launch_ln_rows(w.vt_xf, vb.n2_g, vb.n2_b, w.vt_xb, f1, Mt, E, 1e-6f, st, err)); }
+              RUN(launch_ln_rows(w.vt_xf, W(vp.n2.g), W(vp.n2.b), w.vt_xb, f1, Mt, E, 1e-6f, st, err)); }
             d = IgemmDesc();
-            d.X = w.vt_xb; d.Wt = vb.fc1_w; d.M = Mt; d.N = 4 * E; d.Cin = E; d.ldx = E; d.bias = vb.fc1_b; d.act = ACT_GELU; d.out_op = w.vt_h; d.out_fmt = MIX ? f2 : -1;
+            d.X = w.vt_xb; d.Wt = vb.fc1_w; d.M = Mt; d.N = 4 * E; d.Cin = E; d.ldx = E; d.bias = W(vp.fc1.b); d.act = ACT_GELU; d.out_op = w.vt_h; d.out_fmt = MIX ? f2 : -1;
             RUN(gemm(d, f1));
             d = IgemmDesc();
-            d.X = w.vt_h; d.Wt = vb.fc2_w; d.M = Mt; d.N = E; d.Cin = 4 * E; d.ldx = 4 * E; d.bias = vb.fc2_b; d.res1 = w.vt_xf; d.out_f32 = w.vt_xf;      // x += mlp (in place)
+            d.X = w.vt_h; d.Wt = vb.fc2_w; d.M = Mt; d.N = E; d.Cin = 4 * E; d.ldx = 4 * E; d.bias = W(vp.fc2.b); d.res1 = w.vt_xf; d.out_f32 = w.vt_xf;      // x += mlp (in place)
             for (int k = 0; k < 2; ++k)
                 if (i == a.vit_hooks[k]) { d.out_op = w.vt_tok[k]; d.out_fmt = MIX ? GF(gname("ro", k)) : -1; }   // hooks on blocks[8], blocks[11] (vit.py:168-171): operand copy for the readout GEMM
             RUN(gemm(d, f2));
             if (i + 1 < a.vit_depth) {
                 const int fn = GF(gvit(i + 1, "qkv"));
                 PROF("ln_rows", 0.0, (double)Mt * E * (4.0 + (fn >= 2 ? 4 : 2)));
-                RUN(launch_ln_rows(w.vt_xf, Y.blocks[i + 1].n1_g, Y.blocks[i + 1].n1_b, w.vt_xb, fn, Mt, E, 1e-6f, st, err));
+                RUN(launch_ln_rows(w.vt_xf, W(YP.vit[i + 1].n1.g), W(YP.vit[i + 1].n1.b), w.vt_xb, fn, Mt, E, 1e-6f, st, err));
             }
         }
         // ---- act_postprocess3 / 4: ProjectReadout (cat(token, cls) @ W^T + GELU, the cat never materialises) -> Conv1x1 (-> Conv3x3 / 2) ----
         for (int k = 0; k < 2; ++k) {
             const int fr = GF(gname("ro", k)), fp4 = GF("pp4");
             IgemmDesc d;
-            d.X = w.vt_tok[k]; d.Wt = Y.ro_w[k]; d.M = Mp; d.N = E; d.Cin = 2 * E; d.ldx = E; d.bias = Y.ro_b[k]; d.act = ACT_GELU; d.out_op = w.vt_ro;
+            d.X = w.vt_tok[k]; d.Wt = Y.ro_w[k]; d.M = Mp; d.N = E; d.Cin = 2 * E; d.ldx = E; d.bias = W(YP.ro[k].project.b); d.act = ACT_GELU; d.out_op = w.vt_ro;
             d.grp_rows = G * G; d.grp_stride = (long long)NT * E; d.grp_off = E; d.seg2_k = E; d.seg2_off = 0;
             RUN(gemm(d, fr));
             d = IgemmDesc();
-            d.X = w.vt_ro; d.Wt = Y.pp_w[k]; d.M = Mp; d.N = a.fdim(2 + k); d.Cin = E; d.ldx = E; d.bias = Y.pp_b[k]; d.H = G; d.W = G;
+            d.X = w.vt_ro; d.Wt = Y.pp_w[k]; d.M = Mp; d.N = a.fdim(2 + k); d.Cin = E; d.ldx = E; d.bias = W(YP.ro[k].conv.b); d.H = G; d.W = G;
             d.out_op = k == 0 ? w.feat[2] : w.vt_pp4; d.out_halo = 1; d.out_fmt = MIX ? (k == 0 ? GF("lrn2") : fp4) : -1;
             RUN(gemm(d, fr));
             if (k == 1) {
                 d = IgemmDesc();
                 d.X = w.vt_pp4; d.Wt = Y.pp4_w; d.M = B * (G / 2) * (G / 2); d.N = a.fdim(3); d.Cin = a.fdim(3); d.taps = 9; d.H = G / 2; d.W = G / 2; d.Hi = G; d.Wi = G;
-                d.stride = 2; d.pad = 1; d.in_halo = 1; d.bias = Y.pp4_b; d.out_op = w.feat[3]; d.out_halo = 1; d.out_fmt = MIX ? GF("lrn3") : -1;
+                d.stride = 2; d.pad = 1; d.in_halo = 1; d.bias = W(YP.pp4.b); d.out_op = w.feat[3]; d.out_halo = 1; d.out_fmt = MIX ? GF("lrn3") : -1;
                 RUN(gemm(d, fp4));
             }
         }
@@ -958,14 +745,15 @@ static int run_chunk(Handle& h, const Workspace& w, const float* x, int B, float
     // block's output (the next block's attention, or the PatchMerging reduction), fhook = the decoder's layer_rn conv of this stage.
     { const int f0 = GF(gblk(0, 0, "qkv"));
       PROF("patch_embed_ln", 0.0, (double)B * a.img * a.img * 12.0 + (double)B * a.grid() * a.grid() * a.embed * 6.0);
-    RUN(launch_patch_embed(x, P.patch_wT, W(ENC + "patch_embed.proj.bias"), W(ENC + "patch_embed.norm.weight"),
-                           W(ENC + "patch_embed.norm.bias"), w.xf, f0 == 2 ? nullptr : static_cast<bf16_t*>(w.xb), f0 == 2 ? 0 : f0, B, a.img, a.embed, st, err)); }
+    RUN(launch_patch_embed(x, P.patch_wT, W(MP.swin.patch.b), W(MP.swin.patch_norm.g),
+                           W(MP.swin.patch_norm.b), w.xf, f0 == 2 ? nullptr : static_cast<bf16_t*>(w.xb), f0 == 2 ? 0 : f0, B, a.img, a.embed, st, err)); }
     for (int s = 0; s < 4; ++s) {
         const int C = a.dim(s), res = a.res(s), M = B * res * res, wsz = a.ws(s), H = a.heads[s];
         bool merged = false;   // the stage's last block wrote its operand copy straight into the PatchMerging layout (w.hbuf)
         const int fhook = GF(gname("lrn", s));
         for (int j = 0; j < a.depths[s]; ++j) {
             const BlockW& bw = P.blocks[s][j];
+            const SwinBlockP& bp = MP.swin.blk[s][j];
             const bool last = j == a.depths[s] - 1;
             // one format per GEMM: fa (qkv), fp (proj), fm (fc1), f2 (fc2); each producer writes its operand copy for the launch that reads it
             const int fa = GF(gblk(s, j, "qkv")), fp = GF(gblk(s, j, "proj")), fm = GF(gblk(s, j, "fc1")), f2 = GF(gblk(s, j, "fc2"));
@@ -997,39 +785,39 @@ static int run_chunk(Handle& h, const Workspace& w, const float* x, int B, float
                                                a.shift(s, j), H, st, err, (MIX && fp == 3) ? 1 : 0)); }
             const bool fuse_ln = C <= 128;  // whole rows fit one igemm tile; measured: a win for C = 96, a wash at 192, a loss beyond
             d = IgemmDesc();
-            d.X = b_attn; d.Wt = bw.proj_w; d.M = M; d.N = C; d.Cin = C; d.ldx = C; d.bias = bw.proj_b;
+            d.X = b_attn; d.Wt = bw.proj_w; d.M = M; d.N = C; d.Cin = C; d.ldx = C; d.bias = W(bp.proj.b);
             if (fuse_ln) {
-                d.ln_g = bw.n1_g; d.ln_b = bw.n1_b; d.ln_xf = w.xf; d.out_op = fm == 2 ? nullptr : w.xb; d.out_fmt = MIX ? fm : -1;
+                d.ln_g = W(bp.n1.g); d.ln_b = W(bp.n1.b); d.ln_xf = w.xf; d.out_op = fm == 2 ? nullptr : w.xb; d.out_fmt = MIX ? fm : -1;
                 RUN(gemm(d, fp));
             } else {
                 d.out_f32 = b_y1;
                 RUN(gemm(d, fp));
                 { PROF("ln_residual", 0.0, (double)M * C * 14.0);
-                  RUN(launch_ln_residual(b_y1, bw.n1_g, bw.n1_b, b_xf, fm == 2 ? nullptr : static_cast<bf16_t*>(b_x1), nullptr, nullptr, fm == 2 ? 0 : fm, M, C, 1, res, 0, st, err)); }
+                  RUN(launch_ln_residual(b_y1, W(bp.n1.g), W(bp.n1.b), b_xf, fm == 2 ? nullptr : static_cast<bf16_t*>(b_x1), nullptr, nullptr, fm == 2 ? 0 : fm, M, C, 1, res, 0, st, err)); }
             }
             if (fm <= 1 && f2 == fm && fnext == fm && (!hook || fhook == fm) && C <= h.mlp_fuse_max && mlp_ln_supported(C) &&
                 !group_x2w(h, gblk(s, j, "fc1")) && !group_x2w(h, gblk(s, j, "fc2"))) {   // (the fused kernel reads plain fp16 weights)   // fc1 + GELU + fc2 + LayerNorm + residual as one launch
                 PROF("mlp_ln_fused", 16.0 * M * (double)C * C, 0.0);
-                RUN(launch_mlp_ln(static_cast<const bf16_t*>(b_x1), b_xf, static_cast<const bf16_t*>(bw.fc1_w), bw.fc1_b, static_cast<const bf16_t*>(bw.fc2_w),
-                                  bw.fc2_b, bw.n2_g, bw.n2_b, static_cast<bf16_t*>(b_x2), hook ? static_cast<bf16_t*>(w.feat[s]) : nullptr, fm,
+                RUN(launch_mlp_ln(static_cast<const bf16_t*>(b_x1), b_xf, static_cast<const bf16_t*>(bw.fc1_w), W(bp.fc1.b), static_cast<const bf16_t*>(bw.fc2_w),
+                                  W(bp.fc2.b), W(bp.n2.g), W(bp.n2.b), static_cast<bf16_t*>(b_x2), hook ? static_cast<bf16_t*>(w.feat[s]) : nullptr, fm,
                                   M, C, res, res, to_merge ? 1 : 0, st, err));
                 merged = to_merge;
                 continue;
             }
             d = IgemmDesc();
-            d.X = b_x1; d.Wt = bw.fc1_w; d.M = M; d.N = 4 * C; d.Cin = C; d.ldx = C; d.bias = bw.fc1_b; d.act = ACT_GELU; d.out_op = b_hbuf; d.out_fmt = MIX ? f2 : -1;
+            d.X = b_x1; d.Wt = bw.fc1_w; d.M = M; d.N = 4 * C; d.Cin = C; d.ldx = C; d.bias = W(bp.fc1.b); d.act = ACT_GELU; d.out_op = b_hbuf; d.out_fmt = MIX ? f2 : -1;
             RUN(gemm(d, fm));
             d = IgemmDesc();
-            d.X = b_hbuf; d.Wt = bw.fc2_w; d.M = M; d.N = C; d.Cin = 4 * C; d.ldx = 4 * C; d.bias = bw.fc2_b;
+            d.X = b_hbuf; d.Wt = bw.fc2_w; d.M = M; d.N = C; d.Cin = 4 * C; d.ldx = 4 * C; d.bias = W(bp.fc2.b);
             if (fuse_ln) {
-                d.ln_g = bw.n2_g; d.ln_b = bw.n2_b; d.ln_xf = w.xf; d.out_op = fnext == 2 ? nullptr : w.xb; d.out_fmt = MIX ? fnext : -1;   // C <= 128: never a persistent-path stage; the LayerNorm epilogue writes plain rows (merge_gather follows)
+                d.ln_g = W(bp.n2.g); d.ln_b = W(bp.n2.b); d.ln_xf = w.xf; d.out_op = fnext == 2 ? nullptr : w.xb; d.out_fmt = MIX ? fnext : -1;   // C <= 128: never a persistent-path stage; the LayerNorm epilogue writes plain rows (merge_gather follows)
                 if (hook) { d.ln_halo = w.feat[s]; d.H = res; d.W = res; d.halo_fmt = MIX ? fhook : -1; }
                 RUN(gemm(d, f2));
             } else {
             d.out_f32 = b_y2;
             RUN(gemm(d, f2));
             { PROF("ln_residual", 0.0, (double)M * C * 14.0);
-              RUN(launch_ln_residual(b_y2, bw.n2_g, bw.n2_b, b_xf, fnext == 2 ? nullptr : static_cast<bf16_t*>(b_x2),
+              RUN(launch_ln_residual(b_y2, W(bp.n2.g), W(bp.n2.b), b_xf, fnext == 2 ? nullptr : static_cast<bf16_t*>(b_x2),
                                      (hook && fhook != 2) ? static_cast<bf16_t*>(w.feat[s]) : nullptr, (hook && fhook == 2) ? static_cast<float*>(w.feat[s]) : nullptr,
                                      fnext == 2 ? 0 : fnext, M, C, 1, res, to_merge ? 1 : 0, st, err, nullptr, 1, fhook == 2 ? -1 : fhook));
               merged = to_merge; }
@@ -1040,10 +828,10 @@ static int run_chunk(Handle& h, const Workspace& w, const float* x, int B, float
             if (!merged) { PROF("merge_gather", 0.0, (double)M * C * 4.0);
               RUN(launch_merge_gather(w.xb, w.hbuf, B, res, C, fg >= 2 ? 4 : 2, st, err)); }
             IgemmDesc d;
-            d.X = w.hbuf; d.Wt = P.merge[s].red_w; d.M = M / 4; d.N = 2 * C; d.Cin = 4 * C; d.ldx = 4 * C; d.out_f32 = w.y;
+            d.X = w.hbuf; d.Wt = P.merge_w[s]; d.M = M / 4; d.N = 2 * C; d.Cin = 4 * C; d.ldx = 4 * C; d.out_f32 = w.y;
             RUN(gemm(d, fg));
             { PROF("ln_residual", 0.0, (double)(M / 4) * 2 * C * 10.0);
-              RUN(launch_ln_residual(w.y, P.merge[s].g, P.merge[s].b, w.xf, fn == 2 ? nullptr : static_cast<bf16_t*>(w.xb), nullptr, nullptr,
+              RUN(launch_ln_residual(w.y, W(MP.swin.merge[s].norm.g), W(MP.swin.merge[s].norm.b), w.xf, fn == 2 ? nullptr : static_cast<bf16_t*>(w.xb), nullptr, nullptr,
                                      fn == 2 ? 0 : fn, M / 4, 2 * C, 0, res / 2, 0, st, err)); }
         }
     }
@@ -1067,11 +855,12 @@ static int run_chunk(Handle& h, const Workspace& w, const float* x, int B, float
         const void* fused_relu = w.lrn_relu[l];
         if (l < 3) {  // output = path + RCU1(layer_rn)
             const RcuW& u1 = P.rcu[l][0];
+            const RcuP& p1 = MP.refine[l].rcu[0];
             IgemmDesc d = conv(w.lrn_relu[l], F, u1.w1, F, r);
-            d.bias = u1.b1; d.act = ACT_RELU; d.out_op = w.t_relu[l]; d.out_halo = 1;
+            d.bias = W(p1.c1.b); d.act = ACT_RELU; d.out_op = w.t_relu[l]; d.out_halo = 1;
             RUN(gemm(d, fR));
             d = conv(w.t_relu[l], F, u1.w2, F, r);
-            d.bias = u1.b2; d.res1 = w.lrn_raw[l];
+            d.bias = W(p1.c2.b); d.res1 = w.lrn_raw[l];
             d.res2 = w.oc[l + 1]; d.res2_h = a.fres(l + 1); d.res2_w = a.fres(l + 1);  // bilinear(out_conv output of the coarser level), on the fly
             d.out_f32 = w.out_raw[l]; d.out_op = w.out_relu[l]; d.out_halo = 1; d.act = ACT_RELU;
             RUN(gemm(d, fR));
@@ -1080,16 +869,17 @@ static int run_chunk(Handle& h, const Workspace& w, const float* x, int B, float
         }
         {   // RCU2
             const RcuW& u2 = P.rcu[l][1];
+            const RcuP& p2 = MP.refine[l].rcu[1];
             IgemmDesc d = conv(fused_relu, F, u2.w1, F, r);
-            d.bias = u2.b1; d.act = ACT_RELU; d.out_op = w.t_relu[l]; d.out_halo = 1;
+            d.bias = W(p2.c1.b); d.act = ACT_RELU; d.out_op = w.t_relu[l]; d.out_halo = 1;
             RUN(gemm(d, fR));
             d = conv(w.t_relu[l], F, u2.w2, F, r);
-            d.bias = u2.b2; d.res1 = fused_raw; d.out_op = w.u[l]; d.out_fmt = MIX ? fO : -1;
+            d.bias = W(p2.c2.b); d.res1 = fused_raw; d.out_op = w.u[l]; d.out_fmt = MIX ? fO : -1;
             RUN(gemm(d, fR));
         }
         {   // out_conv (1x1) BEFORE the bilinear resize: both are linear and the interpolation weights sum to 1
             IgemmDesc d;
-            d.X = w.u[l]; d.Wt = P.oc_w[l]; d.M = M; d.N = F; d.Cin = F; d.ldx = F; d.bias = P.oc_b[l]; d.out_f32 = w.oc[l];
+            d.X = w.u[l]; d.Wt = P.oc_w[l]; d.M = M; d.N = F; d.Cin = F; d.ldx = F; d.bias = W(MP.refine[l].out_conv.b); d.out_f32 = w.oc[l];
             RUN(gemm(d, fO));
         }
         if (l == 0) { PROF("bilinear_resize", 0.0, (double)M * F * (4.0 + 8.0));
@@ -1100,13 +890,13 @@ static int run_chunk(Handle& h, const Workspace& w, const float* x, int B, float
     const int r1 = 2 * a.fres(0), r0 = 4 * a.fres(0);
     {
         IgemmDesc d = conv(w.path1, F, P.d0_w, F / 2, r1);
-        d.bias = P.d0_b;
+        d.bias = W(MP.depth.c0.b);
         if (fD2 <= 1 && F == 256) {
             // fused: up-sample + conv3x3(128->32) + ReLU + 1x1 + ReLU straight from the half-resolution map (16-bit operands)
             d.out_op = w.d1; d.out_fmt = MIX ? fD2 : -1;
             RUN(gemm(d, fH));
             PROF("depth_tail_fused", 2.0 * B * r0 * r0 * 32.0 * 9.0 * (F / 2), 0.0);
-            RUN(launch_depth_tail(static_cast<const bf16_t*>(w.d1), static_cast<const bf16_t*>(P.d2_w), P.d2_b, P.d4_w, P.d4_b, inv256, fD2, B, r1, r1, st, err));
+            RUN(launch_depth_tail(static_cast<const bf16_t*>(w.d1), static_cast<const bf16_t*>(P.d2_w), W(MP.depth.c2.b), W(MP.depth.c4.w), P.d4_b, inv256, fD2, B, r1, r1, st, err));
         } else {
             const bool d1_16 = fH <= 1 && !MIX;   // uniform 16-bit mode with F != 256: the half-resolution map stays a 16-bit operand
             if (d1_16) d.out_op = w.d1; else to_plain(d, w.d1, fH);
@@ -1115,7 +905,7 @@ static int run_chunk(Handle& h, const Workspace& w, const float* x, int B, float
               RUN(launch_bilinear(w.d1, d1_16 ? 1 : 0, nullptr, fD2 == 2 ? nullptr : static_cast<bf16_t*>(w.d1u), fD2 == 2 ? static_cast<float*>(w.d1u) : nullptr, 1, fD2 == 2 ? 0 : fD2, B, r1,
                                   r1, r0, r0, F / 2, st, err)); }
             d = conv(w.d1u, F / 2, P.d2_w, 32, r0);
-            d.bias = P.d2_b; d.act = ACT_RELU; d.dot_w = P.d4_w; d.dot_b = P.d4_b; d.out_dot = inv256;
+            d.bias = W(MP.depth.c2.b); d.act = ACT_RELU; d.dot_w = W(MP.depth.c4.w); d.dot_b = P.d4_b; d.out_dot = inv256;
             RUN(gemm(d, fD2));
         }
         // seg head: conv3x3 + folded BN + ReLU, then the 1x1 classifier + up-sampling + activation (f32 VALU).  The feature map between them is
@@ -1127,17 +917,17 @@ static int run_chunk(Handle& h, const Workspace& w, const float* x, int B, float
         if (seg_dot3_active(h)) {
             // the 1x1 classifier rides in the convolution's epilogue (igemm D3): the 256-channel feature map -- 67 MB written and read back per
             // forward at B = 8, rounded to 16 bits on the way -- is never stored; the logits come from the f32 accumulators
-            d.dot3 = 1; d.dot_w = P.s4_w; d.out_dot = static_cast<float*>(w.s1);   // [F / BN][M][4] partial logits in the feature map's buffer
+            d.dot3 = 1; d.dot_w = W(MP.seg.c4.w); d.out_dot = static_cast<float*>(w.s1);   // [F / BN][M][4] partial logits in the feature map's buffer
             d.f16 = fH == 1;
             const int parts = F / igemm_dot3_bn(d);   // one plane per channel tile of the launch (128-wide tiles: 2; the 16-wave 256 x 256 tile: 1)
             RUN(gemm(d, fH));
             PROF("seg_tail", 0.0, (double)B * r1 * r1 * (parts * 16.0 + 12.0 + 12.0 + 48.0));
-            RUN(launch_seg_tail_parts(static_cast<const float*>(w.s1), parts, P.s4_b, w.s2, seg256, B, r1, r1, h.cfg.sigmoid, st, err));
+            RUN(launch_seg_tail_parts(static_cast<const float*>(w.s1), parts, W(MP.seg.c4.b), w.s2, seg256, B, r1, r1, h.cfg.sigmoid, st, err));
         } else {
         if (s1_f32) to_plain(d, w.s1, fH); else { d.out_op = w.s1; d.out_fmt = MIX ? 1 : -1; }
         RUN(gemm(d, fH));
         { PROF("seg_tail", 0.0, (double)B * r1 * r1 * (F * 2.0 + 12.0 + 48.0));
-          RUN(launch_seg_tail(w.s1, s1_f32 ? 1 : 0, fS1 == 1, P.s4_w, P.s4_b, w.s2, seg256, B, r1, r1, h.cfg.sigmoid, st, err)); }
+          RUN(launch_seg_tail(w.s1, s1_f32 ? 1 : 0, fS1 == 1, W(MP.seg.c4.w), W(MP.seg.c4.b), w.s2, seg256, B, r1, r1, h.cfg.sigmoid, st, err)); }
         }
         ++launches;
     }

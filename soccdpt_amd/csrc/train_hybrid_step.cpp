@@ -13,27 +13,6 @@ namespace {
 const float kWsEps = 1e-8f;    // timm StdConv2dSame
 const float kLnEps = 1e-6f;    // timm VisionTransformer norm_layer
 
-std::string rn_key(int s, int j) { return ENC + "patch_embed.backbone.stages." + std::to_string(s) + ".blocks." + std::to_string(j) + "."; }
-std::string vit_key(int i) { return ENC + "blocks." + std::to_string(i) + "."; }
-
-// the bottleneck list of ResNetV2 (3, 4, 9): geometry only
-void describe_blocks(const Arch& a, std::vector<RnBlkT>& out) {
-    out.clear();
-    int prev = a.stem_ch, r = a.img / 4;
-    for (int s3 = 0; s3 < 3; ++s3) {
-        const int cout = 256 << s3, mid = cout / 4;
-        for (int j = 0; j < a.rn_layers[s3]; ++j) {
-            RnBlkT b{};
-            b.cin = prev; b.cout = cout; b.mid = mid; b.proj = (j == 0); b.stride = (j == 0 && s3 > 0) ? 2 : 1;
-            b.rin = r; b.rout = r / b.stride;
-            b.key = rn_key(s3, j);
-            out.push_back(b);
-            prev = cout;
-            r = b.rout;
-        }
-    }
-}
-
 }  // namespace
 
 // Backward of a 3x3 convolution with tap-major weights Wtap [N][9][C] over a zero-haloed input [B][Hi+2][Hi+2][C], output Ho x Ho.
@@ -112,8 +91,9 @@ void from_partials(Ctx& c, GnApplyArgs& g, int slot, int slot2 = -1) {
 
 void hy_carve_halo(const Handle& h, int B, TArena& ar, Tape& T) {
     HyTape& Y = T.hy;
-    describe_blocks(h.arch, Y.blk);
-    for (auto& b : Y.blk) b.t1 = ar.f((size_t)B * (b.rin + 2) * (b.rin + 2) * b.mid);
+    const std::vector<RnBlockP>& rn = h.params.hy.rn;
+    Y.blk.assign(rn.size(), RnBlkT{});
+    for (size_t i = 0; i < rn.size(); ++i) Y.blk[i].t1 = ar.f((size_t)B * (rn[i].rin + 2) * (rn[i].rin + 2) * rn[i].mid);
     const int G = h.arch.grid();
     Y.pp4_in = ar.f((size_t)B * (G + 2) * (G + 2) * h.arch.fdim(3));
 }
@@ -130,24 +110,26 @@ void hy_carve(const Handle& h, int B, TArena& ar, Tape& T, size_t& maxAct) {
     Y.pool = ar.f((size_t)B * H2 * H2 * a.stem_ch);
     Y.pool_idx = reinterpret_cast<uint8_t*>(ar.f(((size_t)B * H2 * H2 * a.stem_ch + 3) / 4));
     maxAct = std::max(maxAct, M1s * 160);
-    for (auto& b : Y.blk) {
-        const size_t Min = (size_t)B * b.rin * b.rin, Mout = (size_t)B * b.rout * b.rout;
-        b.w_ds = b.proj ? ar.f((size_t)b.cout * b.cin) : nullptr;
-        b.w_c1 = ar.f((size_t)b.mid * b.cin);
-        b.w_c2 = ar.f((size_t)b.mid * 9 * b.mid);
-        b.w_c3 = ar.f((size_t)b.cout * b.mid);
-        b.ds_raw = b.proj ? ar.f(Mout * b.cout) : nullptr;
-        b.ds_stats = b.proj ? ar.f((size_t)B * 64) : nullptr;
-        b.c1_raw = ar.f(Min * b.mid);
+    for (size_t i = 0; i < Y.blk.size(); ++i) {
+        RnBlkT& b = Y.blk[i];
+        const RnBlockP& p = h.params.hy.rn[i];
+        const size_t Min = (size_t)B * p.rin * p.rin, Mout = (size_t)B * p.rout * p.rout;
+        b.w_ds = p.proj ? ar.f((size_t)p.cout * p.cin) : nullptr;
+        b.w_c1 = ar.f((size_t)p.mid * p.cin);
+        b.w_c2 = ar.f((size_t)p.mid * 9 * p.mid);
+        b.w_c3 = ar.f((size_t)p.cout * p.mid);
+        b.ds_raw = p.proj ? ar.f(Mout * p.cout) : nullptr;
+        b.ds_stats = p.proj ? ar.f((size_t)B * 64) : nullptr;
+        b.c1_raw = ar.f(Min * p.mid);
         b.c1_stats = ar.f((size_t)B * 64);
-        b.c2_raw = ar.f(Mout * b.mid);
+        b.c2_raw = ar.f(Mout * p.mid);
         b.c2_stats = ar.f((size_t)B * 64);
-        b.t2 = ar.f(Mout * b.mid);
-        b.c3_raw = ar.f(Mout * b.cout);
+        b.t2 = ar.f(Mout * p.mid);
+        b.c3_raw = ar.f(Mout * p.cout);
         b.c3_stats = ar.f((size_t)B * 64);
-        b.out = ar.f(Mout * b.cout);
-        maxAct = std::max(maxAct, std::max(Min * (size_t)std::max(b.cin, b.mid), Mout * (size_t)b.cout));
-        maxAct = std::max(maxAct, Mout * 9 * (size_t)b.mid);   // dcol of the strided 3x3
+        b.out = ar.f(Mout * p.cout);
+        maxAct = std::max(maxAct, std::max(Min * (size_t)std::max(p.cin, p.mid), Mout * (size_t)p.cout));
+        maxAct = std::max(maxAct, Mout * 9 * (size_t)p.mid);   // dcol of the strided 3x3
     }
     Y.gn_part_floats = M1s * 2;   // (M / 32 tiles) x 32 groups x 2 at the stem's M
     for (int i = 0; i < 2; ++i) Y.gn_part[i] = ar.f(Y.gn_part_floats);
@@ -186,73 +168,74 @@ int hy_forward(Ctx& c, const float* x) {
     hipStream_t st = c.st;
     std::string& err = c.err;
     const int S = a.img, H1 = S / 2, H2 = S / 4;
-    const std::string bb = ENC + "patch_embed.backbone.";
+    const HybridP& P = h.params.hy;
     // ---- stem: Conv 7x7 / 2 'SAME' (im2col + GEMM) -> GroupNorm + ReLU -> MaxPool 3x3 / 2 'SAME' ----
     TRY(launch_stem_im2col(x, Y.a0, 2, B, S, st, err));
-    TRY(launch_ws_conv_w(c.W(bb + "stem.conv.weight"), Y.w_stem, 2, a.stem_ch, 3, 7, 160, kWsEps, st, err));
+    TRY(launch_ws_conv_w(c.W(P.stem_w), Y.w_stem, 2, a.stem_ch, 3, 7, 160, kWsEps, st, err));
     {
         IgemmDesc d;
         d.X = Y.a0; d.Wt = Y.w_stem; d.M = B * H1 * H1; d.N = a.stem_ch; d.Cin = 160; d.ldx = 160; d.out_f32 = Y.stem_raw;
         with_stats(c, d, Y.stem_stats, a.stem_ch, H1 * H1);
         TRY(gemm(c, d));
         TRY(launch_gn_finish(Y.gn_part[0], Y.stem_stats, B, H1 * H1 / Y.gn_bm[0], 32, H1 * H1, a.stem_ch / 32, 1e-5f, st, err));
-        TRY(launch_gn_relu_maxpool(Y.stem_raw, Y.stem_stats, c.W(bb + "stem.norm.weight"), c.W(bb + "stem.norm.bias"), Y.pool, 2, B, H1, a.stem_ch, a.stem_ch / 32, st, err));
+        TRY(launch_gn_relu_maxpool(Y.stem_raw, Y.stem_stats, c.W(P.stem_n.g), c.W(P.stem_n.b), Y.pool, 2, B, H1, a.stem_ch, a.stem_ch / 32, st, err));
     }
     const float* xcur = Y.pool;
     int hook = 0, cnt = 0, stage = 0;
-    for (auto& b : Y.blk) {
-        const int Min = B * b.rin * b.rin, Mout = B * b.rout * b.rout;
-        const std::string& k = b.key;
+    for (size_t bi = 0; bi < Y.blk.size(); ++bi) {
+        RnBlkT& b = Y.blk[bi];
+        const RnBlockP& p = P.rn[bi];
+        const int Min = B * p.rin * p.rin, Mout = B * p.rout * p.rout;
         b.xin = xcur;
-        if (b.proj) {
-            TRY(launch_ws_conv_w(c.W(k + "downsample.conv.weight"), b.w_ds, 2, b.cout, b.cin, 1, b.cin, kWsEps, st, err));
+        if (p.proj) {
+            TRY(launch_ws_conv_w(c.W(p.ds_w), b.w_ds, 2, p.cout, p.cin, 1, p.cin, kWsEps, st, err));
             IgemmDesc d;
-            d.X = b.xin; d.Wt = b.w_ds; d.M = Mout; d.N = b.cout; d.Cin = b.cin; d.out_f32 = b.ds_raw;
-            if (b.stride == 1) d.ldx = b.cin;
-            else { d.gather1 = 1; d.stride = b.stride; d.pad = 0; d.in_halo = 0; d.Hi = b.rin; d.Wi = b.rin; d.H = b.rout; d.W = b.rout; }
-            with_stats(c, d, b.ds_stats, b.cout, b.rout * b.rout, 1);
-            TRY(gemm_fwd(c, d, (size_t)Min * b.cin, (size_t)b.cout * b.cin));   // (x3 only for the un-strided form: gemm_fwd checks)
+            d.X = b.xin; d.Wt = b.w_ds; d.M = Mout; d.N = p.cout; d.Cin = p.cin; d.out_f32 = b.ds_raw;
+            if (p.stride == 1) d.ldx = p.cin;
+            else { d.gather1 = 1; d.stride = p.stride; d.pad = 0; d.in_halo = 0; d.Hi = p.rin; d.Wi = p.rin; d.H = p.rout; d.W = p.rout; }
+            with_stats(c, d, b.ds_stats, p.cout, p.rout * p.rout, 1);
+            TRY(gemm_fwd(c, d, (size_t)Min * p.cin, (size_t)p.cout * p.cin));   // (x3 only for the un-strided form: gemm_fwd checks)
         }
         {
-            TRY(launch_ws_conv_w(c.W(k + "conv1.weight"), b.w_c1, 2, b.mid, b.cin, 1, b.cin, kWsEps, st, err));
+            TRY(launch_ws_conv_w(c.W(p.c1_w), b.w_c1, 2, p.mid, p.cin, 1, p.cin, kWsEps, st, err));
             IgemmDesc d;
-            d.X = b.xin; d.Wt = b.w_c1; d.M = Min; d.N = b.mid; d.Cin = b.cin; d.ldx = b.cin; d.out_f32 = b.c1_raw;
-            with_stats(c, d, b.c1_stats, b.mid, b.rin * b.rin);
-            TRY(gemm_fwd(c, d, (size_t)Min * b.cin, (size_t)b.mid * b.cin));
+            d.X = b.xin; d.Wt = b.w_c1; d.M = Min; d.N = p.mid; d.Cin = p.cin; d.ldx = p.cin; d.out_f32 = b.c1_raw;
+            with_stats(c, d, b.c1_stats, p.mid, p.rin * p.rin);
+            TRY(gemm_fwd(c, d, (size_t)Min * p.cin, (size_t)p.mid * p.cin));
             GnApplyArgs g;
-            g.raw = b.c1_raw; g.stats = b.c1_stats; g.gamma = c.W(k + "norm1.weight"); g.beta = c.W(k + "norm1.bias"); g.out_halo = b.t1;
-            g.M = (size_t)Min; g.HW = b.rin * b.rin; g.W = b.rin; g.C = b.mid; g.cpg = b.mid / 32;
+            g.raw = b.c1_raw; g.stats = b.c1_stats; g.gamma = c.W(p.n1.g); g.beta = c.W(p.n1.b); g.out_halo = b.t1;
+            g.M = (size_t)Min; g.HW = p.rin * p.rin; g.W = p.rin; g.C = p.mid; g.cpg = p.mid / 32;
             from_partials(c, g, 0);
             TRY(launch_gn_apply(g, 2, st, err));
         }
         {
-            TRY(launch_ws_conv_w(c.W(k + "conv2.weight"), b.w_c2, 2, b.mid, b.mid, 3, 9 * b.mid, kWsEps, st, err));
+            TRY(launch_ws_conv_w(c.W(p.c2_w), b.w_c2, 2, p.mid, p.mid, 3, 9 * p.mid, kWsEps, st, err));
             IgemmDesc d;
-            d.X = b.t1; d.Wt = b.w_c2; d.M = Mout; d.N = b.mid; d.Cin = b.mid; d.taps = 9; d.H = b.rout; d.W = b.rout; d.Hi = b.rin; d.Wi = b.rin;
-            d.stride = b.stride; d.pad = b.stride == 1 ? 1 : 0; d.in_halo = 1; d.out_f32 = b.c2_raw;
-            with_stats(c, d, b.c2_stats, b.mid, b.rout * b.rout);
-            TRY(gemm_fwd(c, d, (size_t)B * (b.rin + 2) * (b.rin + 2) * b.mid, (size_t)9 * b.mid * b.mid));
+            d.X = b.t1; d.Wt = b.w_c2; d.M = Mout; d.N = p.mid; d.Cin = p.mid; d.taps = 9; d.H = p.rout; d.W = p.rout; d.Hi = p.rin; d.Wi = p.rin;
+            d.stride = p.stride; d.pad = p.stride == 1 ? 1 : 0; d.in_halo = 1; d.out_f32 = b.c2_raw;
+            with_stats(c, d, b.c2_stats, p.mid, p.rout * p.rout);
+            TRY(gemm_fwd(c, d, (size_t)B * (p.rin + 2) * (p.rin + 2) * p.mid, (size_t)9 * p.mid * p.mid));
             GnApplyArgs g;
-            g.raw = b.c2_raw; g.stats = b.c2_stats; g.gamma = c.W(k + "norm2.weight"); g.beta = c.W(k + "norm2.bias"); g.out_op = b.t2;
-            g.M = (size_t)Mout; g.HW = b.rout * b.rout; g.W = b.rout; g.C = b.mid; g.cpg = b.mid / 32;
+            g.raw = b.c2_raw; g.stats = b.c2_stats; g.gamma = c.W(p.n2.g); g.beta = c.W(p.n2.b); g.out_op = b.t2;
+            g.M = (size_t)Mout; g.HW = p.rout * p.rout; g.W = p.rout; g.C = p.mid; g.cpg = p.mid / 32;
             from_partials(c, g, 0);
             TRY(launch_gn_apply(g, 2, st, err));
         }
         {
-            TRY(launch_ws_conv_w(c.W(k + "conv3.weight"), b.w_c3, 2, b.cout, b.mid, 1, b.mid, kWsEps, st, err));
+            TRY(launch_ws_conv_w(c.W(p.c3_w), b.w_c3, 2, p.cout, p.mid, 1, p.mid, kWsEps, st, err));
             IgemmDesc d;
-            d.X = b.t2; d.Wt = b.w_c3; d.M = Mout; d.N = b.cout; d.Cin = b.mid; d.ldx = b.mid; d.out_f32 = b.c3_raw;
-            with_stats(c, d, b.c3_stats, b.cout, b.rout * b.rout);
-            TRY(gemm_fwd(c, d, (size_t)Mout * b.mid, (size_t)b.cout * b.mid));
+            d.X = b.t2; d.Wt = b.w_c3; d.M = Mout; d.N = p.cout; d.Cin = p.mid; d.ldx = p.mid; d.out_f32 = b.c3_raw;
+            with_stats(c, d, b.c3_stats, p.cout, p.rout * p.rout);
+            TRY(gemm_fwd(c, d, (size_t)Mout * p.mid, (size_t)p.cout * p.mid));
             GnApplyArgs g;
-            g.raw = b.c3_raw; g.stats = b.c3_stats; g.gamma = c.W(k + "norm3.weight"); g.beta = c.W(k + "norm3.bias");
-            if (b.proj) { g.raw2 = b.ds_raw; g.stats2 = b.ds_stats; g.gamma2 = c.W(k + "downsample.norm.weight"); g.beta2 = c.W(k + "downsample.norm.bias"); }
+            g.raw = b.c3_raw; g.stats = b.c3_stats; g.gamma = c.W(p.n3.g); g.beta = c.W(p.n3.b);
+            if (p.proj) { g.raw2 = b.ds_raw; g.stats2 = b.ds_stats; g.gamma2 = c.W(p.ds_n.g); g.beta2 = c.W(p.ds_n.b); }
             else g.res = b.xin;
             g.out_f32 = b.out;
             ++cnt;
             if (stage < 2 && cnt == a.rn_layers[stage]) g.out_halo = T.feat[hook++];   // hooks on stages[0], stages[1] (vit.py:164-167)
-            g.M = (size_t)Mout; g.HW = b.rout * b.rout; g.W = b.rout; g.C = b.cout; g.cpg = b.cout / 32;
-            from_partials(c, g, 0, b.proj ? 1 : -1);
+            g.M = (size_t)Mout; g.HW = p.rout * p.rout; g.W = p.rout; g.C = p.cout; g.cpg = p.cout / 32;
+            from_partials(c, g, 0, p.proj ? 1 : -1);
             TRY(launch_gn_apply(g, 2, st, err));
             if (cnt == a.rn_layers[stage]) { ++stage; cnt = 0; }
         }
@@ -263,51 +246,51 @@ int hy_forward(Ctx& c, const float* x) {
     const int E = a.vit_dim, G = a.grid(), NT = G * G + 1, Mt = B * NT, Mp = B * G * G;
     {
         IgemmDesc d;
-        d.X = xcur; d.Wt = c.W(ENC + "patch_embed.proj.weight"); d.M = Mp; d.N = E; d.Cin = 1024; d.ldx = 1024; d.bias = c.W(ENC + "patch_embed.proj.bias"); d.out_f32 = Y.pe_y;
+        d.X = xcur; d.Wt = c.W(P.pe.w); d.M = Mp; d.N = E; d.Cin = 1024; d.ldx = 1024; d.bias = c.W(P.pe.b); d.out_f32 = Y.pe_y;
         TRY(gemm(c, d));
-        TRY(launch_vit_tokens_ln(Y.pe_y, c.W(ENC + "cls_token"), c.W(ENC + "pos_embed"), Y.x0, c.W(vit_key(0) + "norm1.weight"), c.W(vit_key(0) + "norm1.bias"), Y.vb[0].ln1, 2,
+        TRY(launch_vit_tokens_ln(Y.pe_y, c.W(P.cls), c.W(P.pos), Y.x0, c.W(P.vit[0].n1.g), c.W(P.vit[0].n1.b), Y.vb[0].ln1, 2,
                                  B, NT, E, kLnEps, st, err));
     }
     const float* tcur = Y.x0;
     for (int i = 0; i < a.vit_depth; ++i) {
         VitBlkT& v = Y.vb[i];
-        const std::string k = vit_key(i);
+        const VitBlockP& p = P.vit[i];
         v.xin = tcur;
-        if (i > 0) TRY(launch_ln_rows(const_cast<float*>(v.xin), c.W(k + "norm1.weight"), c.W(k + "norm1.bias"), v.ln1, 2, Mt, E, kLnEps, st, err));
+        if (i > 0) TRY(launch_ln_rows(const_cast<float*>(v.xin), c.W(p.n1.g), c.W(p.n1.b), v.ln1, 2, Mt, E, kLnEps, st, err));
         IgemmDesc d;
-        d.X = v.ln1; d.Wt = c.W(k + "attn.qkv.weight"); d.M = Mt; d.N = 3 * E; d.Cin = E; d.ldx = E; d.bias = c.W(k + "attn.qkv.bias"); d.out_f32 = v.qkv;
+        d.X = v.ln1; d.Wt = c.W(p.qkv.w); d.M = Mt; d.N = 3 * E; d.Cin = E; d.ldx = E; d.bias = c.W(p.qkv.b); d.out_f32 = v.qkv;
         TRY(gemm_fwd(c, d, (size_t)Mt * E, (size_t)3 * E * E));   // x3 operands in the amp modes (train_step.cpp: gemm_fwd), exact f32 otherwise
         TRY(launch_vit_attention(v.qkv, v.attn, SOCCDPT_PREC_F32, B, NT, a.vit_heads, st, err));   // the exact-f32 MFMA kernel of the inference path (vit_attention.hip)
         d = IgemmDesc();
-        d.X = v.attn; d.Wt = c.W(k + "attn.proj.weight"); d.M = Mt; d.N = E; d.Cin = E; d.ldx = E; d.bias = c.W(k + "attn.proj.bias"); d.res1 = v.xin; d.out_f32 = v.x1;
+        d.X = v.attn; d.Wt = c.W(p.proj.w); d.M = Mt; d.N = E; d.Cin = E; d.ldx = E; d.bias = c.W(p.proj.b); d.res1 = v.xin; d.out_f32 = v.x1;
         TRY(gemm_fwd(c, d, (size_t)Mt * E, (size_t)E * E));
-        TRY(launch_ln_rows(v.x1, c.W(k + "norm2.weight"), c.W(k + "norm2.bias"), v.ln2, 2, Mt, E, kLnEps, st, err));
+        TRY(launch_ln_rows(v.x1, c.W(p.n2.g), c.W(p.n2.b), v.ln2, 2, Mt, E, kLnEps, st, err));
         d = IgemmDesc();
-        d.X = v.ln2; d.Wt = c.W(k + "mlp.fc1.weight"); d.M = Mt; d.N = 4 * E; d.Cin = E; d.ldx = E; d.bias = c.W(k + "mlp.fc1.bias"); d.act = ACT_GELU;
+        d.X = v.ln2; d.Wt = c.W(p.fc1.w); d.M = Mt; d.N = 4 * E; d.Cin = E; d.ldx = E; d.bias = c.W(p.fc1.b); d.act = ACT_GELU;
         d.out_f32 = v.hpre; d.out_op = v.hact;
         TRY(gemm_fwd(c, d, (size_t)Mt * E, (size_t)4 * E * E));
         d = IgemmDesc();
-        d.X = v.hact; d.Wt = c.W(k + "mlp.fc2.weight"); d.M = Mt; d.N = E; d.Cin = 4 * E; d.ldx = 4 * E; d.bias = c.W(k + "mlp.fc2.bias"); d.res1 = v.x1; d.out_f32 = v.xout;
+        d.X = v.hact; d.Wt = c.W(p.fc2.w); d.M = Mt; d.N = E; d.Cin = 4 * E; d.ldx = 4 * E; d.bias = c.W(p.fc2.b); d.res1 = v.x1; d.out_f32 = v.xout;
         TRY(gemm_fwd(c, d, (size_t)Mt * 4 * E, (size_t)4 * E * E));
         tcur = v.xout;
     }
     // ---- act_postprocess3 / 4: ProjectReadout -> Conv1x1 (-> Conv3x3 / 2) ----
     for (int k = 0; k < 2; ++k) {
-        const std::string ap = HYB + "act_postprocess" + std::to_string(3 + k) + ".";
+        const ReadoutP& ro = P.ro[k];
         TRY(th_readout_cat(Y.vb[a.vit_hooks[k]].xout, Y.cat[k], B, NT, E, st, err));
         IgemmDesc d;
-        d.X = Y.cat[k]; d.Wt = c.W(ap + "0.project.0.weight"); d.M = Mp; d.N = E; d.Cin = 2 * E; d.ldx = 2 * E; d.bias = c.W(ap + "0.project.0.bias"); d.act = ACT_GELU;
+        d.X = Y.cat[k]; d.Wt = c.W(ro.project.w); d.M = Mp; d.N = E; d.Cin = 2 * E; d.ldx = 2 * E; d.bias = c.W(ro.project.b); d.act = ACT_GELU;
         d.out_f32 = Y.ro_pre[k]; d.out_op = Y.ro_act[k];
         TRY(gemm(c, d));
         d = IgemmDesc();
-        d.X = Y.ro_act[k]; d.Wt = c.W(ap + "3.weight"); d.M = Mp; d.N = a.fdim(2 + k); d.Cin = E; d.ldx = E; d.bias = c.W(ap + "3.bias"); d.H = G; d.W = G;
+        d.X = Y.ro_act[k]; d.Wt = c.W(ro.conv.w); d.M = Mp; d.N = a.fdim(2 + k); d.Cin = E; d.ldx = E; d.bias = c.W(ro.conv.b); d.H = G; d.W = G;
         d.out_op = k == 0 ? T.feat[2] : Y.pp4_in; d.out_halo = 1;
         TRY(gemm(c, d));
         if (k == 1) {
-            TRY(launch_conv_w(c.W(ap + "4.weight"), nullptr, Y.w_pp4, 1, 0, a.fdim(3), a.fdim(3), st, err));
+            TRY(launch_conv_w(c.W(P.pp4.w), nullptr, Y.w_pp4, 1, 0, a.fdim(3), a.fdim(3), st, err));
             d = IgemmDesc();
             d.X = Y.pp4_in; d.Wt = Y.w_pp4; d.M = B * (G / 2) * (G / 2); d.N = a.fdim(3); d.Cin = a.fdim(3); d.taps = 9; d.H = G / 2; d.W = G / 2; d.Hi = G; d.Wi = G;
-            d.stride = 2; d.pad = 1; d.in_halo = 1; d.bias = c.W(ap + "4.bias"); d.out_op = T.feat[3]; d.out_halo = 1;
+            d.stride = 2; d.pad = 1; d.in_halo = 1; d.bias = c.W(P.pp4.b); d.out_op = T.feat[3]; d.out_halo = 1;
             TRY(gemm(c, d));
         }
     }
@@ -323,6 +306,7 @@ int hy_backward(Ctx& c) {
     hipStream_t st = c.st;
     std::string& err = c.err;
     float** G = T.G;
+    const HybridP& P = h.params.hy;
     const int E = a.vit_dim, Gd = a.grid(), NT = Gd * Gd + 1;
     const size_t Mt = (size_t)B * NT, Mp = (size_t)B * Gd * Gd;
     // re-derive the input pointers of the forward walk
@@ -333,23 +317,23 @@ int hy_backward(Ctx& c) {
         for (auto& v : Y.vb) { v.xin = tcur; tcur = v.xout; }
     }
     // weight-standardised convolution: gradient of the standardised weights (tap-major, in S_dw) -> parameter gradient
-    auto ws_grad = [&](const std::string& key, const float* wh, int Cout, int Cin, int k, int Kpad) -> int {
+    auto ws_grad = [&](PRef key, const float* wh, int Cout, int Cin, int k, int Kpad) -> int {
         float* dw = c.Gd(key);
         if (!dw) return 0;
         return th_ws_bwd(T.S_dw, wh, c.W(key), dw, Cout, Cin, k, Kpad, kWsEps, st, err);
     };
     // ---- read-outs: gradient of a hooked token stream from the gradient of its reassembled map ----
     auto readout_bwd = [&](int k, int accumulate) -> int {
-        const std::string ap = HYB + "act_postprocess" + std::to_string(3 + k) + ".";
+        const ReadoutP& ro = P.ro[k];
         const float* dmap = T.DF[2 + k];
         if (k == 1) {   // Conv2d(768, 768, 3, stride 2, padding 1)
-            TRY(conv_gen_bwd(c, dmap, Y.pp4_in, Y.w_pp4, Gd, Gd / 2, a.fdim(3), a.fdim(3), 2, 1, G[0], c.Gd(ap + "4.weight") ? T.S_dw : nullptr, c.Gd(ap + "4.bias")));
-            if (float* dw = c.Gd(ap + "4.weight")) TRY(tr_wgrad_permute(T.S_dw, dw, a.fdim(3), a.fdim(3), st, err));
+            TRY(conv_gen_bwd(c, dmap, Y.pp4_in, Y.w_pp4, Gd, Gd / 2, a.fdim(3), a.fdim(3), 2, 1, G[0], c.Gd(P.pp4.w) ? T.S_dw : nullptr, c.Gd(P.pp4.b)));
+            if (float* dw = c.Gd(P.pp4.w)) TRY(tr_wgrad_permute(T.S_dw, dw, a.fdim(3), a.fdim(3), st, err));
             dmap = G[0];
         }
-        TRY(linear_bwd(c, dmap, Y.ro_act[k], c.W(ap + "3.weight"), Mp, a.fdim(2 + k), E, G[1], nullptr, c.Gd(ap + "3.weight"), c.Gd(ap + "3.bias")));
+        TRY(linear_bwd(c, dmap, Y.ro_act[k], c.W(ro.conv.w), Mp, a.fdim(2 + k), E, G[1], nullptr, c.Gd(ro.conv.w), c.Gd(ro.conv.b)));
         TRY(tr_gelu_bwd(G[1], Y.ro_pre[k], G[1], Mp * E, st, err));
-        TRY(linear_bwd(c, G[1], Y.cat[k], c.W(ap + "0.project.0.weight"), Mp, E, 2 * E, G[2], nullptr, c.Gd(ap + "0.project.0.weight"), c.Gd(ap + "0.project.0.bias")));
+        TRY(linear_bwd(c, G[1], Y.cat[k], c.W(ro.project.w), Mp, E, 2 * E, G[2], nullptr, c.Gd(ro.project.w), c.Gd(ro.project.b)));
         TRY(th_readout_cat_bwd(G[2], Y.GT, B, NT, E, accumulate, st, err));
         return 0;
     };
@@ -359,27 +343,27 @@ int hy_backward(Ctx& c) {
         if (i == a.vit_hooks[0]) TRY(readout_bwd(0, 1));
         if (i > a.vit_hooks[1]) continue;
         VitBlkT& v = Y.vb[i];
-        const std::string k = vit_key(i);
+        const VitBlockP& p = P.vit[i];
         // xout = x1 + fc2(gelu(fc1(LN2(x1))))
-        TRY(linear_bwd(c, Y.GT, v.hact, c.W(k + "mlp.fc2.weight"), Mt, E, 4 * E, G[0], nullptr, c.Gd(k + "mlp.fc2.weight"), c.Gd(k + "mlp.fc2.bias")));
+        TRY(linear_bwd(c, Y.GT, v.hact, c.W(p.fc2.w), Mt, E, 4 * E, G[0], nullptr, c.Gd(p.fc2.w), c.Gd(p.fc2.b)));
         TRY(tr_gelu_bwd(G[0], v.hpre, G[0], Mt * 4 * E, st, err));
-        TRY(linear_bwd(c, G[0], v.ln2, c.W(k + "mlp.fc1.weight"), Mt, 4 * E, E, G[1], nullptr, c.Gd(k + "mlp.fc1.weight"), c.Gd(k + "mlp.fc1.bias")));
-        TRY(ln_bwd(c, v.x1, c.W(k + "norm2.weight"), G[1], G[2], G[3], Mt, E, c.Gd(k + "norm2.weight"), c.Gd(k + "norm2.bias"), kLnEps));
+        TRY(linear_bwd(c, G[0], v.ln2, c.W(p.fc1.w), Mt, 4 * E, E, G[1], nullptr, c.Gd(p.fc1.w), c.Gd(p.fc1.b)));
+        TRY(ln_bwd(c, v.x1, c.W(p.n2.g), G[1], G[2], G[3], Mt, E, c.Gd(p.n2.g), c.Gd(p.n2.b), kLnEps));
         TRY(tr_axpy(G[2], Y.GT, Mt * E, st, err));                                   // G2 = d x1
         // x1 = xin + proj(attn(qkv(LN1(xin))))
-        TRY(linear_bwd(c, G[2], v.attn, c.W(k + "attn.proj.weight"), Mt, E, E, G[0], nullptr, c.Gd(k + "attn.proj.weight"), c.Gd(k + "attn.proj.bias")));
+        TRY(linear_bwd(c, G[2], v.attn, c.W(p.proj.w), Mt, E, E, G[0], nullptr, c.Gd(p.proj.w), c.Gd(p.proj.b)));
         // 16-bit products in the 16-bit amp modes (autocast semantics), exact ones otherwise; v.rowstat is this launch's scratch ({m + ln l, delta} per query)
         const OpFmt attn_fmt = op_is16(amp_fmt(c)) ? amp_fmt(c) : OpFmt::F32;
         TRY(th_vit_attention_bwd_mfma(v.qkv, v.attn, G[0], v.rowstat, G[4], B, NT, a.vit_heads, st, err, attn_fmt));
-        TRY(linear_bwd(c, G[4], v.ln1, c.W(k + "attn.qkv.weight"), Mt, 3 * E, E, G[1], nullptr, c.Gd(k + "attn.qkv.weight"), c.Gd(k + "attn.qkv.bias")));
-        TRY(ln_bwd(c, v.xin, c.W(k + "norm1.weight"), G[1], G[0], G[3], Mt, E, c.Gd(k + "norm1.weight"), c.Gd(k + "norm1.bias"), kLnEps));
+        TRY(linear_bwd(c, G[4], v.ln1, c.W(p.qkv.w), Mt, 3 * E, E, G[1], nullptr, c.Gd(p.qkv.w), c.Gd(p.qkv.b)));
+        TRY(ln_bwd(c, v.xin, c.W(p.n1.g), G[1], G[0], G[3], Mt, E, c.Gd(p.n1.g), c.Gd(p.n1.b), kLnEps));
         TRY(copy_d2d(c, Y.GT, G[2], Mt * E * 4, "hy_backward"));
         TRY(tr_axpy(Y.GT, G[0], Mt * E, st, err));                                   // GT = d xin
     }
     // ---- tokens = cat(cls, proj(features)) + pos_embed ----
     {
-        float* dpos = c.Gd(ENC + "pos_embed");
-        float* dcls = c.Gd(ENC + "cls_token");
+        float* dpos = c.Gd(P.pos);
+        float* dcls = c.Gd(P.cls);
         if (dpos || dcls) {
             // sum over the batch of the token-stream gradient: [B][NT*E] -> [NT*E]  (tr_colsum: rows = samples)
             float* tmp = dpos ? dpos : G[3];
@@ -387,61 +371,60 @@ int hy_backward(Ctx& c) {
             if (dcls) TRY(copy_d2d(c, dcls, tmp, (size_t)E * 4, "hy_backward"));
         }
         TRY(th_tokens_to_patches(Y.GT, G[0], B, NT, E, st, err));
-        TRY(linear_bwd(c, G[0], Y.blk.back().out, c.W(ENC + "patch_embed.proj.weight"), Mp, E, 1024, Y.GR, nullptr, c.Gd(ENC + "patch_embed.proj.weight"),
-                       c.Gd(ENC + "patch_embed.proj.bias")));
+        TRY(linear_bwd(c, G[0], Y.blk.back().out, c.W(P.pe.w), Mp, E, 1024, Y.GR, nullptr, c.Gd(P.pe.w),
+                       c.Gd(P.pe.b)));
     }
     // ---- ResNetV2 stages, last block -> first ----
     int stage = 2, cnt = a.rn_layers[2];
     for (int bi = (int)Y.blk.size() - 1; bi >= 0; --bi) {
         RnBlkT& b = Y.blk[bi];
-        const std::string& k = b.key;
-        const size_t Min = (size_t)B * b.rin * b.rin, Mout = (size_t)B * b.rout * b.rout;
-        if (stage < 2 && cnt == a.rn_layers[stage]) TRY(tr_axpy(Y.GR, T.DF[stage], Mout * b.cout, st, err));   // hooked stage output
+        const RnBlockP& p = P.rn[bi];
+        const size_t Min = (size_t)B * p.rin * p.rin, Mout = (size_t)B * p.rout * p.rout;
+        if (stage < 2 && cnt == a.rn_layers[stage]) TRY(tr_axpy(Y.GR, T.DF[stage], Mout * p.cout, st, err));   // hooked stage output
         // out = relu(GN3(conv3(t2)) + shortcut)
-        TRY(tr_relu_bwd(Y.GR, b.out, nullptr, G[0], Mout * b.cout, st, err));                       // G0 = d (sum)
-        TRY(th_gn_bwd(G[0], b.c3_raw, b.c3_stats, c.W(k + "norm3.weight"), c.W(k + "norm3.bias"), G[1], c.Gd(k + "norm3.weight"), c.Gd(k + "norm3.bias"), T.S_col, B,
-                      b.rout * b.rout, b.cout, b.cout / 32, 0, st, err));
-        TRY(linear_bwd(c, G[1], b.t2, b.w_c3, Mout, b.cout, b.mid, G[2], nullptr, c.Gd(k + "conv3.weight") ? T.S_dw : nullptr, nullptr));
-        TRY(ws_grad(k + "conv3.weight", b.w_c3, b.cout, b.mid, 1, b.mid));
-        TRY(th_gn_bwd(G[2], b.c2_raw, b.c2_stats, c.W(k + "norm2.weight"), c.W(k + "norm2.bias"), G[2], c.Gd(k + "norm2.weight"), c.Gd(k + "norm2.bias"), T.S_col, B,
-                      b.rout * b.rout, b.mid, b.mid / 32, 1, st, err));
-        TRY(conv_gen_bwd(c, G[2], b.t1, b.w_c2, b.rin, b.rout, b.mid, b.mid, b.stride, b.stride == 1 ? 1 : 0, G[1], c.Gd(k + "conv2.weight") ? T.S_dw : nullptr, nullptr));
-        TRY(ws_grad(k + "conv2.weight", b.w_c2, b.mid, b.mid, 3, 9 * b.mid));
-        TRY(th_gn_bwd(G[1], b.c1_raw, b.c1_stats, c.W(k + "norm1.weight"), c.W(k + "norm1.bias"), G[1], c.Gd(k + "norm1.weight"), c.Gd(k + "norm1.bias"), T.S_col, B,
-                      b.rin * b.rin, b.mid, b.mid / 32, 1, st, err));
-        TRY(linear_bwd(c, G[1], b.xin, b.w_c1, Min, b.mid, b.cin, G[3], nullptr, c.Gd(k + "conv1.weight") ? T.S_dw : nullptr, nullptr));   // G3 = d xin (conv path)
-        TRY(ws_grad(k + "conv1.weight", b.w_c1, b.mid, b.cin, 1, b.cin));
-        if (!b.proj) {
-            TRY(tr_axpy(G[3], G[0], Min * b.cin, st, err));                                        // identity shortcut
+        TRY(tr_relu_bwd(Y.GR, b.out, nullptr, G[0], Mout * p.cout, st, err));                       // G0 = d (sum)
+        TRY(th_gn_bwd(G[0], b.c3_raw, b.c3_stats, c.W(p.n3.g), c.W(p.n3.b), G[1], c.Gd(p.n3.g), c.Gd(p.n3.b), T.S_col, B,
+                      p.rout * p.rout, p.cout, p.cout / 32, 0, st, err));
+        TRY(linear_bwd(c, G[1], b.t2, b.w_c3, Mout, p.cout, p.mid, G[2], nullptr, c.Gd(p.c3_w) ? T.S_dw : nullptr, nullptr));
+        TRY(ws_grad(p.c3_w, b.w_c3, p.cout, p.mid, 1, p.mid));
+        TRY(th_gn_bwd(G[2], b.c2_raw, b.c2_stats, c.W(p.n2.g), c.W(p.n2.b), G[2], c.Gd(p.n2.g), c.Gd(p.n2.b), T.S_col, B,
+                      p.rout * p.rout, p.mid, p.mid / 32, 1, st, err));
+        TRY(conv_gen_bwd(c, G[2], b.t1, b.w_c2, p.rin, p.rout, p.mid, p.mid, p.stride, p.stride == 1 ? 1 : 0, G[1], c.Gd(p.c2_w) ? T.S_dw : nullptr, nullptr));
+        TRY(ws_grad(p.c2_w, b.w_c2, p.mid, p.mid, 3, 9 * p.mid));
+        TRY(th_gn_bwd(G[1], b.c1_raw, b.c1_stats, c.W(p.n1.g), c.W(p.n1.b), G[1], c.Gd(p.n1.g), c.Gd(p.n1.b), T.S_col, B,
+                      p.rin * p.rin, p.mid, p.mid / 32, 1, st, err));
+        TRY(linear_bwd(c, G[1], b.xin, b.w_c1, Min, p.mid, p.cin, G[3], nullptr, c.Gd(p.c1_w) ? T.S_dw : nullptr, nullptr));   // G3 = d xin (conv path)
+        TRY(ws_grad(p.c1_w, b.w_c1, p.mid, p.cin, 1, p.cin));
+        if (!p.proj) {
+            TRY(tr_axpy(G[3], G[0], Min * p.cin, st, err));                                        // identity shortcut
         } else {
-            TRY(th_gn_bwd(G[0], b.ds_raw, b.ds_stats, c.W(k + "downsample.norm.weight"), c.W(k + "downsample.norm.bias"), G[2], c.Gd(k + "downsample.norm.weight"),
-                          c.Gd(k + "downsample.norm.bias"), T.S_col, B, b.rout * b.rout, b.cout, b.cout / 32, 0, st, err));
+            TRY(th_gn_bwd(G[0], b.ds_raw, b.ds_stats, c.W(p.ds_n.g), c.W(p.ds_n.b), G[2], c.Gd(p.ds_n.g),
+                          c.Gd(p.ds_n.b), T.S_col, B, p.rout * p.rout, p.cout, p.cout / 32, 0, st, err));
             const float* xs = b.xin;
-            if (b.stride != 1) { TRY(th_stride_gather(b.xin, Y.xg, B, b.rin, b.rout, b.cin, b.stride, st, err)); xs = Y.xg; }
-            TRY(linear_bwd(c, G[2], xs, b.w_ds, Mout, b.cout, b.cin, G[1], nullptr, c.Gd(k + "downsample.conv.weight") ? T.S_dw : nullptr, nullptr));
-            TRY(ws_grad(k + "downsample.conv.weight", b.w_ds, b.cout, b.cin, 1, b.cin));
-            if (b.stride == 1) TRY(tr_axpy(G[3], G[1], Min * b.cin, st, err));
-            else TRY(th_stride_scatter_add(G[1], G[3], B, b.rin, b.rout, b.cin, b.stride, st, err));
+            if (p.stride != 1) { TRY(th_stride_gather(b.xin, Y.xg, B, p.rin, p.rout, p.cin, p.stride, st, err)); xs = Y.xg; }
+            TRY(linear_bwd(c, G[2], xs, b.w_ds, Mout, p.cout, p.cin, G[1], nullptr, c.Gd(p.ds_w) ? T.S_dw : nullptr, nullptr));
+            TRY(ws_grad(p.ds_w, b.w_ds, p.cout, p.cin, 1, p.cin));
+            if (p.stride == 1) TRY(tr_axpy(G[3], G[1], Min * p.cin, st, err));
+            else TRY(th_stride_scatter_add(G[1], G[3], B, p.rin, p.rout, p.cin, p.stride, st, err));
         }
-        TRY(copy_d2d(c, Y.GR, G[3], Min * b.cin * 4, "hy_backward"));
+        TRY(copy_d2d(c, Y.GR, G[3], Min * p.cin * 4, "hy_backward"));
         if (--cnt == 0 && stage > 0) { --stage; cnt = a.rn_layers[stage]; }
     }
     // ---- stem ----
     {
-        const std::string bb = ENC + "patch_embed.backbone.";
         const int H1 = a.img / 2;
         const size_t M1s = (size_t)B * H1 * H1;
-        float* dwk = c.Gd(bb + "stem.conv.weight");
-        float* dg = c.Gd(bb + "stem.norm.weight");
-        float* dbt = c.Gd(bb + "stem.norm.bias");
+        float* dwk = c.Gd(P.stem_w);
+        float* dg = c.Gd(P.stem_n.g);
+        float* dbt = c.Gd(P.stem_n.b);
         if (dwk || dg || dbt) {
-            TRY(th_maxpool_bwd(Y.GR, Y.stem_raw, Y.stem_stats, c.W(bb + "stem.norm.weight"), c.W(bb + "stem.norm.bias"), Y.pool_idx, G[0], B, H1, a.stem_ch, a.stem_ch / 32, st,
+            TRY(th_maxpool_bwd(Y.GR, Y.stem_raw, Y.stem_stats, c.W(P.stem_n.g), c.W(P.stem_n.b), Y.pool_idx, G[0], B, H1, a.stem_ch, a.stem_ch / 32, st,
                                err));
-            TRY(th_gn_bwd(G[0], Y.stem_raw, Y.stem_stats, c.W(bb + "stem.norm.weight"), c.W(bb + "stem.norm.bias"), G[0], dg, dbt, T.S_col, B, H1 * H1, a.stem_ch,
+            TRY(th_gn_bwd(G[0], Y.stem_raw, Y.stem_stats, c.W(P.stem_n.g), c.W(P.stem_n.b), G[0], dg, dbt, T.S_col, B, H1 * H1, a.stem_ch,
                           a.stem_ch / 32, 1, st, err));
             if (dwk) {
                 TRY(linear_bwd(c, G[0], Y.a0, nullptr, M1s, a.stem_ch, 160, nullptr, nullptr, T.S_dw, nullptr));
-                TRY(th_ws_bwd(T.S_dw, Y.w_stem, c.W(bb + "stem.conv.weight"), dwk, a.stem_ch, 3, 7, 160, kWsEps, st, err));
+                TRY(th_ws_bwd(T.S_dw, Y.w_stem, c.W(P.stem_w), dwk, a.stem_ch, 3, 7, 160, kWsEps, st, err));
             }
         }
     }

@@ -24,11 +24,6 @@ struct TArena {
     }
 };
 
-static const std::string ENC = "depth_net.pretrained.model.";
-static const std::string HYB = "depth_net.pretrained.";
-static const std::string SCR = "depth_net.scratch.";
-inline std::string blk_key(int s, int j) { return ENC + "layers." + std::to_string(s) + ".blocks." + std::to_string(j) + "."; }
-
 constexpr size_t kTrainSkPartFloats = (size_t)8 << 20;   // 32 MB of f32 split-K partials
 constexpr size_t kTrainSkCountWords = 4096;
 constexpr size_t kTrainTnArenaFloats = (size_t)160 << 20;   // 640 MB: the weight-gradient partials of one backward pass wait here for the batched sum (train.h TnDefer); flushed when full
@@ -42,9 +37,6 @@ struct BlkT {
 
 // ViT-hybrid encoder tape (train_hybrid_step.cpp)
 struct RnBlkT {
-    int cin, cout, mid, stride, rin, rout;
-    bool proj;
-    std::string key;
     const float* xin;                           // [B*rin*rin][cin]
     float *w_ds, *w_c1, *w_c2, *w_c3;           // standardised weights, tap-major
     float *ds_raw, *ds_stats, *c1_raw, *c1_stats, *t1 /*halo*/, *c2_raw, *c2_stats, *t2, *c3_raw, *c3_stats, *out;
@@ -110,8 +102,8 @@ struct Ctx {
     std::unordered_set<const void*> grad_ptrs;   // the bound parameter-gradient buffers: only sums that land THERE may wait (a gradient written into scratch is read by its caller's next launch)
     bool may_defer(const float* dW, const float* db) const { return tn.arena && grad_ptrs.count(dW) && (!db || grad_ptrs.count(db)); }
     void arm_defer(float* arena, size_t cap) { tn.arena = arena; tn.cap = cap; for (const auto& w : h.weights) if (w.grad) grad_ptrs.insert(w.grad); }
-    const float* W(const std::string& key) const { return h.weights[h.index.at(key)].ptr; }
-    float* Gd(const std::string& key) const { return h.weights[h.index.at(key)].grad; }
+    const float* W(PRef r) const { return h.W(r); }
+    float* Gd(PRef r) const { return h.G(r); }
 };
 
 #define TRY(call) do { if (call) return 1; } while (0)
@@ -165,7 +157,7 @@ int ln_bwd(Ctx& c, const float* y, const float* g, const float* dout, float* dy,
 int ln_bwd_on(float* s_col, hipStream_t st, std::string& err, const float* y, const float* g, const float* dout, float* dy, float* xhat, size_t M, int C, float* dg,
               float* dbeta, float eps);
 IgemmDesc conv_desc(const void* X, int Cin, const void* Wt, int N, int r, int B);
-bool any_grad(const Handle& h, const std::string& prefix);
+bool any_grad(const Handle& h, Span s);   // is a gradient bound to any tensor of the span?
 
 // train_hybrid_step.cpp
 // Backward of a 3x3 convolution with tap-major weights Wtap [N][9][C] over a zero-haloed input [B][Hi+2][Hi+2][C], output Ho x Ho; dWtap_out [N][9][C]

@@ -472,9 +472,9 @@ IgemmDesc conv_desc(const void* X, int Cin, const void* Wt, int N, int r, int B)
     return d;
 }
 
-bool any_grad(const Handle& h, const std::string& prefix) {
-    for (const auto& w : h.weights)
-        if (w.grad && w.key.compare(0, prefix.size(), prefix) == 0) return true;
+bool any_grad(const Handle& h, Span s) {
+    for (int i = s.lo; i < s.hi; ++i)
+        if (h.weights[i].grad) return true;
     return false;
 }
 
@@ -648,10 +648,11 @@ int train_workspace_tensor(Handle& h, int B, const char* name, size_t* byte_offs
             int i = -1, used = 0;
             if (sscanf(k.c_str() + 6, "%d%n", &i, &used) == 1 && i >= 0 && i < (int)Y.blk.size()) {
                 const RnBlkT& b = Y.blk[i];
+                const RnBlockP& g = h.params.hy.rn[i];
                 const std::string part = k.substr(6 + used);
-                if (part == ".t1") { p = b.t1; n = (size_t)B * (b.rin + 2) * (b.rin + 2) * b.mid; }
-                else if (part == ".t2") { p = b.t2; n = (size_t)B * b.rout * b.rout * b.mid; }
-                else if (part == ".out") { p = b.out; n = (size_t)B * b.rout * b.rout * b.cout; }
+                if (part == ".t1") { p = b.t1; n = (size_t)B * (g.rin + 2) * (g.rin + 2) * g.mid; }
+                else if (part == ".t2") { p = b.t2; n = (size_t)B * g.rout * g.rout * g.mid; }
+                else if (part == ".out") { p = b.out; n = (size_t)B * g.rout * g.rout * g.cout; }
             }
         }
     }
@@ -694,6 +695,7 @@ int train_forward(Handle& h, const float* x, int B, float* inv, float* seg, void
     carve(h, B, ar, T);
     T.dropout_p = dropout_p;
     Ctx c{h, T, B, st, err};
+    const ModelP& P = h.params;
     const int F = h.cfg.features;
     {
         hipError_t e = hipMemsetAsync(static_cast<char*>(ws) + T.halo_lo, 0, T.halo_hi - T.halo_lo, st);
@@ -704,12 +706,12 @@ int train_forward(Handle& h, const float* x, int B, float* inv, float* seg, void
     const int G = a.grid(), C0 = a.embed;
     const size_t M0 = (size_t)B * G * G;
     TRY(tr_patch_im2col(x, T.patches, B, a.img, st, err));
-    TRY(tr_pad_cols(c.W(ENC + "patch_embed.proj.weight"), T.pe_wpad, C0, 48, 64, st, err));
+    TRY(tr_pad_cols(c.W(P.swin.patch.w), T.pe_wpad, C0, 48, 64, st, err));
     {
         IgemmDesc d;
-        d.X = T.patches; d.Wt = T.pe_wpad; d.M = (int)M0; d.N = C0; d.Cin = 64; d.ldx = 64; d.bias = c.W(ENC + "patch_embed.proj.bias"); d.out_f32 = T.pe_pre;
+        d.X = T.patches; d.Wt = T.pe_wpad; d.M = (int)M0; d.N = C0; d.Cin = 64; d.ldx = 64; d.bias = c.W(P.swin.patch.b); d.out_f32 = T.pe_pre;
         TRY(gemm_fwd(c, d, M0 * 64, (size_t)C0 * 64));
-        TRY(launch_ln_residual(T.pe_pre, c.W(ENC + "patch_embed.norm.weight"), c.W(ENC + "patch_embed.norm.bias"), T.x0, nullptr, nullptr, nullptr, 0, (int)M0, C0, 0, G, 0,
+        TRY(launch_ln_residual(T.pe_pre, c.W(P.swin.patch_norm.g), c.W(P.swin.patch_norm.b), T.x0, nullptr, nullptr, nullptr, 0, (int)M0, C0, 0, G, 0,
                                st, err));
     }
     const float* xcur = T.x0;
@@ -719,7 +721,7 @@ int train_forward(Handle& h, const float* x, int B, float* inv, float* seg, void
         const int C = a.dim(s), res = a.res(s), M = B * res * res, wsz = a.ws(s), H = a.heads[s];
         for (int j = 0; j < a.depths[s]; ++j) {
             BlkT& b = T.blk[s][j];
-            const std::string k = blk_key(s, j);
+            const SwinBlockP& p = P.swin.blk[s][j];
             b.xin = xcur;
             // stochastic depth (timm DropPath on both residual branches; rate rising linearly over the blocks): per-sample scales for this block
             const float dp_p = nblk_total > 1 ? h.train_drop_path * (float)blk_index / (float)(nblk_total - 1) : 0.f;
@@ -729,58 +731,56 @@ int train_forward(Handle& h, const float* x, int B, float* inv, float* seg, void
                 TRY(tr_drop_path_fill(b.dp + B, B, dp_p, seed, 2u * (unsigned)blk_index + 1u, st, err));
             }
             ++blk_index;
-            TRY(launch_qkv_bias(c.W(k + "attn.q_bias"), c.W(k + "attn.v_bias"), b.qkv_bias, C, st, err));
-            TRY(launch_logit_scale(c.W(k + "attn.logit_scale"), b.scale, H, st, err));
-            TRY(launch_cpb_table(c.W(k + "attn.cpb_mlp.0.weight"), c.W(k + "attn.cpb_mlp.0.bias"), c.W(k + "attn.cpb_mlp.2.weight"), b.table, wsz, a.pretrained_window[s], H,
+            TRY(launch_qkv_bias(c.W(p.q_bias), c.W(p.v_bias), b.qkv_bias, C, st, err));
+            TRY(launch_logit_scale(c.W(p.logit_scale), b.scale, H, st, err));
+            TRY(launch_cpb_table(c.W(p.cpb0_w), c.W(p.cpb0_b), c.W(p.cpb2_w), b.table, wsz, a.pretrained_window[s], H,
                                  st, err));
             TRY(launch_attn_bias(b.table, b.bias_acc, wsz, H, st, err));
             IgemmDesc d;
-            d.X = b.xin; d.Wt = c.W(k + "attn.qkv.weight"); d.M = M; d.N = 3 * C; d.Cin = C; d.ldx = C; d.bias = b.qkv_bias; d.out_f32 = b.qkv;
+            d.X = b.xin; d.Wt = c.W(p.qkv_w); d.M = M; d.N = 3 * C; d.Cin = C; d.ldx = C; d.bias = b.qkv_bias; d.out_f32 = b.qkv;
             TRY(gemm_fwd(c, d, (size_t)M * C, (size_t)3 * C * C));
             TRY(launch_window_attention_f32(b.qkv, b.bias_acc, b.table, b.scale, b.attn, B, res, wsz, a.shift(s, j), H, st, err));
             d = IgemmDesc();
-            d.X = b.attn; d.Wt = c.W(k + "attn.proj.weight"); d.M = M; d.N = C; d.Cin = C; d.ldx = C; d.bias = c.W(k + "attn.proj.bias"); d.out_f32 = b.a_pre;
+            d.X = b.attn; d.Wt = c.W(p.proj.w); d.M = M; d.N = C; d.Cin = C; d.ldx = C; d.bias = c.W(p.proj.b); d.out_f32 = b.a_pre;
             TRY(gemm_fwd(c, d, (size_t)M * C, (size_t)C * C));
             TRY(copy_d2d(c, b.x1, b.xin, (size_t)M * C * 4, "train_forward copy"));
-            TRY(launch_ln_residual(b.a_pre, c.W(k + "norm1.weight"), c.W(k + "norm1.bias"), b.x1, nullptr, nullptr, nullptr, 0, M, C, 1, res, 0, st, err,
+            TRY(launch_ln_residual(b.a_pre, c.W(p.n1.g), c.W(p.n1.b), b.x1, nullptr, nullptr, nullptr, 0, M, C, 1, res, 0, st, err,
                                    dp_on ? b.dp : nullptr, res * res));
             d = IgemmDesc();
-            d.X = b.x1; d.Wt = c.W(k + "mlp.fc1.weight"); d.M = M; d.N = 4 * C; d.Cin = C; d.ldx = C; d.bias = c.W(k + "mlp.fc1.bias"); d.act = ACT_GELU;
+            d.X = b.x1; d.Wt = c.W(p.fc1.w); d.M = M; d.N = 4 * C; d.Cin = C; d.ldx = C; d.bias = c.W(p.fc1.b); d.act = ACT_GELU;
             d.out_f32 = b.hpre; d.out_op = b.hact;
             TRY(gemm_fwd(c, d, (size_t)M * C, (size_t)4 * C * C));
             d = IgemmDesc();
-            d.X = b.hact; d.Wt = c.W(k + "mlp.fc2.weight"); d.M = M; d.N = C; d.Cin = 4 * C; d.ldx = 4 * C; d.bias = c.W(k + "mlp.fc2.bias"); d.out_f32 = b.m_pre;
+            d.X = b.hact; d.Wt = c.W(p.fc2.w); d.M = M; d.N = C; d.Cin = 4 * C; d.ldx = 4 * C; d.bias = c.W(p.fc2.b); d.out_f32 = b.m_pre;
             TRY(gemm_fwd(c, d, (size_t)M * 4 * C, (size_t)4 * C * C));
             TRY(copy_d2d(c, b.xout, b.x1, (size_t)M * C * 4, "train_forward copy"));
-            TRY(launch_ln_residual(b.m_pre, c.W(k + "norm2.weight"), c.W(k + "norm2.bias"), b.xout, nullptr, nullptr, j == a.hooks[s] ? T.feat[s] : nullptr, 0, M, C, 1, res, 0,
+            TRY(launch_ln_residual(b.m_pre, c.W(p.n2.g), c.W(p.n2.b), b.xout, nullptr, nullptr, j == a.hooks[s] ? T.feat[s] : nullptr, 0, M, C, 1, res, 0,
                                    st, err, dp_on ? b.dp + B : nullptr, res * res));
             xcur = b.xout;
         }
         if (s < 3) {
-            const std::string dk = ENC + "layers." + std::to_string(s) + ".downsample.";
+            const MergeP& mp = P.swin.merge[s];
             TRY(launch_merge_gather(xcur, T.mg[s], B, res, C, 4, st, err));
             IgemmDesc d;
-            d.X = T.mg[s]; d.Wt = c.W(dk + "reduction.weight"); d.M = M / 4; d.N = 2 * C; d.Cin = 4 * C; d.ldx = 4 * C; d.out_f32 = T.mr_pre[s];
+            d.X = T.mg[s]; d.Wt = c.W(mp.red_w); d.M = M / 4; d.N = 2 * C; d.Cin = 4 * C; d.ldx = 4 * C; d.out_f32 = T.mr_pre[s];
             TRY(gemm_fwd(c, d, (size_t)M * C, (size_t)8 * C * C));
-            TRY(launch_ln_residual(T.mr_pre[s], c.W(dk + "norm.weight"), c.W(dk + "norm.bias"), T.mx[s], nullptr, nullptr, nullptr, 0, M / 4, 2 * C, 0, res / 2, 0, st, err));
+            TRY(launch_ln_residual(T.mr_pre[s], c.W(mp.norm.g), c.W(mp.norm.b), T.mx[s], nullptr, nullptr, nullptr, 0, M / 4, 2 * C, 0, res / 2, 0, st, err));
             xcur = T.mx[s];
         }
     }
     }
     // ---------------- decoder ----------------
     for (int l = 0; l < 4; ++l) {
-        TRY(launch_conv_w(c.W(SCR + "layer" + std::to_string(l + 1) + "_rn.weight"), nullptr, T.w_lrn[l], 1, 0, F, a.fdim(l), st, err));
-        const std::string rb = SCR + "refinenet" + std::to_string(l + 1) + ".";
+        TRY(launch_conv_w(c.W(P.layer_rn[l]), nullptr, T.w_lrn[l], 1, 0, F, a.fdim(l), st, err));
         for (int u = 0; u < 2; ++u) {
             if (l == 3 && u == 0) continue;
-            const std::string ub = rb + "resConfUnit" + std::to_string(u + 1) + ".";
-            TRY(launch_conv_w(c.W(ub + "conv1.weight"), nullptr, T.w_rcu[l][u][0], 1, 0, F, F, st, err));
-            TRY(launch_conv_w(c.W(ub + "conv2.weight"), nullptr, T.w_rcu[l][u][1], 1, 0, F, F, st, err));
+            TRY(launch_conv_w(c.W(P.refine[l].rcu[u].c1.w), nullptr, T.w_rcu[l][u][0], 1, 0, F, F, st, err));
+            TRY(launch_conv_w(c.W(P.refine[l].rcu[u].c2.w), nullptr, T.w_rcu[l][u][1], 1, 0, F, F, st, err));
         }
     }
     for (int l = 3; l >= 0; --l) {
         const int r = a.fres(l), M = B * r * r;
-        const std::string rb = SCR + "refinenet" + std::to_string(l + 1) + ".";
+        const RefineP& R = P.refine[l];
         {
             IgemmDesc d = conv_desc(T.feat[l], a.fdim(l), T.w_lrn[l], F, r, B);
             d.out_f32 = T.lrn_raw[l]; d.out_op = T.lrn_relu[l]; d.out_halo = 1; d.act = ACT_RELU;
@@ -789,12 +789,12 @@ int train_forward(Handle& h, const float* x, int B, float* inv, float* seg, void
         const float* fused_raw = T.lrn_raw[l];
         const float* fused_relu = T.lrn_relu[l];
         if (l < 3) {
-            const std::string ub = rb + "resConfUnit1.";
+            const RcuP& ub = R.rcu[0];
             IgemmDesc d = conv_desc(T.lrn_relu[l], F, T.w_rcu[l][0][0], F, r, B);
-            d.bias = c.W(ub + "conv1.bias"); d.act = ACT_RELU; d.out_op = T.t1[l]; d.out_halo = 1;
+            d.bias = c.W(ub.c1.b); d.act = ACT_RELU; d.out_op = T.t1[l]; d.out_halo = 1;
             TRY(gemm_fwd(c, d, Halo{r, r, F}.elems(B), (size_t)F * 9 * F));
             d = conv_desc(T.t1[l], F, T.w_rcu[l][0][1], F, r, B);
-            d.bias = c.W(ub + "conv2.bias"); d.res1 = T.lrn_raw[l];
+            d.bias = c.W(ub.c2.b); d.res1 = T.lrn_raw[l];
             d.res2 = T.oc[l + 1]; d.res2_h = a.fres(l + 1); d.res2_w = a.fres(l + 1);
             d.out_f32 = T.out_raw[l]; d.out_op = T.out_relu[l]; d.out_halo = 1; d.act = ACT_RELU;
             TRY(gemm_fwd(c, d, Halo{r, r, F}.elems(B), (size_t)F * 9 * F));
@@ -802,17 +802,17 @@ int train_forward(Handle& h, const float* x, int B, float* inv, float* seg, void
             fused_relu = T.out_relu[l];
         }
         {
-            const std::string ub = rb + "resConfUnit2.";
+            const RcuP& ub = R.rcu[1];
             IgemmDesc d = conv_desc(fused_relu, F, T.w_rcu[l][1][0], F, r, B);
-            d.bias = c.W(ub + "conv1.bias"); d.act = ACT_RELU; d.out_op = T.t2[l]; d.out_halo = 1;
+            d.bias = c.W(ub.c1.b); d.act = ACT_RELU; d.out_op = T.t2[l]; d.out_halo = 1;
             TRY(gemm_fwd(c, d, Halo{r, r, F}.elems(B), (size_t)F * 9 * F));
             d = conv_desc(T.t2[l], F, T.w_rcu[l][1][1], F, r, B);
-            d.bias = c.W(ub + "conv2.bias"); d.res1 = fused_raw; d.out_f32 = T.u[l];
+            d.bias = c.W(ub.c2.b); d.res1 = fused_raw; d.out_f32 = T.u[l];
             TRY(gemm_fwd(c, d, Halo{r, r, F}.elems(B), (size_t)F * 9 * F));
         }
         {
             IgemmDesc d;
-            d.X = T.u[l]; d.Wt = c.W(rb + "out_conv.weight"); d.M = M; d.N = F; d.Cin = F; d.ldx = F; d.bias = c.W(rb + "out_conv.bias"); d.out_f32 = T.oc[l];
+            d.X = T.u[l]; d.Wt = c.W(R.out_conv.w); d.M = M; d.N = F; d.Cin = F; d.ldx = F; d.bias = c.W(R.out_conv.b); d.out_f32 = T.oc[l];
             TRY(gemm_fwd(c, d, (size_t)M * F, (size_t)F * F));
         }
         if (l == 0) TRY(launch_bilinear(T.oc[0], 0, nullptr, nullptr, T.path1, 1, 0, B, r, r, 2 * r, 2 * r, F, st, err));
@@ -820,28 +820,28 @@ int train_forward(Handle& h, const float* x, int B, float* inv, float* seg, void
     // ---------------- heads ----------------
     const int r1 = 2 * a.fres(0), r0 = 4 * a.fres(0);
     const size_t M1 = (size_t)B * r1 * r1, M0p = (size_t)B * r0 * r0;
-    TRY(launch_conv_w(c.W(SCR + "output_conv.0.weight"), nullptr, T.w_d0, 1, 0, F / 2, F, st, err));
-    TRY(launch_conv_w(c.W(SCR + "output_conv.2.weight"), nullptr, T.w_d2, 1, 0, 32, F / 2, st, err));
-    TRY(launch_conv_w(c.W("seg_head.0.weight"), nullptr, T.w_s0, 1, 0, F, F, st, err));
+    TRY(launch_conv_w(c.W(P.depth.c0.w), nullptr, T.w_d0, 1, 0, F / 2, F, st, err));
+    TRY(launch_conv_w(c.W(P.depth.c2.w), nullptr, T.w_d2, 1, 0, 32, F / 2, st, err));
+    TRY(launch_conv_w(c.W(P.seg.c0_w), nullptr, T.w_s0, 1, 0, F, F, st, err));
     {
         IgemmDesc d = conv_desc(T.path1, F, T.w_d0, F / 2, r1, B);
-        d.bias = c.W(SCR + "output_conv.0.bias"); d.out_f32 = T.d1;
+        d.bias = c.W(P.depth.c0.b); d.out_f32 = T.d1;
         TRY(gemm_fwd(c, d, Halo{r1, r1, F}.elems(B), (size_t)(F / 2) * 9 * F));
         TRY(launch_bilinear(T.d1, 0, nullptr, nullptr, T.d1u, 1, 0, B, r1, r1, r0, r0, F / 2, st, err));
         d = conv_desc(T.d1u, F / 2, T.w_d2, 32, r0, B);
-        d.bias = c.W(SCR + "output_conv.2.bias"); d.out_f32 = T.e;
+        d.bias = c.W(P.depth.c2.b); d.out_f32 = T.e;
         TRY(gemm_fwd(c, d, Halo{r0, r0, F / 2}.elems(B), (size_t)32 * 9 * (F / 2)));
-        TRY(tr_depth_tail_fwd(T.e, c.W(SCR + "output_conv.4.weight"), c.W(SCR + "output_conv.4.bias"), T.inv, M0p, 32, st, err));
+        TRY(tr_depth_tail_fwd(T.e, c.W(P.depth.c4.w), c.W(P.depth.c4.b), T.inv, M0p, 32, st, err));
         TRY(copy_d2d(c, inv, T.inv, M0p * 4, "train_forward inv"));
     }
     {
         IgemmDesc d = conv_desc(T.path1, F, T.w_s0, F, r1, B);
         d.out_f32 = T.c_raw;
         TRY(gemm_fwd(c, d, Halo{r1, r1, F}.elems(B), (size_t)F * 9 * F));
-        TRY(tr_bn_stats(T.c_raw, T.bn_stats, const_cast<float*>(c.W("seg_head.1.running_mean")), const_cast<float*>(c.W("seg_head.1.running_var")), T.S_col, F, M1, 1e-5f,
+        TRY(tr_bn_stats(T.c_raw, T.bn_stats, const_cast<float*>(c.W(P.seg.bn_mean)), const_cast<float*>(c.W(P.seg.bn_var)), T.S_col, F, M1, 1e-5f,
                         0.1f, st, err));
-        TRY(tr_bn_relu_dropout_fwd(T.c_raw, T.bn_stats, c.W("seg_head.1.weight"), c.W("seg_head.1.bias"), T.r, T.keep, M1, F, dropout_p, seed, st, err));
-        TRY(launch_seg_tail(T.r, 1, 0, c.W("seg_head.4.weight"), c.W("seg_head.4.bias"), T.logits, T.seg, B, r1, r1, h.cfg.sigmoid, st, err));
+        TRY(tr_bn_relu_dropout_fwd(T.c_raw, T.bn_stats, c.W(P.seg.bn.g), c.W(P.seg.bn.b), T.r, T.keep, M1, F, dropout_p, seed, st, err));
+        TRY(launch_seg_tail(T.r, 1, 0, c.W(P.seg.c4.w), c.W(P.seg.c4.b), T.logits, T.seg, B, r1, r1, h.cfg.sigmoid, st, err));
         TRY(copy_d2d(c, seg, T.seg, M0p * 3 * 4, "train_forward seg"));
     }
     return 0;
@@ -857,6 +857,7 @@ static int encoder_backward(Ctx& c) {
     std::string& err = c.err;
     float** G = T.G;
     if (a.hybrid) return hy_backward(c);
+    const ModelP& P = h.params;
     {
         const float* xcur = T.x0;
         for (int s = 0; s < 4; ++s) {
@@ -866,82 +867,67 @@ static int encoder_backward(Ctx& c) {
     }
     // ---------------- encoder, last stage -> first ----------------
     bool have = false;   // GX holds a gradient
-    // trainable parameters at or before (stage s, block j) in forward order?  The walk ends below the earliest one.
-    auto trains_upto = [&](int s, int j) {
-        if (any_grad(h, ENC + "patch_embed.")) return true;
-        for (int t = 0; t <= s; ++t) {
-            if (t < s && any_grad(h, ENC + "layers." + std::to_string(t) + ".")) return true;
-            if (t == s)
-                for (int i = 0; i <= j; ++i)
-                    if (any_grad(h, blk_key(s, i))) return true;
-        }
-        return false;
-    };
     for (int s = 3; s >= 0; --s) {
         const int C = a.dim(s), res = a.res(s), wsz = a.ws(s), H = a.heads[s];
         const size_t M = (size_t)B * res * res;
         for (int j = a.depths[s] - 1; j >= 0; --j) {
             BlkT& b = T.blk[s][j];
-            const std::string k = blk_key(s, j);
+            const SwinBlockP& p = P.swin.blk[s][j];
             if (j == a.hooks[s]) {
                 if (have) TRY(tr_axpy(T.GX, T.DF[s], M * C, st, err));
                 else TRY(copy_d2d(c, T.GX, T.DF[s], M * C * 4, "train_backward"));
                 have = true;
             }
             if (!have) continue;   // blocks after the last hooked one do not reach the outputs
-            if (!trains_upto(s, j)) return 0;
+            if (!any_grad(h, p.upto)) return 0;   // nothing trainable at or before this block in forward order: the walk ends below the earliest trainable tensor
             // xout = x1 + dp2 * LN2(m_pre)      (dp: the forward's per-sample DropPath scales; the gradient entering the branch is scaled alike)
             const bool dp_on = h.train_drop_path > 0.f;
             const float* g_mlp = T.GX;
             if (dp_on) { TRY(tr_scale_rows(T.GX, G[4], b.dp + B, M, C, res * res, st, err)); g_mlp = G[4]; }
-            TRY(ln_bwd(c, b.m_pre, c.W(k + "norm2.weight"), g_mlp, G[0], G[1], M, C, c.Gd(k + "norm2.weight"), c.Gd(k + "norm2.bias")));
-            TRY(linear_bwd(c, G[0], b.hact, c.W(k + "mlp.fc2.weight"), M, C, 4 * C, G[2], nullptr, c.Gd(k + "mlp.fc2.weight"), c.Gd(k + "mlp.fc2.bias")));
+            TRY(ln_bwd(c, b.m_pre, c.W(p.n2.g), g_mlp, G[0], G[1], M, C, c.Gd(p.n2.g), c.Gd(p.n2.b)));
+            TRY(linear_bwd(c, G[0], b.hact, c.W(p.fc2.w), M, C, 4 * C, G[2], nullptr, c.Gd(p.fc2.w), c.Gd(p.fc2.b)));
             TRY(tr_gelu_bwd(G[2], b.hpre, G[2], M * 4 * C, st, err));
-            TRY(linear_bwd(c, G[2], b.x1, c.W(k + "mlp.fc1.weight"), M, 4 * C, C, G[3], T.GX, c.Gd(k + "mlp.fc1.weight"), c.Gd(k + "mlp.fc1.bias")));   // G3 = d x1
+            TRY(linear_bwd(c, G[2], b.x1, c.W(p.fc1.w), M, 4 * C, C, G[3], T.GX, c.Gd(p.fc1.w), c.Gd(p.fc1.b)));   // G3 = d x1
             // x1 = xin + dp1 * LN1(a_pre)
             const float* g_att = G[3];
             if (dp_on) { TRY(tr_scale_rows(G[3], G[4], b.dp, M, C, res * res, st, err)); g_att = G[4]; }
-            TRY(ln_bwd(c, b.a_pre, c.W(k + "norm1.weight"), g_att, G[0], G[1], M, C, c.Gd(k + "norm1.weight"), c.Gd(k + "norm1.bias")));
-            TRY(linear_bwd(c, G[0], b.attn, c.W(k + "attn.proj.weight"), M, C, C, G[2], nullptr, c.Gd(k + "attn.proj.weight"), c.Gd(k + "attn.proj.bias")));
+            TRY(ln_bwd(c, b.a_pre, c.W(p.n1.g), g_att, G[0], G[1], M, C, c.Gd(p.n1.g), c.Gd(p.n1.b)));
+            TRY(linear_bwd(c, G[0], b.attn, c.W(p.proj.w), M, C, C, G[2], nullptr, c.Gd(p.proj.w), c.Gd(p.proj.b)));
             // train_attn.hip.  amp modes: the four products of the attention backward on 16-bit MFMAs too (autocast semantics); exact f32 and x3: exact products
             const OpFmt attn_fmt = op_is16(amp_fmt(c)) ? amp_fmt(c) : OpFmt::F32;
             TRY(tr_attention_bwd_mfma(b.qkv, b.attn, G[2], b.table, b.scale, T.dS, T.rowstat, T.dscale_part, G[4], B, res, wsz, a.shift(s, j), H, st, err, attn_fmt));
             {
-                float* dls = c.Gd(k + "attn.logit_scale");
-                float* dw0 = c.Gd(k + "attn.cpb_mlp.0.weight");
-                float* db0 = c.Gd(k + "attn.cpb_mlp.0.bias");
-                float* dw2 = c.Gd(k + "attn.cpb_mlp.2.weight");
+                float* dls = c.Gd(p.logit_scale);
+                float* dw0 = c.Gd(p.cpb0_w);
+                float* db0 = c.Gd(p.cpb0_b);
+                float* dw2 = c.Gd(p.cpb2_w);
                 if (dls || dw0 || db0 || dw2)
-                    TRY(tr_attn_param_grads(T.dS, T.dscale_part, b.table, c.W(k + "attn.logit_scale"), c.W(k + "attn.cpb_mlp.0.weight"), c.W(k + "attn.cpb_mlp.0.bias"),
-                                            c.W(k + "attn.cpb_mlp.2.weight"), T.dtable, T.dt, T.S_cpb, dls, dw0, db0, dw2, B * (res / wsz) * (res / wsz), wsz,
+                    TRY(tr_attn_param_grads(T.dS, T.dscale_part, b.table, c.W(p.logit_scale), c.W(p.cpb0_w), c.W(p.cpb0_b),
+                                            c.W(p.cpb2_w), T.dtable, T.dt, T.S_cpb, dls, dw0, db0, dw2, B * (res / wsz) * (res / wsz), wsz,
                                             a.pretrained_window[s], H, tr_attention_bwd_mfma_slots(wsz), st, err));
             }
             {
-                float* dq = c.Gd(k + "attn.q_bias");
-                float* dv = c.Gd(k + "attn.v_bias");
+                float* dq = c.Gd(p.q_bias);
+                float* dv = c.Gd(p.v_bias);
                 float* dbias = (dq || dv) ? T.S_vec : nullptr;
-                TRY(linear_bwd(c, G[4], b.xin, c.W(k + "attn.qkv.weight"), M, 3 * C, C, T.GX, G[3], c.Gd(k + "attn.qkv.weight"), dbias));
+                TRY(linear_bwd(c, G[4], b.xin, c.W(p.qkv_w), M, 3 * C, C, T.GX, G[3], c.Gd(p.qkv_w), dbias));
                 if (dbias) TRY(tr_qv_bias_grad(dbias, dq, dv, C, st, err));
             }
         }
         if (!have) continue;
-        {   // anything trainable in patch_embed or stages < s (their blocks and PatchMerging)?
-            bool below = any_grad(h, ENC + "patch_embed.");
-            for (int t = 0; t < s; ++t) below = below || any_grad(h, ENC + "layers." + std::to_string(t) + ".");
-            if (!below) return 0;
-        }
+        if (!any_grad(h, P.swin.below[s])) return 0;   // nothing trainable in patch_embed or stages < s (their blocks and PatchMerging)
         if (s > 0) {
             // x_s = LN(reduction(gather(x_{s-1})))   (timm PatchMerging of Swin-V2: reduction then norm)
             const int Cp = a.dim(s - 1);
-            const std::string dk = ENC + "layers." + std::to_string(s - 1) + ".downsample.";
-            TRY(ln_bwd(c, T.mr_pre[s - 1], c.W(dk + "norm.weight"), T.GX, G[0], G[1], M, C, c.Gd(dk + "norm.weight"), c.Gd(dk + "norm.bias")));
-            TRY(linear_bwd(c, G[0], T.mg[s - 1], c.W(dk + "reduction.weight"), M, C, 4 * Cp, G[2], nullptr, c.Gd(dk + "reduction.weight"), nullptr));
+            const MergeP& mp = P.swin.merge[s - 1];
+            TRY(ln_bwd(c, T.mr_pre[s - 1], c.W(mp.norm.g), T.GX, G[0], G[1], M, C, c.Gd(mp.norm.g), c.Gd(mp.norm.b)));
+            TRY(linear_bwd(c, G[0], T.mg[s - 1], c.W(mp.red_w), M, C, 4 * Cp, G[2], nullptr, c.Gd(mp.red_w), nullptr));
             TRY(tr_merge_scatter(G[2], T.GX, B, a.res(s - 1), Cp, st, err));
         } else {
             const int C0 = a.embed;
-            TRY(ln_bwd(c, T.pe_pre, c.W(ENC + "patch_embed.norm.weight"), T.GX, G[0], G[1], M, C0, c.Gd(ENC + "patch_embed.norm.weight"), c.Gd(ENC + "patch_embed.norm.bias")));
-            float* dw = c.Gd(ENC + "patch_embed.proj.weight");
-            TRY(linear_bwd(c, G[0], T.patches, T.pe_wpad, M, C0, 64, nullptr, nullptr, dw ? T.S_dw + kPeGradOffset : nullptr, c.Gd(ENC + "patch_embed.proj.bias")));
+            TRY(ln_bwd(c, T.pe_pre, c.W(P.swin.patch_norm.g), T.GX, G[0], G[1], M, C0, c.Gd(P.swin.patch_norm.g), c.Gd(P.swin.patch_norm.b)));
+            float* dw = c.Gd(P.swin.patch.w);
+            TRY(linear_bwd(c, G[0], T.patches, T.pe_wpad, M, C0, 64, nullptr, nullptr, dw ? T.S_dw + kPeGradOffset : nullptr, c.Gd(P.swin.patch.b)));
             if (dw) TRY(tr_pad_cols(T.S_dw + kPeGradOffset, dw, C0, 64, 48, st, err));
         }
     }
@@ -975,6 +961,7 @@ int train_backward(Handle& h, const float* x, int B, const float* d_inv, const f
     carve(h, B, ar, T);
     T.dropout_p = h.train_key.dropout_p;
     Ctx c{h, T, B, st, err};
+    const ModelP& P = h.params;
     c.arm_defer(T.tn_arena, kTrainTnArenaFloats);   // weight-gradient partials wait for ONE batched sum at the end of the pass (train.h TnDefer)
     TRY(stage_weights(c));
     auto pass = [&]() -> int {
@@ -982,54 +969,54 @@ int train_backward(Handle& h, const float* x, int B, const float* d_inv, const f
     float** G = T.G;
     const int r1 = 2 * a.fres(0), r0 = 4 * a.fres(0);
     const size_t M1 = (size_t)B * r1 * r1, M0p = (size_t)B * r0 * r0;
-    const bool enc_train = any_grad(h, HYB);   // "depth_net.pretrained.": the timm model and, for the hybrid, the act_postprocess read-outs
+    const bool enc_train = any_grad(h, P.encoder);   // depth_net.pretrained.*: the timm model and, for the hybrid, the act_postprocess read-outs
     // Frozen prefixes (freeze helpers of model/loss.py, PatchWiseInplace): the gradient stops flowing where nothing upstream is trainable
     bool lvl_own[4], lvl_side[4];   // level l: RCU2 / out_conv / anything coarser  |  RCU1 + layer_rn + encoder hook
     for (int l = 0; l < 4; ++l) {
-        const std::string rb = SCR + "refinenet" + std::to_string(l + 1) + ".";
-        lvl_own[l] = any_grad(h, rb + "out_conv") || any_grad(h, rb + "resConfUnit2");
-        lvl_side[l] = enc_train || any_grad(h, rb + "resConfUnit1") || any_grad(h, SCR + "layer" + std::to_string(l + 1) + "_rn");
+        const RefineP& R = P.refine[l];
+        lvl_own[l] = any_grad(h, R.out_conv_span) || any_grad(h, R.rcu_span[1]);
+        lvl_side[l] = enc_train || any_grad(h, R.rcu_span[0]) || any_grad(h, span_of(P.layer_rn[l]));
     }
     bool need_level[5];             // the gradient has to reach level l's out_conv output
     need_level[4] = false;
     for (int l = 3; l >= 0; --l) need_level[l] = lvl_own[l] || lvl_side[l] || need_level[l + 1];
     // ---------------- depth head ----------------
     {
-        TRY(tr_depth_tail_bwd(d_inv, T.inv, T.e, c.W(SCR + "output_conv.4.weight"), G[0], G[1], M0p, 32, st, err));
-        float* dw4 = c.Gd(SCR + "output_conv.4.weight");
-        float* db4 = c.Gd(SCR + "output_conv.4.bias");
+        TRY(tr_depth_tail_bwd(d_inv, T.inv, T.e, c.W(P.depth.c4.w), G[0], G[1], M0p, 32, st, err));
+        float* dw4 = c.Gd(P.depth.c4.w);
+        float* db4 = c.Gd(P.depth.c4.b);
         if (dw4 || db4) {
             TRY(tr_colsum(G[1], nullptr, T.S_vec, T.S_col, M0p, 33, 0, st, err));
             if (dw4) TRY(copy_d2d(c, dw4, T.S_vec, 32 * 4, "train_backward"));
             if (db4) TRY(copy_d2d(c, db4, T.S_vec + 32, 4, "train_backward"));
         }
-        TRY(conv3_bwd(c, G[0], T.d1u, c.W(SCR + "output_conv.2.weight"), r0, 32, F / 2, G[2], nullptr, c.Gd(SCR + "output_conv.2.weight"), c.Gd(SCR + "output_conv.2.bias")));
+        TRY(conv3_bwd(c, G[0], T.d1u, c.W(P.depth.c2.w), r0, 32, F / 2, G[2], nullptr, c.Gd(P.depth.c2.w), c.Gd(P.depth.c2.b)));
         TRY(tr_bilinear_bwd(G[2], G[3], B, r1, r1, r0, r0, F / 2, 0, st, err));
-        TRY(conv3_bwd(c, G[3], T.path1, c.W(SCR + "output_conv.0.weight"), r1, F / 2, F, need_level[0] ? T.GP : nullptr, nullptr, c.Gd(SCR + "output_conv.0.weight"),
-                      c.Gd(SCR + "output_conv.0.bias")));
+        TRY(conv3_bwd(c, G[3], T.path1, c.W(P.depth.c0.w), r1, F / 2, F, need_level[0] ? T.GP : nullptr, nullptr, c.Gd(P.depth.c0.w),
+                      c.Gd(P.depth.c0.b)));
     }
     // ---------------- seg head ----------------
     {
         TRY(tr_seg_act_bwd(d_seg, T.seg, G[0], B, 3, r0, h.cfg.sigmoid, st, err));
         TRY(tr_bilinear_bwd(G[0], G[1], B, r1, r1, r0, r0, 3, 0, st, err));   // d logits [M1][3]
-        if (float* dw = c.Gd("seg_head.4.weight")) TRY(tr_smallk_wgrad(G[1], T.r, dw, T.S_col, M1, F, 3, st, err));
-        if (float* db = c.Gd("seg_head.4.bias")) {
+        if (float* dw = c.Gd(P.seg.c4.w)) TRY(tr_smallk_wgrad(G[1], T.r, dw, T.S_col, M1, F, 3, st, err));
+        if (float* db = c.Gd(P.seg.c4.b)) {
             // colsum needs N >= 1: three columns
             TRY(tr_colsum(G[1], nullptr, db, T.S_col, M1, 3, 0, st, err));
         }
-        TRY(tr_smallk_dgrad(G[1], c.W("seg_head.4.weight"), G[2], M1, F, 3, st, err));
+        TRY(tr_smallk_dgrad(G[1], c.W(P.seg.c4.w), G[2], M1, F, 3, st, err));
         TRY(tr_bn_relu_dropout_bwd_pre(G[2], T.r, T.keep, G[0], M1 * F, T.dropout_p, st, err));
         TRY(tr_bn_xhat(T.c_raw, T.bn_stats, G[3], M1, F, st, err));
         float* dbeta = T.S_vec;
         float* dgamma = T.S_vec + F;
         TRY(tr_colsum(G[0], nullptr, dbeta, T.S_col, M1, F, 0, st, err));
         TRY(tr_colsum(G[0], G[3], dgamma, T.S_col, M1, F, 0, st, err));
-        if (float* p = c.Gd("seg_head.1.bias")) TRY(copy_d2d(c, p, dbeta, F * 4, "train_backward"));
-        if (float* p = c.Gd("seg_head.1.weight")) TRY(copy_d2d(c, p, dgamma, F * 4, "train_backward"));
-        TRY(tr_bn_bwd(G[0], T.c_raw, T.bn_stats, c.W("seg_head.1.weight"), dbeta, dgamma, G[2], M1, F, st, err));
+        if (float* p = c.Gd(P.seg.bn.b)) TRY(copy_d2d(c, p, dbeta, F * 4, "train_backward"));
+        if (float* p = c.Gd(P.seg.bn.g)) TRY(copy_d2d(c, p, dgamma, F * 4, "train_backward"));
+        TRY(tr_bn_bwd(G[0], T.c_raw, T.bn_stats, c.W(P.seg.bn.g), dbeta, dgamma, G[2], M1, F, st, err));
         // path_1's im2col^T is still in S_T2 from output_conv.0's weight gradient (same input image, nothing in between writes S_T2)
-        const bool xt_ready = c.Gd(SCR + "output_conv.0.weight") != nullptr;
-        TRY(conv3_bwd(c, G[2], T.path1, c.W("seg_head.0.weight"), r1, F, F, need_level[0] ? T.GP : nullptr, T.GP, c.Gd("seg_head.0.weight"), nullptr, xt_ready));
+        const bool xt_ready = c.Gd(P.depth.c0.w) != nullptr;
+        TRY(conv3_bwd(c, G[2], T.path1, c.W(P.seg.c0_w), r1, F, F, need_level[0] ? T.GP : nullptr, T.GP, c.Gd(P.seg.c0_w), nullptr, xt_ready));
     }
     if (!need_level[0]) return 0;
     TRY(tr_bilinear_bwd(T.GP, T.DOC, B, a.fres(0), a.fres(0), r1, r1, F, 0, st, err));
@@ -1037,15 +1024,15 @@ int train_backward(Handle& h, const float* x, int B, const float* d_inv, const f
     for (int l = 0; l < 4; ++l) {
         const int r = a.fres(l);
         const size_t M = (size_t)B * r * r;
-        const std::string rb = SCR + "refinenet" + std::to_string(l + 1) + ".";
-        TRY(linear_bwd(c, T.DOC, T.u[l], c.W(rb + "out_conv.weight"), M, F, F, G[0], nullptr, c.Gd(rb + "out_conv.weight"), c.Gd(rb + "out_conv.bias")));
+        const RefineP& R = P.refine[l];
+        TRY(linear_bwd(c, T.DOC, T.u[l], c.W(R.out_conv.w), M, F, F, G[0], nullptr, c.Gd(R.out_conv.w), c.Gd(R.out_conv.b)));
         const float* fused_raw = l < 3 ? T.out_raw[l] : T.lrn_raw[l];
         const float* fused_relu = l < 3 ? T.out_relu[l] : T.lrn_relu[l];
         {
-            const std::string ub = rb + "resConfUnit2.";
-            TRY(conv3_bwd(c, G[0], T.t2[l], c.W(ub + "conv2.weight"), r, F, F, G[1], nullptr, c.Gd(ub + "conv2.weight"), c.Gd(ub + "conv2.bias")));
+            const RcuP& ub = R.rcu[1];
+            TRY(conv3_bwd(c, G[0], T.t2[l], c.W(ub.c2.w), r, F, F, G[1], nullptr, c.Gd(ub.c2.w), c.Gd(ub.c2.b)));
             TRY(tr_relu_bwd_halo(G[1], T.t2[l], nullptr, G[1], B, r, r, F, st, err));
-            TRY(conv3_bwd(c, G[1], fused_relu, c.W(ub + "conv1.weight"), r, F, F, G[2], nullptr, c.Gd(ub + "conv1.weight"), c.Gd(ub + "conv1.bias")));
+            TRY(conv3_bwd(c, G[1], fused_relu, c.W(ub.c1.w), r, F, F, G[2], nullptr, c.Gd(ub.c1.w), c.Gd(ub.c1.b)));
             TRY(tr_relu_bwd(G[2], fused_raw, G[0], G[3], M * F, st, err));   // d fused_raw
         }
         const float* d_lrn = G[3];
@@ -1056,14 +1043,14 @@ int train_backward(Handle& h, const float* x, int B, const float* d_inv, const f
             continue;
         }
         if (l < 3) {
-            const std::string ub = rb + "resConfUnit1.";
-            TRY(conv3_bwd(c, G[3], T.t1[l], c.W(ub + "conv2.weight"), r, F, F, G[1], nullptr, c.Gd(ub + "conv2.weight"), c.Gd(ub + "conv2.bias")));
+            const RcuP& ub = R.rcu[0];
+            TRY(conv3_bwd(c, G[3], T.t1[l], c.W(ub.c2.w), r, F, F, G[1], nullptr, c.Gd(ub.c2.w), c.Gd(ub.c2.b)));
             TRY(tr_relu_bwd_halo(G[1], T.t1[l], nullptr, G[1], B, r, r, F, st, err));
-            TRY(conv3_bwd(c, G[1], T.lrn_relu[l], c.W(ub + "conv1.weight"), r, F, F, G[2], nullptr, c.Gd(ub + "conv1.weight"), c.Gd(ub + "conv1.bias")));
+            TRY(conv3_bwd(c, G[1], T.lrn_relu[l], c.W(ub.c1.w), r, F, F, G[2], nullptr, c.Gd(ub.c1.w), c.Gd(ub.c1.b)));
             TRY(tr_relu_bwd(G[2], T.lrn_raw[l], G[3], G[0], M * F, st, err));
             d_lrn = G[0];
         }
-        const std::string lk = SCR + "layer" + std::to_string(l + 1) + "_rn.weight";
+        const PRef lk = P.layer_rn[l];
         TRY(conv3_bwd(c, d_lrn, T.feat[l], c.W(lk), r, F, a.fdim(l), enc_train ? T.DF[l] : nullptr, nullptr, c.Gd(lk), nullptr));
     }
     if (!enc_train) return 0;

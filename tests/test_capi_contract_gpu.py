@@ -85,6 +85,23 @@ def test_errors_are_returned(model, gpu_device):
     assert eng.L.soccdpt_create(ctypes.byref(cfg), ctypes.byref(h)) != 0
 
 
+@pytest.mark.parametrize("backbone", ["swin2t16_256", "swin2b24_384", "vitb_rn50_384"])
+def test_weight_keys_are_the_consumed_state_dict(gpu_device, backbone):
+    """soccdpt_num_weights / soccdpt_weight_key list the state dict of the backbone without the tensors the forward never reads, in state-dict
+    order (the list tests/test_params_cpu.py holds the parameter table to).  Only creates handles: no kernel runs."""
+    from oracle import soccdpt_ref as R
+    from soccdpt_amd.lib import Engine, make_config
+    from tests.consumed_keys import consumed_shapes
+    cam, cfg = R.Camera(), R.ProjConfig()
+    c = make_config(backbone, 3, 256, False, False, cam.width, cam.height, cam.fx, cam.fy, cam.cx, cam.cy,
+                    cfg.grid_size, cfg.occupancy_shape(), cfg.pc_scale, cfg.pc_shift, cfg.correction_angle)
+    eng = Engine(c, gpu_device)
+    try:
+        assert eng.weight_keys() == [k for k, _ in consumed_shapes(backbone)]
+    finally:
+        eng.close()
+
+
 def test_training_entry_points_return_errors(gpu_device):
     """soccdpt_train_* contract: wrong precision, unbound weights, short workspace, a backward without its forward, a mismatching batch size
     and bad dropout probabilities are refused with a message (non-zero return), never executed; garbage in the workspace is harmless because
