@@ -28,6 +28,8 @@ unsigned long long& launch_counter() {
     static thread_local unsigned long long n = 0;
     return n;
 }
+// for the handle-less entry points defined outside this file (frame_pack.hip): what soccdpt_last_error(NULL) returns
+void set_last_error(const std::string& msg) { g_create_error = msg; }
 }  // namespace soccdpt
 
 static double occ_cells(const soccdpt_config& c) { return (double)c.grid[0] * c.grid[1] * c.grid[2] * c.num_classes; }

@@ -19,11 +19,16 @@ Deviations from the reference, all stated: the target size is the calibration fi
 calibration; the reference hard-codes that literal); y_seg is float32 0 / 1 rather than bool (what the criterion reads); uint16 / float32 disparity
 must be stored at camera size (OpenCV resizes those with float weights; without cv2 there is nothing to pin a resampling against, so none is
 guessed); byte parity of the two uint8 resizes with cv2.resize itself is not pinned for the same reason.  There is no CPU
-fallback: the items need the HIP library and a GPU."""
+fallback: the items need the HIP library and a GPU.
+
+`frame_pack=` (opt-in, datasets/frame_pack.py) takes the decode away as well: the recording's frames are read from one mapped
+file, the pool's threads copy them straight into the pinned staging buffers, label frames go up as palette indices and the targets are built from
+those (soccdpt_pack_targets).  Items and batches are bit-identical to the PNG path's."""
 from __future__ import annotations
 
 import bisect
 import os
+import warnings
 from collections import deque
 from concurrent.futures import ThreadPoolExecutor
 from typing import Callable, Dict, Iterable, List, Optional, Sequence, Tuple
@@ -32,6 +37,7 @@ import numpy as np
 import torch
 
 from .bdd_helper import DEFAULT_CALIB, DEFAULT_DATASET, BengaluruDepthDatasetIterator
+from .frame_pack import FramePack, FramePackError, open_current, pack_path
 
 color_2_class = {
     (0, 0, 0): 0,         # background
@@ -84,8 +90,10 @@ class _Staging:
     def __init__(self, ring: int = 4):
         self.ring, self.slots = ring, {}
 
-    def upload(self, arrays: Sequence[np.ndarray], device: torch.device) -> torch.Tensor:
-        """Equal-shaped host arrays -> one [n, ...] device tensor, copied from pinned memory on the current stream without blocking the host."""
+    def upload(self, arrays: Sequence[np.ndarray], device: torch.device, pool: Optional[ThreadPoolExecutor] = None) -> torch.Tensor:
+        """Equal-shaped host arrays -> one [n, ...] device tensor, copied from pinned memory on the current stream without blocking the host.  With a
+        pool, its threads copy one array each straight into their slice of the pinned buffer (np.copyto releases the GIL) and this thread only waits
+        for them: how the views of a frame pack's mapping are staged."""
         shape, dtype = (len(arrays),) + tuple(arrays[0].shape), torch.from_numpy(np.empty(0, arrays[0].dtype)).dtype
         slots = self.slots.setdefault((shape, dtype), deque())
         if len(slots) < self.ring:
@@ -94,8 +102,11 @@ class _Staging:
             buf, ev = slots.popleft()
             ev.synchronize()
         view = buf.numpy()
-        for i, a in enumerate(arrays):
-            np.copyto(view[i], a)
+        if pool is not None and len(arrays) > 1:
+            list(pool.map(np.copyto, [view[i] for i in range(len(arrays))], arrays))
+        else:
+            for i, a in enumerate(arrays):
+                np.copyto(view[i], a)
         out = buf.to(device, non_blocking=True)
         ev.record(torch.cuda.current_stream(device))
         slots.append((buf, ev))
@@ -109,7 +120,10 @@ class BDD_Dataset(BengaluruDepthDatasetIterator):
     to_camera_size = False                # only the combined class resizes its frames (bengaluru_driving_dataset.py:118-121)
 
     def __init__(self, dataset_path: str = DEFAULT_DATASET, settings_doc: str = DEFAULT_CALIB, transform: Callable = lambda x: x, device=None,
-                 workers: int = DEFAULT_WORKERS):
+                 workers: int = DEFAULT_WORKERS, frame_pack=None, frame_pack_required: bool = False):
+        """frame_pack: None reads the PNGs; True reads <recording>/<id>.sfp, a string <that directory>/<id>.sfp (datasets/frame_pack.py).  A pack that
+        is missing, truncated, of another version or older than its PNGs is not read: the dataset warns once, naming the file, and reads the PNGs;
+        with frame_pack_required it raises FramePackError instead."""
         super().__init__(dataset_path=dataset_path, settings_doc=settings_doc)
         assert transform is not None
         self.img_transform = transform
@@ -121,10 +135,52 @@ class BDD_Dataset(BengaluruDepthDatasetIterator):
         self.last_class_map: Optional[torch.Tensor] = None
         self._staging = _Staging()
         self._on_device: dict = {}
+        self.pack: Optional[FramePack] = None
+        if frame_pack is not None and frame_pack is not False:
+            try:
+                self.pack = open_current(self.dataset_path, frame_pack)
+            except FramePackError as e:
+                if frame_pack_required:
+                    raise
+                warnings.warn(f"{e}; reading the PNGs of {self.dataset_path} instead", RuntimeWarning, stacklevel=2)
 
     # ---- host half: runs in worker threads, touches no GPU ----
+    def _pack_row(self, key: int) -> dict:
+        """The CSV half of a frame dictionary from the pack, with the reader's bounds rules (bdd_helper.frame_paths)."""
+        if key > len(self):
+            raise IndexError("Out of bounds; key=", key)
+        if key < 0 or key == len(self):
+            raise KeyError(key)
+        csv_frame = dict(zip(self.csv_columns, self.csv_dat[key]))
+        return dict(csv_frame=csv_frame, **csv_frame)
+
     def read_frame(self, key: int) -> dict:
-        frame = super().read_frame(key)
+        """The reader's frame dictionary.  From a pack: the same keys and bytes, the arrays being read-only views of the mapping (seg_frame a copy
+        made by the host palette lookup)."""
+        if self.pack is None:
+            frame = super().read_frame(key)
+        else:
+            row, f = self._pack_row(key), self.pack.frame(key)
+            frame = {"rgb_frame": f["rgb"], "disparity_frame": f["disparity"], "seg_frame": self.pack.labels_rgb(key), "csv_frame": row.pop("csv_frame")}
+            frame.update(row)
+        return self._checked(frame, key)
+
+    def batch_frame(self, key: int) -> dict:
+        """What `assemble` takes for frame `key`: read_frame's dictionary, except that a pack with indexed labels hands over the indices themselves
+        (`seg_index`: u32 words, `seg_pack`: the FramePack) instead of looking the colours up on the host."""
+        if self.pack is None or self.pack.raw_labels:
+            frame = self.read_frame(key)
+        else:
+            row, f = self._pack_row(key), self.pack.frame(key)
+            frame = {"rgb_frame": f["rgb"], "disparity_frame": f["disparity"], "seg_index": f["labels"].view(np.int32), "seg_pack": self.pack,
+                     "csv_frame": row.pop("csv_frame")}
+            frame.update(row)
+            self._checked(frame, key)
+        if self.pack is not None:
+            frame["_pooled"] = True      # views of a mapping: staged by the pool's threads
+        return frame
+
+    def _checked(self, frame: dict, key: int) -> dict:
         d = frame["disparity_frame"]
         if self.to_camera_size and d.dtype != np.uint8 and tuple(d.shape) != (self.height, self.width):
             raise NotImplementedError(
@@ -135,7 +191,7 @@ class BDD_Dataset(BengaluruDepthDatasetIterator):
 
     def decode(self, indices: Iterable[int]) -> List[dict]:
         """The frame dictionaries of `indices`, decoded concurrently by the shared pool."""
-        return list(decode_pool(self.workers).map(self.read_frame, [int(i) for i in indices]))
+        return list(decode_pool(self.workers).map(self.batch_frame, [int(i) for i in indices]))
 
     # ---- device half: the caller's thread, the current stream ----
     def _cached(self, key, make):
@@ -156,7 +212,10 @@ class BDD_Dataset(BengaluruDepthDatasetIterator):
     def _upload(self, frames: List[dict], key: str) -> torch.Tensor:
         """frames[i][key], all of one shape and dtype -> [B, ...] on the device; at camera size afterwards when this class resizes."""
         arrays = [f[key] for f in frames]
-        t = self._staging.upload(arrays, self.device)
+        t = self._staging.upload(arrays, self.device, decode_pool(self.workers) if frames[0].get("_pooled") else None)
+        return t if key == "seg_index" else self._to_camera_size(t)
+
+    def _to_camera_size(self, t: torch.Tensor) -> torch.Tensor:
         if not self.to_camera_size:
             return t
         Hc, Wc = int(self.height), int(self.width)
@@ -173,7 +232,14 @@ class BDD_Dataset(BengaluruDepthDatasetIterator):
         """Decoded frames -> the item's tensors for the whole batch, on the current stream of self.device.  Frames stored alike (the sizes and the
         disparity format of one recording) go through one upload, one transform and one targets launch; a batch that mixes recordings stored
         differently is assembled group by group and put back into the batch's order."""
-        kind = lambda f: tuple((f[k].shape, f[k].dtype.str) for k in ("rgb_frame", "seg_frame", "disparity_frame"))
+        def kind(f):
+            if "seg_frame" in f:
+                labels = (f["seg_frame"].shape, f["seg_frame"].dtype.str)
+            elif "y_seg" in self.fields:      # indexed labels are alike when they share the frame size, k and the palette
+                labels = ("indexed", f["seg_pack"].shapes["labels"], f["seg_pack"].k, f["seg_pack"].palette.tobytes())
+            else:                             # not read: only their size counts, as for label frames
+                labels = (f["seg_pack"].shapes["labels"] + (3,), "|u1")
+            return ((f["rgb_frame"].shape, f["rgb_frame"].dtype.str), labels, (f["disparity_frame"].shape, f["disparity_frame"].dtype.str))
         groups: Dict[tuple, List[int]] = {}
         for pos, f in enumerate(frames):
             groups.setdefault(kind(f), []).append(pos)
@@ -191,8 +257,20 @@ class BDD_Dataset(BengaluruDepthDatasetIterator):
         return [self._ones(torch.Size([len(frames)]) + parts[0][k].shape[1:]) if name.startswith("mask") else merged([p[k] for p in parts])
                 for k, name in enumerate(self.fields)]
 
+    def _labels_from_indices(self, frames: List[dict]):
+        """Packed labels of frames stored alike -> (idx [B,words] on the device, pack) when they are stored at the size the targets are wanted at, else
+        (None, the label frames expanded and resized: soccdpt_pack_expand -> soccdpt_vis_resize), ready for soccdpt_data_targets."""
+        from ..lib import op_pack_expand
+        pack = frames[0]["seg_pack"]
+        idx = self._upload(frames, "seg_index")
+        Hl, Wl = pack.shapes["labels"]
+        if not self.to_camera_size or (Hl, Wl) == (int(self.height), int(self.width)):
+            return idx, pack
+        palette = self._cached(("palette", pack.palette.tobytes()), lambda: torch.from_numpy(pack.palette).to(self.device))
+        return None, self._to_camera_size(op_pack_expand(idx, pack.k, palette, Hl, Wl))
+
     def _assemble_alike(self, frames: List[dict]) -> list:
-        from ..lib import op_data_targets
+        from ..lib import op_data_targets, op_pack_targets
         if not hasattr(self.img_transform, "batch"):
             raise TypeError("the datasets need the GPU input transform of model.loader.load_transforms (an object with .batch); got " +
                             type(self.img_transform).__name__)
@@ -202,7 +280,10 @@ class BDD_Dataset(BengaluruDepthDatasetIterator):
             out["x"] = self.img_transform.batch(out["x_raw"])
             want_seg, want_disp = "y_seg" in self.fields, "y_disp" in self.fields
             disp = self._upload(frames, "disparity_frame") if want_disp else None
-            if want_seg:
+            idx = None
+            if want_seg and "seg_index" in frames[0]:
+                idx, seg = self._labels_from_indices(frames)
+            elif want_seg:
                 seg = self._upload(frames, "seg_frame")
             else:       # the kernel reads labels whatever it writes: a depth-only item hands it blank ones and asks for no label output
                 seg = self._cached(("blank", tuple(disp.shape)), lambda: torch.zeros(tuple(disp.shape) + (3,), dtype=torch.uint8, device=self.device))
@@ -210,7 +291,13 @@ class BDD_Dataset(BengaluruDepthDatasetIterator):
             if want_seg or disp is not None:
                 # flip stays 0: the frames are already in the iterator's (channel-flipped) order.  The reference's OccupancyProcessor.process_frame flips
                 # such a frame once and rgb_seg_to_class flips it back before comparing, so its class ids are those of the frame as it is here.
-                t = op_data_targets(seg, colors, disp, want_onehot=want_seg, want_unmatched=want_seg, want_class_map=want_seg and self.keep_class_map)
+                wants = dict(want_onehot=want_seg, want_unmatched=want_seg, want_class_map=want_seg and self.keep_class_map)
+                if idx is not None:      # seg is the pack: the targets straight from the indices
+                    palette = self._cached(("palette", seg.palette.tobytes()), lambda: torch.from_numpy(seg.palette).to(self.device))
+                    Hl, Wl = seg.shapes["labels"]
+                    t = op_pack_targets(idx, seg.k, palette, colors, Hl, Wl, disp, **wants)
+                else:
+                    t = op_data_targets(seg, colors, disp, **wants)
                 out["y_seg"], out["y_disp"] = t["onehot"], t["y_disp"]
                 self.last_unmatched, self.last_class_map = t["unmatched"], t["class_map"]
             if want_disp:
@@ -296,7 +383,7 @@ def submit_decode(dataset, indices: Iterable[int]):
     """Start decoding a batch in the pool -> (leaf that assembles it, one future per frame).  Host work only."""
     head, pairs = _leaves(dataset, indices)
     pool = decode_pool(head.workers)
-    return head, [pool.submit(leaf.read_frame, i) for leaf, i in pairs]
+    return head, [pool.submit(leaf.batch_frame, i) for leaf, i in pairs]
 
 
 def dataset_batch(dataset, indices: Iterable[int]) -> list:

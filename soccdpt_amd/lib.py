@@ -297,6 +297,20 @@ DATA_U8, DATA_U16, DATA_F32 = 0, 1, 2   # SOCCDPT_DATA_* (include/soccdpt_data.h
 DATA_MAX_CLASSES = 8
 
 
+def _pack_prototypes() -> dict:
+    """The same table for include/soccdpt_pack.h (targets from palette-indexed labels, csrc/frame_pack.hip), in that header's order;
+    tests/test_frame_pack_cpu.py holds it against the header.  A fourth header and a fourth table: soccdpt_hip.h and its ABI version do not change."""
+    vp, ci, cs = ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t
+    return {
+        "soccdpt_pack_targets": (ci, [vp, ci, cs, vp, ci, vp, ci, vp, ci, ci, ci, ci, ci, vp, vp, vp, vp, vp]),
+        "soccdpt_pack_expand": (ci, [vp, ci, cs, vp, ci, ci, ci, ci, vp, vp]),
+    }
+
+
+PACK_PROTOTYPES = _pack_prototypes()
+PACK_INDEX_BITS = (1, 2, 4, 8)   # k of include/soccdpt_pack.h
+
+
 def load_library() -> ctypes.CDLL:
     """Load libsoccdpt_hip.so; fail loudly when it has not been built."""
     global _lib
@@ -307,7 +321,7 @@ def load_library() -> ctypes.CDLL:
             f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "(make -C soccdpt_amd/csrc).  The SOccDPT MI355X path has no CPU fallback.")
     L = ctypes.CDLL(LIB_PATH)
-    for table in (PROTOTYPES, VIS_PROTOTYPES, DATA_PROTOTYPES):
+    for table in (PROTOTYPES, VIS_PROTOTYPES, DATA_PROTOTYPES, PACK_PROTOTYPES):
         for symbol, (restype, argtypes) in table.items():
             fn = getattr(L, symbol)
             fn.restype, fn.argtypes = restype, argtypes
@@ -845,6 +859,45 @@ def op_data_resize_u8c1(src: torch.Tensor, Hd: int, Wd: int, ytaps: Optional[tor
     B = src.shape[0]
     out = torch.empty((B, int(Hd), int(Wd)), dtype=torch.uint8, device=src.device)
     _call("soccdpt_data_resize_u8c1", _ptr(src), B, src.shape[1], src.shape[2], _ptr(ytaps), _ptr(xtaps), int(Hd), int(Wd), _ptr(out), device=src.device)
+    return out
+
+
+def _packed_args(idx: torch.Tensor, k: int, palette: torch.Tensor, H: int, W: int):
+    assert idx.is_cuda and idx.dim() == 2 and idx.element_size() == 4 and not idx.dtype.is_floating_point, "idx must be a cuda [B,words] tensor of 32-bit words"
+    assert palette.is_cuda and palette.dtype == torch.uint8 and palette.dim() == 2 and palette.shape[1] == 3, "palette must be a cuda uint8 [P,3] tensor"
+    return _ptr(idx), int(k), int(idx.shape[1]), _ptr(palette), int(palette.shape[0])
+
+
+def op_pack_targets(idx: torch.Tensor, k: int, palette: torch.Tensor, colors: torch.Tensor, H: int, W: int, disp: Optional[torch.Tensor] = None,
+                    flip: bool = False, want_onehot: bool = True, want_class_map: bool = False, want_y_disp: Optional[bool] = None,
+                    want_unmatched: bool = True) -> dict:
+    """op_data_targets for label frames kept as palette indices (soccdpt_pack_targets, include/soccdpt_pack.h): idx [B,words] 32-bit words (cuda), k bits
+    per pixel, palette uint8 [P,3] -> the same dictionary, bit for bit what op_data_targets gives for palette[idx]."""
+    assert colors.is_cuda and colors.dtype == torch.uint8 and colors.dim() == 2 and colors.shape[1] == 3, "colors must be a cuda uint8 [C,3] tensor"
+    B, C, dev = idx.shape[0], colors.shape[0], idx.device
+    H, W = int(H), int(W)
+    dtype = 0
+    if disp is not None:
+        assert disp.is_cuda and tuple(disp.shape) == (B, H, W), "disp must be a cuda [B,H,W] tensor"
+        if disp.dtype not in _DATA_DTYPES:
+            raise TypeError(f"op_pack_targets: disparity of dtype {disp.dtype} (uint8, uint16 or float32)")
+        dtype = _DATA_DTYPES[disp.dtype]
+    if want_y_disp is None:
+        want_y_disp = disp is not None
+    out = dict(
+        onehot=torch.empty((B, C, H, W), dtype=torch.float32, device=dev) if want_onehot else None,
+        class_map=torch.empty((B, H, W), dtype=torch.int32, device=dev) if want_class_map else None,
+        y_disp=torch.empty((B, H, W), dtype=torch.float32, device=dev) if want_y_disp else None,
+        unmatched=torch.empty((B,), dtype=torch.int64, device=dev) if want_unmatched else None)     # u64 counts below 2^63
+    _call("soccdpt_pack_targets", *_packed_args(idx, k, palette, H, W), _ptr(colors), C, _ptr(disp), dtype, B, H, W, 1 if flip else 0, _ptr(out["onehot"]),
+          _ptr(out["class_map"]), _ptr(out["y_disp"]), _ptr(out["unmatched"]), device=dev)
+    return out
+
+
+def op_pack_expand(idx: torch.Tensor, k: int, palette: torch.Tensor, H: int, W: int) -> torch.Tensor:
+    """Palette-indexed label frames (as op_pack_targets takes them) -> uint8 [B,H,W,3] (soccdpt_pack_expand) on the current stream."""
+    out = torch.empty((idx.shape[0], int(H), int(W), 3), dtype=torch.uint8, device=idx.device)
+    _call("soccdpt_pack_expand", *_packed_args(idx, k, palette, H, W), idx.shape[0], int(H), int(W), _ptr(out), device=idx.device)
     return out
 
 

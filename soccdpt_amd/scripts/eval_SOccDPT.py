@@ -44,6 +44,10 @@ def build_parser() -> argparse.ArgumentParser:
     parser.add_argument("-ls", "--load_seg", default=None, help="Which seg checkpoint to load")
     parser.add_argument("--camera_intrinsics_yaml", default=None, help="calibration file (default: the synthetic 1920x1080 camera of SURVEY.md 8d)")
     parser.add_argument("--recordings", nargs="*", default=None, help="recording ids under --base_path (default: the reference's six)")
+    parser.add_argument("--frame_pack", nargs="?", const=True, default=None, metavar="DIR", help="read the recordings' frame packs (<id>.sfp, written by "
+                        "python -m soccdpt_amd.scripts.pack_recordings) instead of decoding their PNGs; bare flag: the pack inside each recording, DIR: "
+                        "a directory of packs.  A missing or stale pack warns and falls back to the PNGs")
+    parser.add_argument("--frame_pack_required", action="store_true", help="with --frame_pack: a missing or stale pack is an error")
     parser.add_argument("--occupancy", action="store_true", help="also evaluate the semantic occupancy grid on the GPU: 3-D IoU against the ground-truth "
                         "grid of OccupancyProcessor and the mean length of the occupancy point list (prints IOU_3D / OCC_POINTS)")
     parser.add_argument("--occupancy-per-frame", dest="occupancy_per_frame", action="store_true", help="implies --occupancy, with the model built with "
@@ -120,12 +124,14 @@ def synthetic_val_set(net, device, img: int, n: int = 10):
     return out
 
 
-def recorded_val_set(base_path: str, transforms, calib: str, device, n: int = 10, recordings=None, want_class_maps: bool = False):
+def recorded_val_set(base_path: str, transforms, calib: str, device, n: int = 10, recordings=None, want_class_maps: bool = False, frame_pack=None,
+                     frame_pack_required: bool = False):
     """The reference's evaluation subset of the recordings under base_path (eval_SOccDPT.py:126-135): random_split(dataset, [n, len - n]) with generator
     seed 0 -> (n items in the datasets' layout, each a batch of one; their ground-truth class maps [1,H,W] int32 from soccdpt_data_targets when asked
     for, else None; the (recording id, frame index) of every item).  The n frames are decoded concurrently, then assembled one by one."""
     from ..datasets.bengaluru_driving_dataset import BDD_Depth_Segmentation, get_bdd_dataset, resolve_index, submit_decode
-    full = get_bdd_dataset(BDD_Depth_Segmentation, transforms, base_path, recordings=recordings, settings_doc=calib, device=device)
+    full = get_bdd_dataset(BDD_Depth_Segmentation, transforms, base_path, recordings=recordings, settings_doc=calib, device=device, frame_pack=frame_pack,
+                           frame_pack_required=frame_pack_required)
     assert len(full) >= n, f"{base_path}: {len(full)} frames, the evaluation subset needs {n}"
     subset, _ = torch.utils.data.random_split(full, [n, len(full) - n], generator=torch.Generator().manual_seed(0))
     pending = [submit_decode(subset, [i]) for i in range(n)]
@@ -187,7 +193,9 @@ def main(args) -> dict:
     if real_data:
         transforms.device = device
         dataset, class_maps, picked = recorded_val_set(os.path.expanduser(args.base_path), transforms, calib, device, n=10,
-                                                       recordings=getattr(args, "recordings", None), want_class_maps=occupancy)
+                                                       recordings=getattr(args, "recordings", None), want_class_maps=occupancy,
+                                                       frame_pack=getattr(args, "frame_pack", None),
+                                                       frame_pack_required=bool(getattr(args, "frame_pack_required", False)))
     else:
         dataset = synthetic_val_set(net, device, net_w, n=10)
     x = dataset[-1][0].to(device=device, dtype=torch.float32)

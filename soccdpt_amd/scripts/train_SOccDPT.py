@@ -128,7 +128,8 @@ class ReduceLROnPlateau:
 
 
 def train_net(SOccDPT_version=3, device="cuda:0", model_type="dpt_swin2_tiny_256", checkpoint_dir="checkpoints", dataset="bdd", base_path="",
-              forward_only=False, max_steps=0, run_id="dummy_run", n_synthetic=12, camera_intrinsics_yaml=None, recordings=None, on_batch=None, **cfg):
+              forward_only=False, max_steps=0, run_id="dummy_run", n_synthetic=12, camera_intrinsics_yaml=None, recordings=None, on_batch=None,
+              frame_pack=None, frame_pack_required=False, **cfg):
     p = dict(SWEEP_DEFAULTS)
     unknown = [k for k in cfg if k not in p]
     assert not unknown, f"unknown sweep parameters: {unknown}"
@@ -166,7 +167,8 @@ def train_net(SOccDPT_version=3, device="cuda:0", model_type="dpt_swin2_tiny_256
     calib = camera_intrinsics_yaml or write_synth_calib(os.path.join(tempfile.mkdtemp(), "calib.yaml"))
     if real_data:
         transforms.device = device
-        full = get_bdd_dataset(BDD_Depth_Segmentation, transforms, base, recordings=recordings, settings_doc=calib, device=device)
+        full = get_bdd_dataset(BDD_Depth_Segmentation, transforms, base, recordings=recordings, settings_doc=calib, device=device, frame_pack=frame_pack,
+                               frame_pack_required=frame_pack_required)
     else:
         full = SyntheticDepthSegDataset(n_synthetic, net_w)
     num_classes = 3
@@ -296,6 +298,10 @@ def build_parser() -> argparse.ArgumentParser:
     parser.add_argument("--camera_intrinsics_yaml", default=None, help="calibration file (default: <base_path>/calibration/pocoX3/calib.yaml if present, "
                         "else the synthetic 1920x1080 camera)")
     parser.add_argument("--recordings", nargs="*", default=None, help="recording ids under --base_path (default: the reference's six)")
+    parser.add_argument("--frame_pack", nargs="?", const=True, default=None, metavar="DIR", help="read the recordings' frame packs (<id>.sfp, written by "
+                        "python -m soccdpt_amd.scripts.pack_recordings) instead of decoding their PNGs; bare flag: the pack inside each recording, DIR: "
+                        "a directory of packs.  A missing or stale pack warns and falls back to the PNGs")
+    parser.add_argument("--frame_pack_required", action="store_true", help="with --frame_pack: a missing or stale pack is an error")
     return parser
 
 
@@ -310,7 +316,8 @@ def main(args):
         out.append(train_net(SOccDPT_version=args.version, device=args.device, model_type=args.model_type, checkpoint_dir=args.checkpoint_dir,
                              dataset=args.dataset, base_path=args.base_path, forward_only=args.forward_only, max_steps=args.max_steps,
                              run_id=f"local_run_{i}", camera_intrinsics_yaml=getattr(args, "camera_intrinsics_yaml", None),
-                             recordings=getattr(args, "recordings", None), **run))
+                             recordings=getattr(args, "recordings", None), frame_pack=getattr(args, "frame_pack", None),
+                             frame_pack_required=bool(getattr(args, "frame_pack_required", False)), **run))
     return out
 
 
