@@ -42,8 +42,10 @@ extern "C" {
  *   9 (soccdpt_train_layer_bwd_args, soccdpt_op_train_layer_bwd_scratch_bytes and soccdpt_op_train_layer_bwd are new -- a test entry into the
  *     training step's layer backward routines; soccdpt_sizeof(5); nothing that existed changed);
  *   10 (soccdpt_train_aux_args, soccdpt_op_train_aux_scratch_bytes and soccdpt_op_train_aux are new -- a stateless test entry into the training
- *     step's non-GEMM launchers; soccdpt_sizeof(6); nothing that existed changed). */
-#define SOCCDPT_ABI_VERSION 10
+ *     step's non-GEMM launchers; soccdpt_sizeof(6); nothing that existed changed);
+ *   11 (soccdpt_fwd_aux_args and soccdpt_op_fwd_aux are new -- a stateless test entry into the forward path's non-GEMM launchers; soccdpt_sizeof(7);
+ *     nothing that existed changed). */
+#define SOCCDPT_ABI_VERSION 11
 
 /* backbone ids: model/loader.py:65-77 (model_type switch), model/blocks.py:59-78 */
 #define SOCCDPT_BACKBONE_SWIN2T16_256 0 /* dpt_swin2_tiny_256 */
@@ -103,7 +105,7 @@ const char* soccdpt_last_error(void* handle); /* handle may be NULL: last create
 int soccdpt_abi_version(void);
 /* sizeof of the public structs as the LIBRARY was compiled (a binding checks its own layout against these): which = 0 soccdpt_config,
  * 1 soccdpt_igemm_args, 2 soccdpt_kernel_stat, 3 soccdpt_calib_report, 4 soccdpt_calib_options, 5 soccdpt_train_layer_bwd_args,
- * 6 soccdpt_train_aux_args; unknown -> 0 */
+ * 6 soccdpt_train_aux_args, 7 soccdpt_fwd_aux_args; unknown -> 0 */
 size_t soccdpt_sizeof(int which);
 
 /* ---- precision map (SOCCDPT_PREC_MIXED handles only) ----
@@ -680,6 +682,74 @@ typedef struct soccdpt_train_aux_args {
 } soccdpt_train_aux_args;
 size_t soccdpt_op_train_aux_scratch_bytes(const soccdpt_train_aux_args* args);
 int soccdpt_op_train_aux(const soccdpt_train_aux_args* args, void* dev_scratch, size_t scratch_bytes, void* stream);
+
+/* Test entry into the forward path's launchers that are neither a GEMM nor attention (csrc/elementwise.hip, csrc/hybrid.hip): ONE operation on caller-supplied
+ * device tensors, through the launch_* function model.cpp / train_step.cpp / train_hybrid_step.cpp call, and in their composition where there is one
+ * (launch_patch_w then launch_patch_embed; launch_seg_tail = classifier + up-sampling).  No handle, no allocation, no scratch, no synchronisation; a refused
+ * call has launched nothing; errors through soccdpt_last_error(NULL).  All tensors are f32 unless noted, rows are NHWC pixels, "opt" = may be NULL, slots a
+ * kind does not name are ignored.  flags: bits 0-3 per kind (below), bits 4-7 `fmt` = the operand format written (elementwise.hip kinds: hf 0 bf16, 1 fp16,
+ * 3 x3, for CVT also 5 = IEEE fp16 without saturation; hybrid.hip kinds: out_mode 0 bf16, 1 fp16, 2 f32, 3 x3), bits 8-11 = 1 + the halo's format where it
+ * differs from fmt (0: the same).  "op" = a tensor in that format (2 bytes per element, 4 for f32 / x3).  *path_out (opt) receives the SOCCDPT_FWD_PATH_* of
+ * the kernel the launcher chose (0 for launchers with one kernel).
+ *   PATCH_EMBED      Conv2d(3, C0, 4, 4) + LayerNorm(C0, eps 1e-5).  dim {B, S, C0}; C0 <= 128, S % 32 == 0.  in {x [B][3][S][S], w [C0][48], bias [C0], g [C0], beta [C0]};
+ *                    out {xf [B (S/4)^2][C0], xb op opt, wT [48][128] (launch_patch_w's output: the weight the kernel reads)}.
+ *   LN_RESIDUAL      xf = (residual ? xf : 0) + row_scale * (LN(y) g + beta), eps 1e-5.  dim {M, C, res, rows_per_scale}; flags bit 0 residual, bit 1 merge (xb in the
+ *                    PatchMerging layout [B][res/2][res/2][4C]).  in {y [M][C], g [C], beta [C], row_scale [ceil(M / rows_per_scale)] opt}; out {xf [M][C], xb op opt,
+ *                    halo [B][res+2][res+2][C] op (halo format) opt, halo_f32 alike opt}: the interior of a halo is written, its ring is not.  res: the side of the token
+ *                    grid (M = B res^2), needed by merge and the halos.  C <= 1024; C % 256 == 0 takes the float4 kernels: every tensor 16-byte aligned then.
+ *   MERGE_GATHER     dim {B, R, C, elem_bytes}; R even, C elem_bytes % 16 == 0, 16-byte aligned.  in {in [B][R][R][C]}; out {out [B][R/2][R/2][4C]}.
+ *   BILINEAR         align_corners = True.  dim {B, h, w, H, W, C}; flags bit 0: the input is 16-bit (format fmt), bit 1: out_op is a zero-halo image.  in {in [B][h][w][C]};
+ *                    out {out_f32 [B][H][W][C] opt, out_op op opt (plain, or [B][H+2][W+2][C]), out_f32_halo opt}.  C % 4 == 0; x3 needs f32 input and C % 16 == 0; 16-byte
+ *                    aligned tensors.
+ *   SEG_TAIL         Conv2d(256, 3, 1) + x2 bilinear + activation.  dim {B, h, w}; flags bit 0 sigmoid (else ScaledTanh), bit 1: the features are f32 (else 16-bit, fmt).
+ *                    in {feat [B h w][256], w [3][256], bias [3]}; out {tmp [B h w][3] (the logits), seg [B][3][2h][2w]}.
+ *   CVT              dim {n}; fmt 0, 1, 3 (n % 16 == 0), 5.  in {in [n]}; out {out op}.
+ *   CONV_W           [Cout][Cin][3][3] -> [Cout][3][3][Cin] (x scale[Cout]).  dim {Cout, Cin}; flags bit 0: f32 output.  in {w, scale opt}; out {out}.
+ *   BN_FOLD          dim {C}.  in {g, b, mean, var}; out {scale [C] = g / sqrt(var + 1e-5), shift [C] = b - mean scale}.
+ *   QKV_BIAS         dim {C}.  in {q [C], v [C]}; out {out [3C] = q, 0, v}.
+ *   LOGIT_SCALE      dim {H}.  in {ls [H]}; out {out [H] = exp(min(ls, ln 100))}.
+ *   CPB_TABLE        dim {ws, pws (0: ws), H}.  in {w0 [512][2], b0 [512], w2 [H][512]}; out {table [(2 ws - 1)^2][H]}.
+ *   WS_CONV_W        dim {Cout, Cin, k, Kpad}; f[0] = eps.  in {w [Cout][Cin][k][k]}; out {out [Cout][Kpad] op, tap-major, zero beyond the fan-in}.
+ *   STEM_IM2COL      dim {B, S}, S even.  in {x [B][3][S][S]}; out {A [B (S/2)^2][160] op}.
+ *   GN_RELU_MAXPOOL  dim {B, Hi, C, cpg}, Hi even.  in {raw [B][Hi][Hi][C], stats [B][C/cpg][2] = mean, rstd, gamma [C], beta [C]}; out {out [B][Hi/2][Hi/2][C] op}.
+ *   VIT_TOKENS_LN    dim {B, ntok, C}, C == 768; f[0] = eps.  in {y [B (ntok-1)][C], cls [C], pos [ntok][C], g [C], be [C]}; out {xf [B ntok][C], xb op}.
+ *   LN_ROWS          dim {rows, C}, C == 768; f[0] = eps.  in {g, be}; out {xf [rows][C] (read, not written), xb op}.
+ *   POS_EMBED_RESIZE dim {g0, g, C}.  in {pos [1 + g0^2][C]}; out {out [1 + g^2][C]}. */
+#define SOCCDPT_FWD_PATCH_EMBED 0
+#define SOCCDPT_FWD_LN_RESIDUAL 1
+#define SOCCDPT_FWD_MERGE_GATHER 2
+#define SOCCDPT_FWD_BILINEAR 3
+#define SOCCDPT_FWD_SEG_TAIL 4
+#define SOCCDPT_FWD_CVT 5
+#define SOCCDPT_FWD_CONV_W 6
+#define SOCCDPT_FWD_BN_FOLD 7
+#define SOCCDPT_FWD_QKV_BIAS 8
+#define SOCCDPT_FWD_LOGIT_SCALE 9
+#define SOCCDPT_FWD_CPB_TABLE 10
+#define SOCCDPT_FWD_WS_CONV_W 11
+#define SOCCDPT_FWD_STEM_IM2COL 12
+#define SOCCDPT_FWD_GN_RELU_MAXPOOL 13
+#define SOCCDPT_FWD_VIT_TOKENS_LN 14
+#define SOCCDPT_FWD_LN_ROWS 15
+#define SOCCDPT_FWD_POS_EMBED_RESIZE 16
+#define SOCCDPT_FWD_KINDS 17
+#define SOCCDPT_FWD_PATH_BILINEAR_GENERIC 1
+#define SOCCDPT_FWD_PATH_BILINEAR_HALO8 2
+#define SOCCDPT_FWD_PATH_BILINEAR_HALO8_X3 3
+#define SOCCDPT_FWD_PATH_SEG_F32 1
+#define SOCCDPT_FWD_PATH_SEG_16 2
+#define SOCCDPT_FWD_PATH_LN_SCALAR 0x100 /* | values per lane: 2, 4, 8, 12, 16 */
+#define SOCCDPT_FWD_PATH_LN_V4 0x200     /* | float4 groups per lane: 1 .. 4 */
+typedef struct soccdpt_fwd_aux_args {
+    int32_t kind;                 /* SOCCDPT_FWD_* */
+    int32_t flags;
+    int64_t dim[6];
+    float f[3];
+    uint32_t reserved;            /* 0 */
+    const void* in[6];
+    void* out[6];
+} soccdpt_fwd_aux_args;
+int soccdpt_op_fwd_aux(const soccdpt_fwd_aux_args* args, uint32_t* path_out, void* stream);
 
 /* Swin-V2 cosine window attention of one block (timm WindowAttention + shift/partition/reverse):
  * qkv [B*res*res][3*heads*32] -> out [B*res*res][heads*32], elements bf16 / f32 / fp16 by `precision` (SOCCDPT_PREC_*).  cpb_table [(2ws-1)^2][heads] f32 is

@@ -115,6 +115,7 @@ size_t soccdpt_sizeof(int which) {
         case 4: return sizeof(soccdpt_calib_options);
         case 5: return sizeof(soccdpt_train_layer_bwd_args);
         case 6: return sizeof(soccdpt_train_aux_args);
+        case 7: return sizeof(soccdpt_fwd_aux_args);
         default: return 0;
     }
 }
@@ -788,6 +789,15 @@ int soccdpt_op_train_aux(const soccdpt_train_aux_args* args, void* dev_scratch, 
     std::string err;
     if (!args) return fail(nullptr, "soccdpt_op_train_aux: null args");
     if (train_aux(*args, dev_scratch, scratch_bytes, (hipStream_t)stream, err)) return fail(nullptr, err);
+    return 0;
+}
+
+int soccdpt_op_fwd_aux(const soccdpt_fwd_aux_args* args, uint32_t* path_out, void* stream) {
+    std::string err;
+    if (!args) return fail(nullptr, "soccdpt_op_fwd_aux: null args");
+    unsigned path = 0;
+    if (fwd_aux(*args, &path, (hipStream_t)stream, err)) return fail(nullptr, err);
+    if (path_out) *path_out = path;
     return 0;
 }
 

@@ -145,7 +145,7 @@ __global__ __launch_bounds__(256) void ln_residual_v4_kernel(const float* __rest
 }
 
 int launch_ln_residual(const float* y, const float* g, const float* beta, float* xf, bf16_t* xb, bf16_t* halo, float* halo_f32, int hf, int M,
-                       int C, int residual, int res, int merge, hipStream_t st, std::string& err, const float* row_scale, int rows_per_scale, int hf_halo) {
+                       int C, int residual, int res, int merge, hipStream_t st, std::string& err, const float* row_scale, int rows_per_scale, int hf_halo, int* path) {
     if (merge && (res <= 0 || (res & 1) || M % (res * res) != 0)) { err = "ln_residual: merged operand layout needs an even token grid"; return 1; }
     if (hf_halo < 0) hf_halo = hf;
     const int x3 = hf == 3 ? 1 : 0, x3h = hf_halo == 3 ? 1 : 0;   // hf / hf_halo: 0 bf16, 1 fp16, 3 x3 (half16.h)
@@ -155,6 +155,12 @@ int launch_ln_residual(const float* y, const float* g, const float* beta, float*
     const int vpl = (C + 63) / 64;
     dim3 grid((M + 3) / 4), block(256);
     if (C % 256 == 0 && C <= 1024) {
+        // float4 loads of y / g / beta / xf, 8- and 16-byte stores of the copies
+        if (!ptr_aligned16(y) || !ptr_aligned16(g) || !ptr_aligned16(beta) || !ptr_aligned16(xf) || !ptr_aligned16(xb) || !ptr_aligned16(halo) || !ptr_aligned16(halo_f32)) {
+            err = "ln_residual: C % 256 == 0 reads and writes float4: 16-byte aligned tensors";
+            return 1;
+        }
+        if (path) *path = SOCCDPT_FWD_PATH_LN_V4 | (C / 256);
 #define LN4_CASE(V)                                                                                                                       \
     do {                                                                                                                                  \
         if (hf) SOCCDPT_LAUNCH((ln_residual_v4_kernel<V, true>), grid, block, 0, st, y, g, beta, xf, xb, halo, halo_f32, M, C, residual, res, merge, x3, x3h, row_scale, rows_per_scale);  \
@@ -169,12 +175,14 @@ int launch_ln_residual(const float* y, const float* g, const float* beta, float*
         if (hf) SOCCDPT_LAUNCH((ln_residual_kernel<V, true>), grid, block, 0, st, y, g, beta, xf, xb, halo, halo_f32, M, C, residual, res, merge, x3, x3h, row_scale, rows_per_scale);  \
         else SOCCDPT_LAUNCH((ln_residual_kernel<V, false>), grid, block, 0, st, y, g, beta, xf, xb, halo, halo_f32, M, C, residual, res, merge, x3, x3h, row_scale, rows_per_scale);    \
     } while (0)
-    if (vpl <= 2) LN_CASE(2);
-    else if (vpl <= 4) LN_CASE(4);
-    else if (vpl <= 8) LN_CASE(8);
-    else if (vpl <= 12) LN_CASE(12);
-    else if (vpl <= 16) LN_CASE(16);
-    else { err = "ln_residual: C > 1024"; return 1; }
+    const int V = vpl <= 2 ? 2 : (vpl <= 4 ? 4 : (vpl <= 8 ? 8 : (vpl <= 12 ? 12 : 16)));
+    if (vpl > 16) { err = "ln_residual: C > 1024"; return 1; }
+    if (path) *path = SOCCDPT_FWD_PATH_LN_SCALAR | V;
+    if (V == 2) LN_CASE(2);
+    else if (V == 4) LN_CASE(4);
+    else if (V == 8) LN_CASE(8);
+    else if (V == 12) LN_CASE(12);
+    else LN_CASE(16);
 #undef LN_CASE
     return check_launch("ln_residual", err);
 }
@@ -201,6 +209,9 @@ __global__ __launch_bounds__(256) void merge_gather_kernel(const uint4* __restri
 }
 
 int launch_merge_gather(const void* in, void* out, int B, int R, int C, int elem_bytes, hipStream_t st, std::string& err) {
+    if (B < 1 || R < 2 || (R & 1)) { err = "merge_gather: the token grid must be even"; return 1; }
+    if (C < 1 || elem_bytes < 1 || ((size_t)C * elem_bytes) % 16) { err = "merge_gather: a token's channels must be a multiple of 16 bytes (the kernel moves 16-byte chunks)"; return 1; }
+    if (!ptr_aligned16(in) || !ptr_aligned16(out)) { err = "merge_gather: 16-byte aligned tensors"; return 1; }
     const int cpt = C * elem_bytes / 16;
     const size_t total = (size_t)B * (R / 2) * (R / 2) * 4 * cpt;
     size_t blocks = (total + 255) / 256;
@@ -347,8 +358,9 @@ __global__ __launch_bounds__(256) void bilinear_f32_to_halo8_x3_kernel(const flo
 }
 
 int launch_bilinear(const void* in, int in_is_bf16, float* out_f32, bf16_t* out_bf16, float* out_f32_halo, int out_halo, int hf, int B, int h,
-                    int w, int H, int W, int C, hipStream_t st, std::string& err) {
+                    int w, int H, int W, int C, hipStream_t st, std::string& err, int* path) {
     if (C % 4) { err = "bilinear: C % 4 != 0"; return 1; }
+    if (!ptr_aligned16(in) || !ptr_aligned16(out_f32) || !ptr_aligned16(out_bf16) || !ptr_aligned16(out_f32_halo)) { err = "bilinear: four channels per access: 16-byte aligned tensors"; return 1; }
     const int x3 = hf == 3 ? 1 : 0;   // hf: 0 bf16, 1 fp16, 3 x3 output in out_bf16 (half16.h)
     if (x3 && (C % 16 || in_is_bf16)) { err = "bilinear: x3 output needs f32 input and C % 16 == 0"; return 1; }
     hf = hf == 1;
@@ -356,6 +368,7 @@ int launch_bilinear(const void* in, int in_is_bf16, float* out_f32, bf16_t* out_
         const size_t total8 = (size_t)B * H * W * (C / 8);
         size_t blocks8 = (total8 + 255) / 256;
         if (blocks8 > 8192) blocks8 = 8192;
+        if (path) *path = SOCCDPT_FWD_PATH_BILINEAR_HALO8_X3;
         SOCCDPT_LAUNCH(bilinear_f32_to_halo8_x3_kernel, dim3((unsigned)blocks8), dim3(256), 0, st, (const float*)in, static_cast<void*>(out_bf16), B, h, w, H, W, C);
         return check_launch("bilinear", err);
     }
@@ -363,12 +376,14 @@ int launch_bilinear(const void* in, int in_is_bf16, float* out_f32, bf16_t* out_
         const size_t total8 = (size_t)B * H * W * (C / 8);
         size_t blocks8 = (total8 + 255) / 256;
         if (blocks8 > 8192) blocks8 = 8192;
+        if (path) *path = SOCCDPT_FWD_PATH_BILINEAR_HALO8;
         LAUNCH_HF(hf, bilinear_f32_to_halo8_kernel, dim3((unsigned)blocks8), dim3(256), 0, st, (const float*)in, out_bf16, B, h, w, H, W, C);
         return check_launch("bilinear", err);
     }
     const size_t total = (size_t)B * H * W * (C / 4);
     size_t blocks = (total + 255) / 256;
     if (blocks > 8192) blocks = 8192;
+    if (path) *path = SOCCDPT_FWD_PATH_BILINEAR_GENERIC;
 #define BL_ARGS(T) dim3((unsigned)blocks), dim3(256), 0, st, (const T*)in, out_f32, out_bf16, out_f32_halo, out_halo, B, h, w, H, W, C, x3
     if (in_is_bf16 && hf) SOCCDPT_LAUNCH((bilinear_kernel<bf16_t, true>), BL_ARGS(bf16_t));
     else if (in_is_bf16) SOCCDPT_LAUNCH((bilinear_kernel<bf16_t, false>), BL_ARGS(bf16_t));
@@ -504,7 +519,10 @@ int launch_seg_tail_parts(const float* part, int ntiles, const float* bias, floa
 }
 
 int launch_seg_tail(const void* feat, int feat_is_f32, int hf, const float* w, const float* bias, float* tmp, float* seg, int B, int h, int wd,
-                    int sigmoid, hipStream_t st, std::string& err) {
+                    int sigmoid, hipStream_t st, std::string& err, int* path) {
+    // both classifiers read 16-byte chunks of the features, the 16-bit one its weights too
+    if (!ptr_aligned16(feat) || (!feat_is_f32 && !ptr_aligned16(w))) { err = "seg_tail: 16-byte aligned features (and weights beside 16-bit features)"; return 1; }
+    if (path) *path = feat_is_f32 ? SOCCDPT_FWD_PATH_SEG_F32 : SOCCDPT_FWD_PATH_SEG_16;
     const int M = B * h * wd;
     const dim3 grid((unsigned)(((size_t)M * 16 + 255) / 256));
     unsigned gl = grid.x > 2048 ? 2048 : grid.x;   // grid-stride (16-bit path): weights are loaded once per thread
@@ -638,6 +656,7 @@ int launch_cvt_bf16(const float* in, bf16_t* out, size_t n, int hf, hipStream_t 
     return check_launch("cvt_bf16", err);
 }
 int launch_conv_w(const float* in, const float* scale, void* out, int out_is_f32, int hf, int Cout, int Cin, hipStream_t st, std::string& err) {
+    if (hf == 3 && Cin % 16) { err = "conv_w: x3 rows are multiples of 16 elements"; return 1; }   // a partial last unit would be written past the tensor's end
     size_t n = (size_t)Cout * Cin * 9, blocks = (n + 255) / 256;
     if (blocks > 2048) blocks = 2048;
     if (hf == 3) SOCCDPT_LAUNCH(conv_w_f32_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, st, in, scale, static_cast<float*>(out), Cout, Cin);   // x3, 4 bytes per element
@@ -655,19 +674,20 @@ int launch_qkv_bias(const float* q, const float* v, float* out, int C, hipStream
     return check_launch("qkv_bias", err);
 }
 int launch_logit_scale(const float* ls, float* out, int H, hipStream_t st, std::string& err) {
-    SOCCDPT_LAUNCH(logit_scale_kernel, dim3(1), dim3(64), 0, st, ls, out, H);
+    if (H < 1) { err = "logit_scale: no heads"; return 1; }
+    SOCCDPT_LAUNCH(logit_scale_kernel, dim3((unsigned)((H + 63) / 64)), dim3(64), 0, st, ls, out, H);
     return check_launch("logit_scale", err);
 }
 int launch_cpb_table(const float* w0, const float* b0, const float* w2, float* table, int ws, int pws, int H, hipStream_t st,
                      std::string& err) {
     const int n = (2 * ws - 1) * (2 * ws - 1) * H;
     const size_t lds = (size_t)(1536 + H * 512) * sizeof(float);   // 8 - 54 KB for 1 - 24 heads... (32 heads: 70 KB)
+    if (lds > 160 * 1024) { err = "cpb_table: too many heads for the LDS-resident MLP"; return 1; }
     static PerDeviceOnce attr;
     if (attr.need()) {
         if (hipFuncSetAttribute(reinterpret_cast<const void*>(&cpb_table_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) { err = "cpb_table: hipFuncSetAttribute failed"; return 1; }
         attr.done();
     }
-    if (lds > 160 * 1024) { err = "cpb_table: too many heads for the LDS-resident MLP"; return 1; }
     SOCCDPT_LAUNCH(cpb_table_kernel, dim3((n + 255) / 256), dim3(256), lds, st, w0, b0, w2, table, ws, pws, H);
     return check_launch("cpb_table", err);
 }

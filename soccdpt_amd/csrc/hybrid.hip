@@ -494,7 +494,11 @@ int launch_gn_finish(const float* part, float* stats, int B, int tps, int G, int
 
 int launch_gn_relu_maxpool(const float* raw, const float* stats, const float* gamma, const float* beta, void* out, int out_mode, int B, int Hi, int C, int cpg,
                            hipStream_t st, std::string& err) {
-    const int Ho = (Hi + 1) / 2;
+    // the kernel pads behind the image only: TF 'SAME' does that at an even side alone (an odd one pads in front as well; th_maxpool_bwd refuses it too)
+    if (B < 1 || Hi < 2 || (Hi & 1)) { err = "gn_relu_maxpool: the input side must be even"; return 1; }
+    if (C % 4 || cpg < 2 || (cpg != 2 && cpg % 4) || C % cpg) { err = "gn_relu_maxpool: bad geometry (C % 4, cpg 2 or a multiple of 4, C % cpg)"; return 1; }   // launch_gn_apply's, for the same Gn4 / Gn4x2 loads
+    if (!ptr_aligned16(raw) || !ptr_aligned16(stats) || !ptr_aligned16(gamma) || !ptr_aligned16(beta) || !ptr_aligned16(out)) { err = "gn_relu_maxpool: 16-byte aligned tensors"; return 1; }
+    const int Ho = Hi / 2;
     const size_t total = (size_t)B * Ho * Ho * (C / 4);
     DISPATCH_OUT(out_mode, SOCCDPT_LAUNCH(gn_relu_maxpool_kernel<OUT>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, raw, stats, gamma, beta, out, B, Hi,
                                                Ho, C, cpg));
@@ -504,6 +508,10 @@ int launch_gn_relu_maxpool(const float* raw, const float* stats, const float* ga
 int launch_vit_tokens_ln(const float* y, const float* cls, const float* pos, float* xf, const float* g, const float* be, void* xb, int out_mode, int B, int ntok,
                          int C, float eps, hipStream_t st, std::string& err) {
     if (C != 768) { err = "vit_tokens_ln: C must be 768"; return 1; }
+    if (!ptr_aligned16(y) || !ptr_aligned16(cls) || !ptr_aligned16(pos) || !ptr_aligned16(xf) || !ptr_aligned16(g) || !ptr_aligned16(be) || !ptr_aligned16(xb)) {
+        err = "vit_tokens_ln: float4 rows: 16-byte aligned tensors";
+        return 1;
+    }
     const int rows = B * ntok;
     DISPATCH_OUT(out_mode, SOCCDPT_LAUNCH((ln768_kernel<OUT, 1>), dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, y, cls, pos, xf, g, be, xb, rows, ntok, eps));
     return check_launch("vit_tokens_ln", err);
@@ -511,6 +519,7 @@ int launch_vit_tokens_ln(const float* y, const float* cls, const float* pos, flo
 
 int launch_ln_rows(float* xf, const float* g, const float* be, void* xb, int out_mode, int rows, int C, float eps, hipStream_t st, std::string& err) {
     if (C != 768) { err = "ln_rows: C must be 768"; return 1; }
+    if (!ptr_aligned16(xf) || !ptr_aligned16(g) || !ptr_aligned16(be) || !ptr_aligned16(xb)) { err = "ln_rows: float4 rows: 16-byte aligned tensors"; return 1; }
     DISPATCH_OUT(out_mode, SOCCDPT_LAUNCH((ln768_kernel<OUT, 0>), dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, nullptr, nullptr, nullptr, xf, g, be, xb, rows,
                                                0, eps));
     return check_launch("ln_rows", err);

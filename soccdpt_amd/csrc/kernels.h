@@ -20,7 +20,9 @@ inline int check_launch(const char* what, std::string& err) {
     return 0;
 }
 
-// elementwise.hip
+inline bool ptr_aligned16(const void* p) { return reinterpret_cast<uintptr_t>(p) % 16 == 0; }   // NULL (an absent optional tensor) counts as aligned
+
+// elementwise.hip.  `path` (optional, where a launcher chooses between kernels): receives the SOCCDPT_FWD_PATH_* of the kernel launched (soccdpt_op_fwd_aux)
 int launch_patch_embed(const float* x, const float* w, const float* bias, const float* g, const float* beta, float* xf, bf16_t* xb,
                        int hf, int B, int S, int C0, hipStream_t st, std::string& err);
 // row_scale (optional): the normalised branch of row m is multiplied by row_scale[m / rows_per_scale] before the residual add (stochastic depth
@@ -28,12 +30,13 @@ int launch_patch_embed(const float* x, const float* w, const float* bias, const 
 // hf_halo: operand format of `halo` when it differs from xb's (SOCCDPT_PREC_MIXED: the hooked map feeds the decoder, xb the next block); -1 = hf
 int launch_ln_residual(const float* y, const float* g, const float* beta, float* xf, bf16_t* xb, bf16_t* halo, float* halo_f32, int hf, int M,
                        int C, int residual, int res, int merge, hipStream_t st, std::string& err, const float* row_scale = nullptr, int rows_per_scale = 1,
-                       int hf_halo = -1);
+                       int hf_halo = -1, int* path = nullptr);
+// R even, C * elem_bytes a multiple of 16, both tensors 16-byte aligned
 int launch_merge_gather(const void* in, void* out, int B, int R, int C, int elem_bytes, hipStream_t st, std::string& err);
 int launch_bilinear(const void* in, int in_is_bf16, float* out_f32, bf16_t* out_bf16, float* out_f32_halo, int out_halo, int hf, int B, int h,
-                    int w, int H, int W, int C, hipStream_t st, std::string& err);
+                    int w, int H, int W, int C, hipStream_t st, std::string& err, int* path = nullptr);
 int launch_seg_tail(const void* feat, int feat_is_f32, int hf, const float* w, const float* bias, float* tmp, float* seg, int B, int h, int wd,
-                    int sigmoid, hipStream_t st, std::string& err);
+                    int sigmoid, hipStream_t st, std::string& err, int* path = nullptr);
 // the classifier was fused into the seg head's convolution (IgemmDesc::dot3): add the n-tiles' partial logits [ntiles][M][4] + bias -> tmp [M][3], then up-sample + activate
 int launch_seg_tail_parts(const float* part, int ntiles, const float* bias, float* tmp, float* seg, int B, int h, int wd, int sigmoid, hipStream_t st, std::string& err);
 int launch_patch_w(const float* w, float* out, int C0, hipStream_t st, std::string& err);
@@ -160,5 +163,8 @@ int launch_window_attention_qkv(const bf16_t* x, const void* wqkv, const float* 
 // x3 != 0: `out` is written in the x3 split-fp16 operand format (half16.h) for the proj GEMM of SOCCDPT_PREC_F16X3
 int launch_window_attention_f32(const float* qkv, const float* bias_acc, const float* table, const float* scale, float* out, int B, int res,
                                 int ws, int shift, int heads, hipStream_t st, std::string& err, int x3 = 0);
+
+// fwd_aux.cpp: one of the launchers above on caller-supplied tensors (soccdpt_op_fwd_aux, include/soccdpt_hip.h: tests)
+int fwd_aux(const soccdpt_fwd_aux_args& a, unsigned* path, hipStream_t st, std::string& err);
 
 }  // namespace soccdpt

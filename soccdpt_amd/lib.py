@@ -15,7 +15,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SOCCDPT_LIB_PATH") or os.path.join(_HERE, "libsoccdpt_hip.so")   # override: A/B of two builds in one GPU call (tools/ab_bench.sh)
 
-ABI_VERSION = 10
+ABI_VERSION = 11
 BACKBONE_IDS = {"swin2t16_256": 0, "swin2b24_384": 1, "vitb_rn50_384": 2}
 PREC_BF16 = 0
 PREC_F32 = 1
@@ -117,6 +117,23 @@ class TrainAuxArgs(ctypes.Structure):
         ("inp", ctypes.c_void_p * 6), ("out", ctypes.c_void_p * 6),
     ]
 
+
+class FwdAuxArgs(ctypes.Structure):
+    """soccdpt_fwd_aux_args (include/soccdpt_hip.h): what flags / dim / f / in / out mean is listed there per kind."""
+    _fields_ = [
+        ("kind", ctypes.c_int32), ("flags", ctypes.c_int32), ("dim", ctypes.c_int64 * 6), ("f", ctypes.c_float * 3), ("reserved", ctypes.c_uint32),
+        ("inp", ctypes.c_void_p * 6), ("out", ctypes.c_void_p * 6),
+    ]
+
+
+# SOCCDPT_FWD_* (include/soccdpt_hip.h), in the header's order
+FWD_KINDS = ("patch_embed", "ln_residual", "merge_gather", "bilinear", "seg_tail", "cvt", "conv_w", "bn_fold", "qkv_bias", "logit_scale", "cpb_table", "ws_conv_w",
+             "stem_im2col", "gn_relu_maxpool", "vit_tokens_ln", "ln_rows", "pos_embed_resize")
+FWD = {name: i for i, name in enumerate(FWD_KINDS)}
+# SOCCDPT_FWD_PATH_*
+FWD_PATH_BILINEAR = {1: "generic", 2: "halo8", 3: "halo8_x3"}
+FWD_PATH_SEG = {1: "f32", 2: "16bit"}
+FWD_PATH_LN_SCALAR, FWD_PATH_LN_V4 = 0x100, 0x200
 
 # SOCCDPT_AUX_* (include/soccdpt_hip.h), in the header's order
 AUX_KINDS = ("ln_bwd", "colsum", "colsum2", "bn_fwd", "bn_bwd", "gn_bwd", "ws_bwd", "bilinear_bwd", "maxpool_bwd", "depth_tail", "smallk", "gelu_bwd", "relu_bwd",
@@ -242,6 +259,7 @@ def _prototypes() -> dict:
         "soccdpt_op_train_layer_bwd": (ci, [vp, P(TrainLayerBwdArgs), vp, cs, P(ctypes.c_uint32), vp]),
         "soccdpt_op_train_aux_scratch_bytes": (cs, [P(TrainAuxArgs)]),
         "soccdpt_op_train_aux": (ci, [P(TrainAuxArgs), vp, cs, vp]),
+        "soccdpt_op_fwd_aux": (ci, [P(FwdAuxArgs), P(ctypes.c_uint32), vp]),
         "soccdpt_op_window_attention": (ci, [vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, vp]),
         "soccdpt_op_window_attention_qkv": (ci, [vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, vp, vp]),
         "soccdpt_op_wino_weights": (ci, [vp, vp, vp, ci, ci, ci, vp]),
@@ -328,7 +346,7 @@ def load_library() -> ctypes.CDLL:
     if L.soccdpt_abi_version() != ABI_VERSION:
         raise RuntimeError("libsoccdpt_hip.so ABI version mismatch; rebuild the library")
     # the ctypes mirrors of the public structs must have the layout the library was compiled with (include/soccdpt_hip.h)
-    for which, cls in ((0, SoccdptConfig), (1, IgemmArgs), (2, KernelStat), (3, CalibReport), (4, CalibOptions), (5, TrainLayerBwdArgs), (6, TrainAuxArgs)):
+    for which, cls in ((0, SoccdptConfig), (1, IgemmArgs), (2, KernelStat), (3, CalibReport), (4, CalibOptions), (5, TrainLayerBwdArgs), (6, TrainAuxArgs), (7, FwdAuxArgs)):
         if L.soccdpt_sizeof(which) != ctypes.sizeof(cls):
             raise RuntimeError(f"libsoccdpt_hip.so: sizeof mismatch for {cls.__name__}: library {L.soccdpt_sizeof(which)}, binding {ctypes.sizeof(cls)}")
     _lib = L
@@ -949,6 +967,14 @@ def op_train_aux(args: TrainAuxArgs, scratch: torch.Tensor) -> None:
     """Kernel-level entry (tests): one non-GEMM launcher of the training step (or the step's composition of a few) on caller-supplied tensors, on the current
     stream of the scratch's device (include/soccdpt_hip.h soccdpt_op_train_aux)."""
     _call("soccdpt_op_train_aux", ctypes.byref(args), scratch.data_ptr(), scratch.numel() * scratch.element_size(), device=scratch.device, guard=False)
+
+
+def op_fwd_aux(args: FwdAuxArgs, device: torch.device) -> int:
+    """Kernel-level entry (tests): one non-GEMM launcher of the forward path on caller-supplied tensors, on the current stream of `device`
+    (include/soccdpt_hip.h soccdpt_op_fwd_aux) -> the SOCCDPT_FWD_PATH_* of the kernel the launcher chose."""
+    path = ctypes.c_uint32(0)
+    _call("soccdpt_op_fwd_aux", ctypes.byref(args), ctypes.byref(path), device=device, guard=False)
+    return int(path.value)
 
 
 def op_window_attention(qkv, cpb_table, scale, out, B, res, ws, shift, heads, precision=PREC_BF16):

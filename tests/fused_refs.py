@@ -83,15 +83,31 @@ def _f32_position_error(n_in: int, n_out: int) -> torch.Tensor:
     return torch.from_numpy(dp)
 
 
+def _f32_halfpixel_error(n_in: int, n_out: int) -> torch.Tensor:
+    """The same for the half-pixel form p = max((i + 0.5) n_in / n_out - 0.5, 0) (hybrid.hip pos_embed_resize_kernel): scale = n_in / n_out in f32 or
+    one ulp either side, i + 0.5 exact, then the product rounded and 0.5 subtracted (rounded again), or both in one fma."""
+    i = np.arange(n_out, dtype=np.float64)
+    exact = np.maximum((i + 0.5) * n_in / n_out - 0.5, 0.0)
+    s = np.float32(n_in) / np.float32(n_out)
+    dp = np.zeros_like(i)
+    for sc in (s, np.nextafter(s, np.float32(0)), np.nextafter(s, np.float32(np.inf))):
+        prod = np.float64(sc) * (i + 0.5)             # exact: 24 x 18 significant bits
+        two = (prod.astype(np.float32).astype(np.float64) - 0.5).astype(np.float32).astype(np.float64)
+        fused = (prod - 0.5).astype(np.float32).astype(np.float64)
+        for f in (two, fused):
+            dp = np.maximum(dp, np.abs(np.maximum(f, 0.0) - exact))
+    return torch.from_numpy(dp)
+
+
 def _axis(n_in: int, n_out: int, align_corners: bool = True):
     """Per output index: i0, i1 (clamped), im = i0 - 1 (clamped), weight l of i1, and the position allowance dp."""
     i = torch.arange(n_out, dtype=torch.float64)
     if align_corners:
         p = i * ((n_in - 1) / (n_out - 1)) if n_out > 1 else torch.zeros_like(i)
         dp = _f32_position_error(n_in, n_out)
-    else:   # torch's half-pixel form (only used to build faults in the self-test)
+    else:   # torch's half-pixel form (the position-embedding resize; the align_corners kernels' self-tests build faults with it)
         p = ((i + 0.5) * (n_in / n_out) - 0.5).clamp(min=0)
-        dp = torch.zeros_like(i)
+        dp = _f32_halfpixel_error(n_in, n_out)
     i0 = p.floor().long().clamp(max=n_in - 1)
     return i0, (i0 + 1).clamp(max=n_in - 1), (i0 - 1).clamp(min=0), p - i0, dp
 
@@ -341,7 +357,11 @@ def x3_parts(raw, shape):
 
 def check_x3(raw, shape, f32_vals, what):
     """An x3 operand copy: hi = RN16(v) exactly and hi + lo / 2048 within 2^-23 |v| + 2^-36 of the kernel's f32 value v."""
-    hi, lo = x3_parts(raw, shape)
+    return check_x3_parts(*x3_parts(raw, shape), f32_vals, what)
+
+
+def check_x3_parts(hi, lo, f32_vals, what):
+    """The same on decoded (hi, lo) values -- for a part of an x3 tensor, such as the interior of a zero-halo image."""
     v = f32_vals.double().cpu()
     exp_hi = v.float().to(torch.float16).double()
     bad_hi = ~(hi == exp_hi)

@@ -36,7 +36,7 @@ def test_header_symbols_exported():
 def test_binding_struct_sizes_match_the_library():
     """The ctypes mirrors of the public structs have exactly the size the LIBRARY was compiled with (soccdpt_sizeof): a field added to
     soccdpt_igemm_args / soccdpt_config without the binding following is caught here and at load_library()."""
-    from soccdpt_amd.lib import CalibOptions, CalibReport, IgemmArgs, KernelStat, SoccdptConfig, TrainAuxArgs, TrainLayerBwdArgs, load_library
+    from soccdpt_amd.lib import CalibOptions, CalibReport, FwdAuxArgs, IgemmArgs, KernelStat, SoccdptConfig, TrainAuxArgs, TrainLayerBwdArgs, load_library
     L = load_library()
     assert L.soccdpt_sizeof(3) == ctypes.sizeof(CalibReport)
     assert L.soccdpt_sizeof(4) == ctypes.sizeof(CalibOptions) == 20
@@ -45,6 +45,7 @@ def test_binding_struct_sizes_match_the_library():
     assert L.soccdpt_sizeof(2) == ctypes.sizeof(KernelStat)
     assert L.soccdpt_sizeof(5) == ctypes.sizeof(TrainLayerBwdArgs) == 14 * 4 + 7 * 8
     assert L.soccdpt_sizeof(6) == ctypes.sizeof(TrainAuxArgs) == 2 * 4 + 6 * 8 + 3 * 4 + 4 + 12 * 8
+    assert L.soccdpt_sizeof(7) == ctypes.sizeof(FwdAuxArgs) == 2 * 4 + 6 * 8 + 3 * 4 + 4 + 12 * 8
     assert L.soccdpt_sizeof(99) == 0
 
 
@@ -197,7 +198,7 @@ def test_prototype_table_matches_the_header():
     integer or float of the same width.  A parameter added to the header without the binding following fails here; no built library is needed."""
     from soccdpt_amd.lib import PROTOTYPES
     header = _header_prototypes()
-    assert sorted(header) == _declared() and len(header) == 82, "the prototype regex and the symbol regex disagree about what the header declares"
+    assert sorted(header) == _declared() and len(header) == 83, "the prototype regex and the symbol regex disagree about what the header declares"
     assert sorted(PROTOTYPES) == sorted(header), (sorted(set(header) - set(PROTOTYPES)), sorted(set(PROTOTYPES) - set(header)))
     assert list(PROTOTYPES) == list(header), "the table follows the header's order"
     for name, (restype, argtypes) in PROTOTYPES.items():
