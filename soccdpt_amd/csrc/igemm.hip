@@ -353,6 +353,11 @@ int launch_igemm(const IgemmDesc& d, hipStream_t stream, std::string& err) {
     }
     if (d.seg2_k && (d.taps != 1 || d.gather1 || !d.grp_rows || d.seg2_k % 128 != 0 || d.seg2_k >= d.Cin)) { err = "igemm: bad second-segment descriptor"; return 1; }
     if (d.grp_rows && (d.taps != 1 || d.gather1)) { err = "igemm: row groups are a plain-mode feature"; return 1; }
+    if (d.taps == 1 && !d.gather1) {   // plain mode: row m starts at X + m * ldx and is staged in 16-byte pieces (x3 rows: the x3 branch below asks for 16 elements)
+        const int esz = d.f32 ? 4 : 2;   // bytes of an X element as ldx counts it: f32; bf16 / fp16 (x2w activations are fp16)
+        if (!d.x3 && (d.ldx < 0 || (long long)d.ldx * esz % 16 != 0)) { err = "igemm: plain-mode rows must start at multiples of 16 bytes (ldx)"; return 1; }
+        if (!d.grp_rows && !d.seg2_k && d.ldx < d.Cin) { err = "igemm: ldx is shorter than a row (ldx >= Cin without row groups or a second segment)"; return 1; }
+    }
     if (d.wt_grp_rows && (d.taps != 1 || d.gather1 || d.wt_grp_rows % 64 != 0 || d.N > 9 * d.wt_grp_rows || d.N % d.wt_grp_rows != 0 ||
                           (!d.wt_kx && d.wt_base - d.wt_rp - 1 + (d.wt_odd < 0 ? d.wt_odd : 0) < 0))) { err = "igemm: bad weight row-group descriptor"; return 1; }
     if ((d.out_halo || d.res2_h) && (d.H <= 0 || d.W <= 0)) { err = "igemm: halo output / sampled residual need H, W"; return 1; }

@@ -40,9 +40,15 @@ def gamma(n: float) -> float:
     return n * U / (1.0 - n * U)
 
 
-def gemm_gamma(fmt: str, K: int) -> float:
-    """Relative bound (times sum |w x|) of a K-long dot product of the igemm / depth-tail kernels in operand format fmt."""
+def gemm_gamma(fmt: str, K: int, mf: int = 16) -> float:
+    """Relative bound (times sum |w x|) of a K-long dot product of the igemm / depth-tail kernels in operand format fmt.
+    mf = 32: the v_mfma_f32_32x32x16 forms of the 16-bit tiles add 16 exact products per k-step -- by the same rule a pairwise sum of 4 levels plus the
+    accumulator add, 5 roundings per ceil(K / 16) steps."""
     steps = -(-K // 32)
+    if fmt in ("bf16", "f16") and mf == 32:
+        return gamma((MFMA_ROUNDINGS - 1) * -(-K // 16))
+    if mf != 16:
+        raise ValueError((fmt, mf))
     if fmt in ("bf16", "f16"):
         return gamma(MFMA_ROUNDINGS * steps)
     if fmt == "x2w":
