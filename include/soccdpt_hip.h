@@ -51,6 +51,7 @@ extern "C" {
 #define SOCCDPT_BACKBONE_SWIN2T16_256 0 /* dpt_swin2_tiny_256 */
 #define SOCCDPT_BACKBONE_SWIN2B24_384 1 /* dpt_swin2_base_384 */
 #define SOCCDPT_BACKBONE_VITB_RN50_384 2 /* dpt_hybrid_384: ResNetV2-50 stem + ViT-B/16 (model/loader.py:115-120, backbones/vit.py:147-258) */
+#define SOCCDPT_BACKBONE_SWIN2L24_384 3 /* dpt_swin2_large_384 (model/loader.py:58-63): forward only, soccdpt_train_* refuses it */
 
 /* dtype codes for soccdpt_bind_weight */
 #define SOCCDPT_DTYPE_F32 0
@@ -691,12 +692,12 @@ int soccdpt_op_train_aux(const soccdpt_train_aux_args* args, void* dev_scratch, 
  * 3 x3, for CVT also 5 = IEEE fp16 without saturation; hybrid.hip kinds: out_mode 0 bf16, 1 fp16, 2 f32, 3 x3), bits 8-11 = 1 + the halo's format where it
  * differs from fmt (0: the same).  "op" = a tensor in that format (2 bytes per element, 4 for f32 / x3).  *path_out (opt) receives the SOCCDPT_FWD_PATH_* of
  * the kernel the launcher chose (0 for launchers with one kernel).
- *   PATCH_EMBED      Conv2d(3, C0, 4, 4) + LayerNorm(C0, eps 1e-5).  dim {B, S, C0}; C0 <= 128, S % 32 == 0.  in {x [B][3][S][S], w [C0][48], bias [C0], g [C0], beta [C0]};
- *                    out {xf [B (S/4)^2][C0], xb op opt, wT [48][128] (launch_patch_w's output: the weight the kernel reads)}.
+ *   PATCH_EMBED      Conv2d(3, C0, 4, 4) + LayerNorm(C0, eps 1e-5).  dim {B, S, C0}; C0 <= 128 or C0 == 192, S % 32 == 0.  in {x [B][3][S][S], w [C0][48], bias [C0], g [C0], beta [C0]};
+ *                    out {xf [B (S/4)^2][C0], xb op opt, wT [48][128] ([48][192] for C0 == 192) (launch_patch_w's output: the weight the kernel reads)}.
  *   LN_RESIDUAL      xf = (residual ? xf : 0) + row_scale * (LN(y) g + beta), eps 1e-5.  dim {M, C, res, rows_per_scale}; flags bit 0 residual, bit 1 merge (xb in the
  *                    PatchMerging layout [B][res/2][res/2][4C]).  in {y [M][C], g [C], beta [C], row_scale [ceil(M / rows_per_scale)] opt}; out {xf [M][C], xb op opt,
  *                    halo [B][res+2][res+2][C] op (halo format) opt, halo_f32 alike opt}: the interior of a halo is written, its ring is not.  res: the side of the token
- *                    grid (M = B res^2), needed by merge and the halos.  C <= 1024; C % 256 == 0 takes the float4 kernels: every tensor 16-byte aligned then.
+ *                    grid (M = B res^2), needed by merge and the halos.  C <= 1024, or 1280 / 1536; C % 256 == 0 takes the float4 kernels: every tensor 16-byte aligned then.
  *   MERGE_GATHER     dim {B, R, C, elem_bytes}; R even, C elem_bytes % 16 == 0, 16-byte aligned.  in {in [B][R][R][C]}; out {out [B][R/2][R/2][4C]}.
  *   BILINEAR         align_corners = True.  dim {B, h, w, H, W, C}; flags bit 0: the input is 16-bit (format fmt), bit 1: out_op is a zero-halo image.  in {in [B][h][w][C]};
  *                    out {out_f32 [B][H][W][C] opt, out_op op opt (plain, or [B][H+2][W+2][C]), out_f32_halo opt}.  C % 4 == 0; x3 needs f32 input and C % 16 == 0; 16-byte

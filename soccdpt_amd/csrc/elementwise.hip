@@ -35,24 +35,32 @@ __device__ __forceinline__ float row_sum(float v) {
 // call site /root/reference/SOccDPT/model/backbones/swin2.py:25-27).  One wave per token.
 // x NCHW f32 [B,3,S,S] -> xf [M,C0] f32 residual stream, xb [M,C0] bf16 GEMM operand.
 // ---------------------------------------------------------------------------------------------
-template <bool F16>
+template <int CPL, bool F16>  // CPL: channels per lane, 2 (C0 <= 128) or 3 (C0 = 192, dpt_swin2_large_384)
 __global__ __launch_bounds__(256) void patch_embed_kernel(const float* __restrict__ x, const float* __restrict__ w,
                                                            const float* __restrict__ bias, const float* __restrict__ g,
                                                            const float* __restrict__ beta, float* __restrict__ xf,
                                                            bf16_t* __restrict__ xb, int B, int S, int C0, int x3) {
-    // lane owns output channels `lane` and `lane + 64`; their 2 x 48 weights live in registers for the whole kernel,
+    // lane owns output channels `lane` and `lane + 64` (CPL = 3: and `lane + 128`); their CPL x 48 weights live in registers for the whole kernel,
     // the 48 patch values are broadcast lane -> SGPR with v_readlane (no LDS, no shuffles)
+    static_assert(CPL == 2 || CPL == 3, "patch_embed: 2 or 3 channels per lane");
+    constexpr int LD = 64 * CPL;   // row length of the prepared filter: patch_w_ld(C0)
     const int G = S / 4, lane = threadIdx.x & 63;
-    const bool a0 = lane < C0, a1 = lane + 64 < C0;
+    const bool a0 = lane < C0, a1 = lane + 64 < C0, a2 = CPL == 3 && lane + 128 < C0;
     typedef __attribute__((ext_vector_type(2))) float f32x2;
     f32x2 wv[48];  // (channel lane, channel lane + 64) pairs: one v_pk_fma_f32 per patch value
+    float wc[CPL == 3 ? 48 : 1];   // CPL = 3: channel lane + 128
 #pragma unroll
-    for (int k = 0; k < 48; ++k) {  // w is the prepared transpose [48][128] (zero-padded): coalesced
-        wv[k] = f32x2{w[k * 128 + lane], w[k * 128 + 64 + lane]};
+    for (int k = 0; k < 48; ++k) {  // w is the prepared transpose [48][LD] (zero-padded): coalesced
+        wv[k] = f32x2{w[k * LD + lane], w[k * LD + 64 + lane]};
+        if constexpr (CPL == 3) wc[k] = w[k * LD + 128 + lane];
     }
     const float b0 = a0 ? bias[lane] : 0.f, b1 = a1 ? bias[lane + 64] : 0.f;
     const float g0 = a0 ? g[lane] : 0.f, g1 = a1 ? g[lane + 64] : 0.f;
     const float e0 = a0 ? beta[lane] : 0.f, e1 = a1 ? beta[lane + 64] : 0.f;
+    float b2 = 0.f, g2 = 0.f, e2 = 0.f;
+    if constexpr (CPL == 3) {
+        if (a2) { b2 = bias[lane + 128]; g2 = g[lane + 128]; e2 = beta[lane + 128]; }
+    }
     const int wave_global = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6), nwaves = gridDim.x * (blockDim.x >> 6);
     // A wave walks STRIPS of 8 horizontally adjacent tokens: the strip's 12 (channel, ky) rows are 12 x 128 contiguous bytes of x,
     // fetched with 6 fully coalesced loads (one token at a time touched 12 lines for 16 bytes each, and the 8 tokens sharing a line
@@ -78,6 +86,7 @@ __global__ __launch_bounds__(256) void patch_embed_kernel(const float* __restric
 #pragma unroll
         for (int t = 0; t < 8; ++t) {
             f32x2 oa = f32x2{b0, b1}, ob = f32x2{0.f, 0.f};  // two accumulator chains halve the dependent-FMA latency
+            float oc = b2, od = 0.f;                           // CPL = 3: the same two chains of channel lane + 128
 #pragma unroll
             for (int k = 0; k < 48; k += 2) {
                 const int ia = (k >> 2) * 32 + t * 4 + (k & 3), ib = ia + 1;  // k = (c*4 + ky)*4 + kx; kx and kx+1 share the row
@@ -85,12 +94,17 @@ __global__ __launch_bounds__(256) void patch_embed_kernel(const float* __restric
                 const float vb = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, cur[ib >> 6]), ib & 63));
                 oa = __builtin_elementwise_fma(f32x2{va, va}, wv[k], oa);
                 ob = __builtin_elementwise_fma(f32x2{vb, vb}, wv[k + 1], ob);
+                if constexpr (CPL == 3) { oc = __builtin_fmaf(va, wc[k], oc); od = __builtin_fmaf(vb, wc[k + 1], od); }
             }
-            const float o0 = oa[0] + ob[0], o1 = oa[1] + ob[1];
+            const float o0 = oa[0] + ob[0], o1 = oa[1] + ob[1], o2 = oc + od;
             const int tok = tok0 + t;
-            const float mean = wave_sum((a0 ? o0 : 0.f) + (a1 ? o1 : 0.f)) / (float)C0;
-            const float d0 = a0 ? o0 - mean : 0.f, d1 = a1 ? o1 - mean : 0.f;
-            const float rstd = rsqrtf(wave_sum(d0 * d0 + d1 * d1) / (float)C0 + 1e-5f);
+            float s12 = (a0 ? o0 : 0.f) + (a1 ? o1 : 0.f);
+            if constexpr (CPL == 3) s12 += a2 ? o2 : 0.f;
+            const float mean = wave_sum(s12) / (float)C0;
+            const float d0 = a0 ? o0 - mean : 0.f, d1 = a1 ? o1 - mean : 0.f, d2 = a2 ? o2 - mean : 0.f;
+            float q12 = d0 * d0 + d1 * d1;
+            if constexpr (CPL == 3) q12 += d2 * d2;
+            const float rstd = rsqrtf(wave_sum(q12) / (float)C0 + 1e-5f);
             if (a0) {
                 const float y = d0 * rstd * g0 + e0;
                 xf[(size_t)tok * C0 + lane] = y;
@@ -101,25 +115,38 @@ __global__ __launch_bounds__(256) void patch_embed_kernel(const float* __restric
                 xf[(size_t)tok * C0 + lane + 64] = y;
                 if (xb) { if (x3) x3_store1(xb, (size_t)tok * C0 + lane + 64, y); else xb[(size_t)tok * C0 + lane + 64] = f2h<F16>(y); }
             }
+            if constexpr (CPL == 3) {
+                if (a2) {
+                    const float y = d2 * rstd * g2 + e2;
+                    xf[(size_t)tok * C0 + lane + 128] = y;
+                    if (xb) { if (x3) x3_store1(xb, (size_t)tok * C0 + lane + 128, y); else xb[(size_t)tok * C0 + lane + 128] = f2h<F16>(y); }
+                }
+            }
         }
     }
 }
 
+// The kernel is instantiated for two (C0 <= 128) and three (C0 = 192) channels per lane, nothing between or beyond
+static bool patch_c0_ok(int C0) { return C0 <= 128 || C0 == 192; }
+
 int launch_patch_embed(const float* x, const float* w, const float* bias, const float* g, const float* beta, float* xf, bf16_t* xb,
                        int hf, int B, int S, int C0, hipStream_t st, std::string& err) {
-    if (C0 > 128) { err = "patch_embed: C0 > 128"; return 1; }
+    if (!patch_c0_ok(C0)) { err = "patch_embed: C0 > 128 (and not 192)"; return 1; }
     if (S % 32) { err = "patch_embed: image size must be a multiple of 32 (strips of 8 patches)"; return 1; }
     const int nstrips = B * (S / 4) * (S / 32);
     int blocks = (nstrips + 3) / 4;  // one 8-token strip per wave and pass; the FMA chain is latency-bound, so favour waves per SIMD
     if (blocks > 2048) blocks = 2048;
     if (blocks < 1) blocks = 1;
-    LAUNCH_HF(hf == 1, patch_embed_kernel, dim3(blocks), dim3(256), 0, st, x, w, bias, g, beta, xf, xb, B, S, C0, hf == 3 ? 1 : 0);   // hf: 0 bf16, 1 fp16, 3 x3 (half16.h)
+#define PE_CASE(CPL, F) SOCCDPT_LAUNCH((patch_embed_kernel<CPL, F>), dim3(blocks), dim3(256), 0, st, x, w, bias, g, beta, xf, xb, B, S, C0, hf == 3 ? 1 : 0)
+    if (C0 <= 128) { if (hf == 1) PE_CASE(2, true); else PE_CASE(2, false); }   // hf: 0 bf16, 1 fp16, 3 x3 (half16.h)
+    else { if (hf == 1) PE_CASE(3, true); else PE_CASE(3, false); }
+#undef PE_CASE
     return check_launch("patch_embed", err);
 }
 
 // ---------------------------------------------------------------------------------------------
 // Swin-V2 residual post-norm: x = x + LN(y) (timm SwinTransformerV2Block; HF modeling_swinv2.py:697-703),
-// or x = LN(y) after PatchMerging.reduction.  One wave per token row, C <= 1024.
+// or x = LN(y) after PatchMerging.reduction.  One wave per token row, C <= 1024 (multiples of 256: up to 1536).
 // Writes the f32 residual stream, its bf16 copy (next GEMM operand) and, for hooked blocks, the
 // zero-haloed NHWC bf16 feature map the decoder's 3x3 reassemble conv reads
 // (/root/reference/SOccDPT/model/backbones/swin_common.py:38-52 does this as Transpose+Unflatten).
@@ -154,7 +181,7 @@ int launch_ln_residual(const float* y, const float* g, const float* beta, float*
     hf = (hf == 1 || hf_halo == 1 || x3 || x3h);   // 16-bit outputs beside an x3 one are IEEE fp16 (SOCCDPT_PREC_MIXED)
     const int vpl = (C + 63) / 64;
     dim3 grid((M + 3) / 4), block(256);
-    if (C % 256 == 0 && C <= 1024) {
+    if (C % 256 == 0 && C <= 1536) {   // 1280 / 1536 (stage 3 of dpt_swin2_large_384) exist on this route only: 5 / 6 float4 groups per lane
         // float4 loads of y / g / beta / xf, 8- and 16-byte stores of the copies
         if (!ptr_aligned16(y) || !ptr_aligned16(g) || !ptr_aligned16(beta) || !ptr_aligned16(xf) || !ptr_aligned16(xb) || !ptr_aligned16(halo) || !ptr_aligned16(halo_f32)) {
             err = "ln_residual: C % 256 == 0 reads and writes float4: 16-byte aligned tensors";
@@ -166,7 +193,10 @@ int launch_ln_residual(const float* y, const float* g, const float* beta, float*
         if (hf) SOCCDPT_LAUNCH((ln_residual_v4_kernel<V, true>), grid, block, 0, st, y, g, beta, xf, xb, halo, halo_f32, M, C, residual, res, merge, x3, x3h, row_scale, rows_per_scale);  \
         else SOCCDPT_LAUNCH((ln_residual_v4_kernel<V, false>), grid, block, 0, st, y, g, beta, xf, xb, halo, halo_f32, M, C, residual, res, merge, x3, x3h, row_scale, rows_per_scale);    \
     } while (0)
-        switch (C / 256) { case 1: LN4_CASE(1); break; case 2: LN4_CASE(2); break; case 3: LN4_CASE(3); break; default: LN4_CASE(4); break; }
+        switch (C / 256) {
+            case 1: LN4_CASE(1); break; case 2: LN4_CASE(2); break; case 3: LN4_CASE(3); break; case 4: LN4_CASE(4); break;
+            case 5: LN4_CASE(5); break; default: LN4_CASE(6); break;
+        }
 #undef LN4_CASE
         return check_launch("ln_residual", err);
     }
@@ -176,7 +206,7 @@ int launch_ln_residual(const float* y, const float* g, const float* beta, float*
         else SOCCDPT_LAUNCH((ln_residual_kernel<V, false>), grid, block, 0, st, y, g, beta, xf, xb, halo, halo_f32, M, C, residual, res, merge, x3, x3h, row_scale, rows_per_scale);    \
     } while (0)
     const int V = vpl <= 2 ? 2 : (vpl <= 4 ? 4 : (vpl <= 8 ? 8 : (vpl <= 12 ? 12 : 16)));
-    if (vpl > 16) { err = "ln_residual: C > 1024"; return 1; }
+    if (vpl > 16) { err = "ln_residual: C > 1024 (beyond it only C = 1280 and 1536, on the float4 route)"; return 1; }
     if (path) *path = SOCCDPT_FWD_PATH_LN_SCALAR | V;
     if (V == 2) LN_CASE(2);
     else if (V == 4) LN_CASE(4);
@@ -577,16 +607,18 @@ __global__ void conv_w_f32_kernel(const float* __restrict__ in, const float* __r
         if constexpr (X3) x3_store1(out, i, v); else out[i] = v;
     }
 }
-// patch-embed weight [C0][48] -> [48][128] zero-padded (coalesced per-lane loads in patch_embed_kernel)
-__global__ void patch_w_kernel(const float* __restrict__ w, float* __restrict__ out, int C0) {
+// patch-embed weight [C0][48] -> [48][ld] zero-padded, ld = patch_w_ld(C0) (coalesced per-lane loads in patch_embed_kernel)
+__global__ void patch_w_kernel(const float* __restrict__ w, float* __restrict__ out, int C0, int ld) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < 48 * 128) {
-        const int k = i / 128, n = i % 128;
+    if (i < 48 * ld) {
+        const int k = i / ld, n = i % ld;
         out[i] = n < C0 ? w[n * 48 + k] : 0.f;
     }
 }
 int launch_patch_w(const float* w, float* out, int C0, hipStream_t st, std::string& err) {
-    SOCCDPT_LAUNCH(patch_w_kernel, dim3(24), dim3(256), 0, st, w, out, C0);
+    if (!patch_c0_ok(C0)) { err = "patch_w: C0 > 128 (and not 192)"; return 1; }
+    const int ld = patch_w_ld(C0);
+    SOCCDPT_LAUNCH(patch_w_kernel, dim3(48 * ld / 256), dim3(256), 0, st, w, out, C0, ld);   // 24 blocks at ld = 128, 36 at 192
     return check_launch("patch_w", err);
 }
 // BatchNorm2d eval fold (model/SOccDPT.py:668): scale = g / sqrt(var + eps), shift = b - mean * scale

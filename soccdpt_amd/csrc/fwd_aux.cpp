@@ -40,7 +40,7 @@ int fwd_plan(const soccdpt_fwd_aux_args& a, std::string& err) {
             if (!dims(3)) return bad(kDims);
             if (!ins(5) || !a.out[0] || !a.out[2]) return bad(kNull);
             if (!hf_ok) return bad(kFmt);
-            if (d[2] > 128) return bad("PATCH_EMBED: C0 > 128");                       // launch_patch_embed's own conditions: it is the second launch
+            if (d[2] > 128 && d[2] != 192) return bad("PATCH_EMBED: C0 > 128 (and not 192)");   // launch_patch_embed's own conditions: it is the second launch (out[2]: [48][patch_w_ld(C0)])
             if (d[1] % 32) return bad("PATCH_EMBED: the image side must be a multiple of 32");
             if (fmt == 3 && d[2] % 16) return bad("PATCH_EMBED: x3 rows are multiples of 16 elements");
             return 0;

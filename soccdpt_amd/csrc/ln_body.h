@@ -77,7 +77,7 @@ __device__ __forceinline__ void ln_residual_row(const float* __restrict__ y, con
     }
 }
 
-// Same, for C % 256 == 0 (C = 256 / 512 / 768 / 1024): a lane owns float4 groups (16-byte loads and stores, a quarter of the memory
+// Same, for C % 256 == 0 (C = 256 / 512 / 768 / 1024, and 1280 / 1536 = V4 5 / 6 for dpt_swin2_large_384's stage 3): a lane owns float4 groups (16-byte loads and stores, a quarter of the memory
 // instructions; base_384's 47 launches per forward are mostly these widths).
 template <int V4, bool F16>  // float4 groups per lane = C / 256
 __device__ __forceinline__ void ln_residual_v4_row(const float* __restrict__ y, const float* __restrict__ g,

@@ -42,6 +42,14 @@ inline Arch arch_swin2b24_384() {
     for (int i = 0; i < 4; ++i) { a.depths[i] = d[i]; a.heads[i] = hd[i]; a.pretrained_window[i] = pw[i]; a.hooks[i] = hk[i]; }
     return a;
 }
+// swinv2_large_window12to24_192to384_22kft1k: base's depths, windows and hooks at embed 192, heads (6, 12, 24, 48); stage 3 is 1536 wide
+inline Arch arch_swin2l24_384() {
+    Arch a = arch_swin2b24_384();
+    a.embed = 192;
+    const int hd[4] = {6, 12, 24, 48};
+    for (int i = 0; i < 4; ++i) a.heads[i] = hd[i];
+    return a;
+}
 inline Arch arch_vitb_rn50_384() {
     Arch a;
     a.hybrid = true; a.img = 384; a.patch = 16;

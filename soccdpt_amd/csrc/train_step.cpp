@@ -478,10 +478,16 @@ bool any_grad(const Handle& h, Span s) {
     return false;
 }
 
+// the backward kernels are instantiated and tested for these three models' widths; a wider Swin-V2 (dpt_swin2_large_384: 1536 channels, 48 heads) runs the forward path only
+static bool train_backbone_ok(const Handle& h) {
+    return h.cfg.backbone == SOCCDPT_BACKBONE_SWIN2T16_256 || h.cfg.backbone == SOCCDPT_BACKBONE_SWIN2B24_384 || h.cfg.backbone == SOCCDPT_BACKBONE_VITB_RN50_384;
+}
+
 int check_train(Handle& h, int B, const void* ws, size_t ws_bytes, std::string& err) {
     if (h.cfg.precision != SOCCDPT_PREC_F32) { err = "soccdpt_train_*: the training step is built for SOCCDPT_PREC_F32 handles only"; return 1; }
     if (h.arch.hybrid && h.arch.grid() != 24) { err = "soccdpt_train_*: the ViT-hybrid encoder trains at 384 x 384 (position embedding used as stored)"; return 1; }
     if (h.cfg.features != 256 || h.cfg.num_classes != 3) { err = "soccdpt_train_*: features must be 256 and num_classes 3"; return 1; }
+    if (!train_backbone_ok(h)) { err = "soccdpt_train_*: the training step is built for dpt_swin2_tiny_256, dpt_swin2_base_384 and dpt_hybrid_384; dpt_swin2_large_384 is forward-only"; return 1; }
     if (B < 1 || !ws) { err = "soccdpt_train_*: bad arguments"; return 1; }
     for (const auto& w : h.weights)
         if (!w.ptr) { err = "soccdpt_train_*: weight not bound: " + w.key; return 1; }
@@ -681,6 +687,7 @@ int train_workspace_tensor(Handle& h, int B, const char* name, size_t* byte_offs
 }
 
 size_t train_workspace_bytes(Handle& h, int B) {
+    if (!train_backbone_ok(h)) return 0;   // no training step for this model: nothing to size (check_train names the reason)
     TArena ar(nullptr);
     Tape T;
     carve(h, B, ar, T);

@@ -397,6 +397,9 @@ class SOccDPT_V3(SOccDPT):
         segmentation [B,C,S,S]) at network resolution -- what SOccDPT_V3.forward hands to the up-sampling / criterion.  Exact f32
         (precision=PREC_F32); follow it with backward(d_inv, d_seg)."""
         from ..lib import PREC_F32
+        from .spec import FORWARD_ONLY_BACKBONES, TRAIN_REFUSAL
+        if self._engine_backbone() in FORWARD_ONLY_BACKBONES:   # before anything is bound or allocated for a step that does not exist
+            raise RuntimeError(TRAIN_REFUSAL)
         if self.precision != PREC_F32:
             raise RuntimeError("the training step is built for precision=PREC_F32 (exact-f32 MFMA); construct the model with it")
         img = backbone_image_size(self._engine_backbone())

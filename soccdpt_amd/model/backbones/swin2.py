@@ -98,3 +98,9 @@ def _make_pretrained_swin2b24_384(pretrained, hooks=None):
     assert not pretrained, "no network access: load weights through load_net / load_state_dict"
     arch = SWIN_ARCHS["swin2b24_384"]
     return SwinBackbone(SwinTransformerV2Params(arch), arch.hooks if hooks is None else hooks)
+
+
+def _make_pretrained_swin2l24_384(pretrained, hooks=None):
+    assert not pretrained, "no network access: load weights through load_net / load_state_dict"
+    arch = SWIN_ARCHS["swin2l24_384"]
+    return SwinBackbone(SwinTransformerV2Params(arch), arch.hooks if hooks is None else hooks)

@@ -4,7 +4,7 @@ _make_encoder / _make_scratch / Interpolate / ResidualConvUnit_custom / FeatureF
 convolutions with fused ReLU / bias / residual epilogues, bilinear resize) runs in libsoccdpt_hip.so."""
 import torch.nn as nn
 
-from .backbones.swin2 import _make_pretrained_swin2b24_384, _make_pretrained_swin2t16_256
+from .backbones.swin2 import _make_pretrained_swin2b24_384, _make_pretrained_swin2l24_384, _make_pretrained_swin2t16_256
 from .backbones.vit import _make_pretrained_vitb_rn50_384
 from .spec import HYBRID_ARCHS, SWIN_ARCHS
 
@@ -20,6 +20,8 @@ def _make_encoder(backbone, features, use_pretrained, groups=1, expand=False, ex
         pretrained = _make_pretrained_swin2t16_256(use_pretrained, hooks=hooks)
     elif backbone == "swin2b24_384":
         pretrained = _make_pretrained_swin2b24_384(use_pretrained, hooks=hooks)
+    elif backbone == "swin2l24_384":
+        pretrained = _make_pretrained_swin2l24_384(use_pretrained, hooks=hooks)
     elif backbone == "vitb_rn50_384":
         pretrained = _make_pretrained_vitb_rn50_384(use_pretrained, hooks=hooks, use_vit_only=use_vit_only, use_readout=use_readout)
     else:

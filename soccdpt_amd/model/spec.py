@@ -49,6 +49,8 @@ SWIN_ARCHS: Dict[str, SwinV2Arch] = {
                                (2, 2, 6, 2), (3, 6, 12, 24), 16, (0, 0, 0, 0), (1, 1, 5, 1)),
     "swin2b24_384": SwinV2Arch("swin2b24_384", "swinv2_base_window12to24_192to384_22kft1k", 384, 4, 128,
                                (2, 2, 18, 2), (4, 8, 16, 32), 24, (12, 12, 12, 6), (1, 1, 17, 1)),
+    "swin2l24_384": SwinV2Arch("swin2l24_384", "swinv2_large_window12to24_192to384_22kft1k", 384, 4, 192,
+                               (2, 2, 18, 2), (6, 12, 24, 48), 24, (12, 12, 12, 6), (1, 1, 17, 1)),
 }
 
 # model_type -> backbone (only the backbones this build implements on the HIP path
@@ -66,6 +68,12 @@ MODEL_TYPE_TO_BACKBONE: Dict[str, str] = {
     "dpt_large_384": "vitl16_384",
     "dpt_hybrid_384": "vitb_rn50_384",
 }
+
+# Backbones with a forward path and no training step (soccdpt_train_* refuses them with the same sentence: csrc/train_step.cpp check_train)
+FORWARD_ONLY_BACKBONES = ("swin2l24_384",)
+TRAIN_REFUSAL = ("the training step is built for dpt_swin2_tiny_256, dpt_swin2_base_384 and dpt_hybrid_384; "
+                 "dpt_swin2_large_384 is forward-only")
+
 
 def backbone_image_size(backbone: str) -> int:
     """Network input size of a backbone this build implements (model/loader.py:141-272 net_w / net_h)."""

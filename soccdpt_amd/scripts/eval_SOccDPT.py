@@ -174,6 +174,9 @@ def main(args) -> dict:
         assert args.load_seg is None or args.load_seg is False, "V2 does not support loading seg"
     elif args.version == 3:
         model_kwargs["load_depth"] = args.load_depth if args.load_depth is not None else False
+        # the reference's script leaves model_type to the class default, so its -t only names the run; here -t builds that model (without it every
+        # model but dpt_swin2_tiny_256 failed at load_state_dict with size mismatches)
+        model_kwargs["model_type"] = args.model_type
         assert args.load_seg is None or args.load_seg is False, "V3 does not support loading seg"
     net = load_model(arch=SOccDPT, model_kwargs=model_kwargs, device=torch.device("cpu"), model_path=args.load,
                      model_type=args.model_type)

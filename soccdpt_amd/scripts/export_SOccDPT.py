@@ -166,6 +166,7 @@ def _shift_mask(res: int, ws: int, shift: int) -> torch.Tensor:
 SWIN = {   # model/dpt.py:51-89 (hooks), backbones/swin2.py:15-30 (timm model names)
     "swin2t16_256": dict(img=256, patch=4, embed=96, depths=(2, 2, 6, 2), heads=(3, 6, 12, 24), window=16, pretrained=(0, 0, 0, 0), hooks=(1, 1, 5, 1)),
     "swin2b24_384": dict(img=384, patch=4, embed=128, depths=(2, 2, 18, 2), heads=(4, 8, 16, 32), window=24, pretrained=(12, 12, 12, 6), hooks=(1, 1, 17, 1)),
+    "swin2l24_384": dict(img=384, patch=4, embed=192, depths=(2, 2, 18, 2), heads=(6, 12, 24, 48), window=24, pretrained=(12, 12, 12, 6), hooks=(1, 1, 17, 1)),
 }
 
 
