@@ -22,7 +22,7 @@ from .base_model import BaseModel
 from .blocks import Interpolate
 from .dpt import DPTDepthModel
 from .scaled_tanh import ScaledTanh
-from .spec import DEFAULT_DEPTH_WEIGHTS, HYBRID_ARCHS, MODEL_TYPE_TO_BACKBONE, SWIN_ARCHS, backbone_image_size, model_types  # noqa: F401
+from .spec import DEFAULT_DEPTH_WEIGHTS, HYBRID_ARCHS, MODEL_TYPE_TO_BACKBONE, SWIN_ARCHS, VIT_ARCHS, backbone_image_size, model_types  # noqa: F401
 
 # /root/reference/SOccDPT/datasets/bdd_helper.py:53-56
 DATASET_BASE = "~/Datasets/Depth_Dataset_Bengaluru"
@@ -108,7 +108,7 @@ class SOccDPT(BaseModel):
 
     # -- engine plumbing --
     def _engine_backbone(self) -> str:
-        return self.backbone if (self.backbone in SWIN_ARCHS or self.backbone in HYBRID_ARCHS) else "swin2t16_256"
+        return self.backbone if (self.backbone in SWIN_ARCHS or self.backbone in HYBRID_ARCHS or self.backbone in VIT_ARCHS) else "swin2t16_256"
 
     def _sigmoid_flag(self) -> bool:
         return True
@@ -397,9 +397,9 @@ class SOccDPT_V3(SOccDPT):
         segmentation [B,C,S,S]) at network resolution -- what SOccDPT_V3.forward hands to the up-sampling / criterion.  Exact f32
         (precision=PREC_F32); follow it with backward(d_inv, d_seg)."""
         from ..lib import PREC_F32
-        from .spec import FORWARD_ONLY_BACKBONES, TRAIN_REFUSAL
+        from .spec import FORWARD_ONLY_BACKBONES, train_refusal
         if self._engine_backbone() in FORWARD_ONLY_BACKBONES:   # before anything is bound or allocated for a step that does not exist
-            raise RuntimeError(TRAIN_REFUSAL)
+            raise RuntimeError(train_refusal(self._engine_backbone()))
         if self.precision != PREC_F32:
             raise RuntimeError("the training step is built for precision=PREC_F32 (exact-f32 MFMA); construct the model with it")
         img = backbone_image_size(self._engine_backbone())

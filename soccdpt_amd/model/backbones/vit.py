@@ -9,7 +9,7 @@ libsoccdpt_hip.so (csrc/hybrid.hip, igemm.hip, vit_attention.hip).  The snapshot
 import torch
 import torch.nn as nn
 
-from ..spec import HYBRID_ARCHS, HybridArch
+from ..spec import HYBRID_ARCHS, VIT_ARCHS, HybridArch, VitArch
 
 
 class _Holder(nn.Module):
@@ -147,6 +147,64 @@ class HybridBackbone(_Holder):
         self.act_postprocess4 = nn.Sequential(ProjectReadout(E), Transpose(1, 2), nn.Unflatten(2, torch.Size([g, g])),
                                               nn.Conv2d(E, f[3], kernel_size=1, stride=1, padding=0),
                                               nn.Conv2d(f[3], f[3], kernel_size=3, stride=2, padding=1))
+
+
+class PatchEmbedParams(_Holder):
+    """timm PatchEmbed: Conv2d(3, embed, patch, patch) with bias; norm is Identity."""
+
+    def __init__(self, arch: VitArch):
+        super().__init__()
+        self.proj = nn.Conv2d(3, arch.embed, kernel_size=arch.patch, stride=arch.patch)
+
+
+class VisionTransformerParams(_Holder):
+    """timm 0.6.12 VisionTransformer (vit_large_patch16_384): own parameters cls_token, pos_embed; children patch_embed, blocks, norm, head."""
+
+    def __init__(self, arch: VitArch):
+        super().__init__()
+        self.arch = arch
+        self.patch_embed = PatchEmbedParams(arch)
+        self.cls_token = nn.Parameter(torch.zeros(1, 1, arch.embed))
+        self.pos_embed = nn.Parameter(torch.randn(1, arch.grid * arch.grid + 1, arch.embed) * 0.02)
+        self.blocks = nn.Sequential(*[VitBlockParams(arch.embed) for _ in range(arch.depth)])
+        self.norm = nn.LayerNorm(arch.embed, eps=1e-6)    # dead on the DPT path (the last hook fires before it)
+        self.head = nn.Linear(arch.embed, 1000)            # dead on the DPT path
+        self.start_index = 1
+        self.patch_size = [arch.patch, arch.patch]
+
+
+class VitBackbone(_Holder):
+    """`pretrained` of the reference for a plain ViT: .model + act_postprocess1..4 (backbones/utils.py:154-262 make_backbone_default with
+    start_index 1, size [384, 384]): every level is ProjectReadout -> Transpose -> Unflatten -> Conv1x1, then ConvTranspose2d(k = s = 4),
+    ConvTranspose2d(k = s = 2), nothing, Conv3x3 stride 2."""
+
+    def __init__(self, model, features, hooks, vit_features, use_readout="project", grid=24):
+        super().__init__()
+        assert use_readout == "project", "DPT builds its encoders with readout='project' (model/dpt.py:36,107)"
+        self.model = model
+        self.hooks = list(hooks)
+        f, E, g = features, vit_features, grid
+
+        def head(c):
+            return [ProjectReadout(E), Transpose(1, 2), nn.Unflatten(2, torch.Size([g, g])), nn.Conv2d(E, c, kernel_size=1, stride=1, padding=0)]
+        self.act_postprocess1 = nn.Sequential(*head(f[0]), nn.ConvTranspose2d(f[0], f[0], kernel_size=4, stride=4, padding=0, bias=True, dilation=1, groups=1))
+        self.act_postprocess2 = nn.Sequential(*head(f[1]), nn.ConvTranspose2d(f[1], f[1], kernel_size=2, stride=2, padding=0, bias=True, dilation=1, groups=1))
+        self.act_postprocess3 = nn.Sequential(*head(f[2]))
+        self.act_postprocess4 = nn.Sequential(*head(f[3]), nn.Conv2d(f[3], f[3], kernel_size=3, stride=2, padding=1))
+
+
+def _make_vit_b16_backbone(model, features=(96, 192, 384, 768), size=(384, 384), hooks=(2, 5, 8, 11), vit_features=768, use_readout="ignore", start_index=1):
+    """backbones/vit.py:88-121: the module tree around a timm VisionTransformer (`model`, then act_postprocess1..4)."""
+    assert start_index == 1 and tuple(size) == (384, 384), "the MI355X path runs the 384 x 384 models with one class token"
+    return VitBackbone(model, list(features), hooks, vit_features, use_readout=use_readout, grid=size[0] // 16)
+
+
+def _make_pretrained_vitl16_384(pretrained, use_readout="ignore", hooks=None):
+    """backbones/vit.py:124-132: timm vit_large_patch16_384, features [256, 512, 1024, 1024], hooks [5, 11, 17, 23]."""
+    assert not pretrained, "no network access: load weights through load_net / load_state_dict"
+    arch = VIT_ARCHS["vitl16_384"]
+    return _make_vit_b16_backbone(VisionTransformerParams(arch), features=arch.features, hooks=arch.hooks if hooks is None else hooks,
+                                  vit_features=arch.embed, use_readout=use_readout)
 
 
 def _make_pretrained_vitb_rn50_384(pretrained, use_readout="ignore", hooks=None, use_vit_only=False):

@@ -69,10 +69,17 @@ MODEL_TYPE_TO_BACKBONE: Dict[str, str] = {
     "dpt_hybrid_384": "vitb_rn50_384",
 }
 
-# Backbones with a forward path and no training step (soccdpt_train_* refuses them with the same sentence: csrc/train_step.cpp check_train)
-FORWARD_ONLY_BACKBONES = ("swin2l24_384",)
+# Backbones with no training step: swin2l24_384 has a forward path (soccdpt_train_* refuses it with the same sentence: csrc/train_step.cpp check_train);
+# vitl16_384 so far exists in this mirror only (tables, module tree, weights) -- the library does not build it yet
+FORWARD_ONLY_BACKBONES = ("swin2l24_384", "vitl16_384")
 TRAIN_REFUSAL = ("the training step is built for dpt_swin2_tiny_256, dpt_swin2_base_384 and dpt_hybrid_384; "
                  "dpt_swin2_large_384 is forward-only")
+TRAIN_REFUSAL_VIT_LARGE = "no training step is built for dpt_large_384 (ViT-L/16)"
+
+
+def train_refusal(backbone: str) -> str:
+    """The sentence training on a backbone without a training step is refused with."""
+    return TRAIN_REFUSAL_VIT_LARGE if backbone == "vitl16_384" else TRAIN_REFUSAL
 
 
 def backbone_image_size(backbone: str) -> int:
@@ -81,6 +88,8 @@ def backbone_image_size(backbone: str) -> int:
         return SWIN_ARCHS[backbone].img
     if backbone in HYBRID_ARCHS:
         return HYBRID_ARCHS[backbone].img
+    if backbone in VIT_ARCHS:
+        return VIT_ARCHS[backbone].img
     raise AssertionError(f"Backbone '{backbone}' not implemented on the MI355X path")
 
 
@@ -223,6 +232,85 @@ def hybrid_param_shapes(arch: HybridArch) -> "OrderedDict[str, Tuple[int, ...]]"
     return p
 
 
+@dataclass(frozen=True)
+class VitArch:
+    """timm 0.6.12 vit_large_patch16_384 as the reference creates it (/root/reference/SOccDPT/model/backbones/vit.py:124-132);
+    hooks /root/reference/SOccDPT/model/dpt.py:88, reassemble channels /root/reference/SOccDPT/model/blocks.py:96-102."""
+    name: str = "vitl16_384"
+    timm_name: str = "vit_large_patch16_384"
+    img: int = 384
+    patch: int = 16
+    embed: int = 1024
+    depth: int = 24
+    heads: int = 16
+    hooks: Tuple[int, ...] = (5, 11, 17, 23)
+    features: Tuple[int, ...] = (256, 512, 1024, 1024)
+
+    @property
+    def grid(self) -> int:
+        return self.img // self.patch
+
+    def dims(self) -> List[int]:
+        return list(self.features)
+
+
+VIT_ARCHS: Dict[str, VitArch] = {"vitl16_384": VitArch()}
+
+
+def arch_of(backbone: str):
+    """The architecture row of a backbone this build implements."""
+    for table in (SWIN_ARCHS, HYBRID_ARCHS, VIT_ARCHS):
+        if backbone in table:
+            return table[backbone]
+    raise AssertionError(f"Backbone '{backbone}' not implemented on the MI355X path")
+
+
+def vit_block_param_shapes(p, E: int, depth: int) -> None:
+    """model.blocks.<i>.* of a timm VisionTransformer in registration order, appended to p."""
+    for i in range(depth):
+        b = f"model.blocks.{i}."
+        p[b + "norm1.weight"] = (E,)
+        p[b + "norm1.bias"] = (E,)
+        p[b + "attn.qkv.weight"] = (3 * E, E)
+        p[b + "attn.qkv.bias"] = (3 * E,)
+        p[b + "attn.proj.weight"] = (E, E)
+        p[b + "attn.proj.bias"] = (E,)
+        p[b + "norm2.weight"] = (E,)
+        p[b + "norm2.bias"] = (E,)
+        p[b + "mlp.fc1.weight"] = (4 * E, E)
+        p[b + "mlp.fc1.bias"] = (4 * E,)
+        p[b + "mlp.fc2.weight"] = (E, 4 * E)
+        p[b + "mlp.fc2.bias"] = (E,)
+
+
+def vit_param_shapes(arch: VitArch) -> "OrderedDict[str, Tuple[int, ...]]":
+    """Parameters of `pretrained` for vitl16_384 in registration order: `model.*` (timm VisionTransformer: own parameters cls_token / pos_embed first, then
+    patch_embed.proj, blocks, norm, head), then act_postprocess1..4 (backbones/vit.py:88-121 via backbones/utils.py:154-262 make_backbone_default):
+    ProjectReadout, Conv1x1, then ConvTranspose2d(k = s = 4) / ConvTranspose2d(k = s = 2) / nothing / Conv3x3 stride 2."""
+    p: "OrderedDict[str, Tuple[int, ...]]" = OrderedDict()
+    E, f = arch.embed, arch.features
+    p["model.cls_token"] = (1, 1, E)
+    p["model.pos_embed"] = (1, arch.grid * arch.grid + 1, E)
+    p["model.patch_embed.proj.weight"] = (E, 3, arch.patch, arch.patch)
+    p["model.patch_embed.proj.bias"] = (E,)
+    vit_block_param_shapes(p, E, arch.depth)
+    p["model.norm.weight"] = (E,)
+    p["model.norm.bias"] = (E,)
+    p["model.head.weight"] = (1000, E)
+    p["model.head.bias"] = (1000,)
+    tails = {1: (f[0], f[0], 4, 4), 2: (f[1], f[1], 2, 2), 4: (f[3], f[3], 3, 3)}   # ConvTranspose2d weights are [in][out][k][k]
+    for n in (1, 2, 3, 4):
+        a = f"act_postprocess{n}."
+        p[a + "0.project.0.weight"] = (E, 2 * E)
+        p[a + "0.project.0.bias"] = (E,)
+        p[a + "3.weight"] = (f[n - 1], E, 1, 1)
+        p[a + "3.bias"] = (f[n - 1],)
+        if n in tails:
+            p[a + "4.weight"] = tails[n]
+            p[a + "4.bias"] = (f[n - 1],)
+    return p
+
+
 def scratch_param_shapes(arch, features: int = 256) -> "OrderedDict[str, Tuple[int, ...]]":
     """depth_net.scratch.* (blocks.py:139-193, dpt.py:133-140,199-219)."""
     p: "OrderedDict[str, Tuple[int, ...]]" = OrderedDict()
@@ -265,6 +353,10 @@ def v3_state_shapes(backbone: str, features: int = 256, num_classes: int = 3) ->
     if backbone in HYBRID_ARCHS:
         arch = HYBRID_ARCHS[backbone]
         for k, v in hybrid_param_shapes(arch).items():
+            out["depth_net.pretrained." + k] = v
+    elif backbone in VIT_ARCHS:
+        arch = VIT_ARCHS[backbone]
+        for k, v in vit_param_shapes(arch).items():
             out["depth_net.pretrained." + k] = v
     else:
         arch = SWIN_ARCHS[backbone]

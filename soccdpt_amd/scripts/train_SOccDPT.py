@@ -130,9 +130,9 @@ class ReduceLROnPlateau:
 def train_net(SOccDPT_version=3, device="cuda:0", model_type="dpt_swin2_tiny_256", checkpoint_dir="checkpoints", dataset="bdd", base_path="",
               forward_only=False, max_steps=0, run_id="dummy_run", n_synthetic=12, camera_intrinsics_yaml=None, recordings=None, on_batch=None,
               frame_pack=None, frame_pack_required=False, **cfg):
-    from ..model.spec import FORWARD_ONLY_BACKBONES, MODEL_TYPE_TO_BACKBONE, TRAIN_REFUSAL
+    from ..model.spec import FORWARD_ONLY_BACKBONES, MODEL_TYPE_TO_BACKBONE, train_refusal
     if MODEL_TYPE_TO_BACKBONE.get(model_type) in FORWARD_ONLY_BACKBONES:   # before any data is read
-        raise RuntimeError(TRAIN_REFUSAL)
+        raise RuntimeError(train_refusal(MODEL_TYPE_TO_BACKBONE[model_type]))
     p = dict(SWEEP_DEFAULTS)
     unknown = [k for k in cfg if k not in p]
     assert not unknown, f"unknown sweep parameters: {unknown}"

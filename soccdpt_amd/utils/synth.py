@@ -83,6 +83,13 @@ def synth_state_dict(backbone: str = "swin2t16_256", features: int = 256, num_cl
     sd[k4 + "weight"] = sd[k4 + "weight"].abs() * 0.01
     sd[k4 + "bias"] = torch.full((1,), 0.015)
     sd["seg_head.4.weight"] = sd["seg_head.4.weight"] * 12.0
+    if backbone == "vitl16_384":
+        # The pure ViT has no normalisation between the image and the token stream (the Swin models have patch_embed.norm, the hybrid its
+        # weight-standardised stem + GroupNorm), and the hooked tokens reach the decoder un-normalised: a variance-preserving filter on pixel values
+        # up to 509 (no /255: synth_input) gives reassembled maps of 40 .. 140 and inverse depths of 1 .. 7, every point outside the grid.
+        # The filter takes the pixels' scale instead (2^-8: exact), which leaves maps of 0.5 .. 4 like the other models'.
+        k = "depth_net.pretrained.model.patch_embed.proj.weight"
+        sd[k] = sd[k] * (1.0 / 256.0)
     if alias_pretrained:  # the reference registers the encoder twice (model/SOccDPT.py:650)
         for k in list(sd.keys()):
             if k.startswith("depth_net.pretrained."):
