@@ -546,6 +546,9 @@ int soccdpt_op_gn_apply(const float* dev_raw, float* dev_stats, const float* dev
  * model/backbones/vit.py:248): qkv [B*N][3*heads*64] -> out [B*N][heads*64] = softmax(q k^T / 8) v per (sample, head); elements
  * bf16 / f32 / fp16 by `precision`.  N <= 608 (dpt_hybrid_384: N = 577). */
 int soccdpt_op_vit_attention(const void* dev_qkv, void* dev_out, int precision, int B, int N, int heads, void* stream);
+/* The same with the fp16 kernel's second output form: out_x3 != 0 (precision == SOCCDPT_PREC_F16 only) writes `out` as x3 operand pairs from the f32
+ * accumulators, [B*N][heads*64] values = 2 fp16 words each -- what the proj GEMM of a SOCCDPT_PREC_MIXED block reads.  out_x3 == 0: soccdpt_op_vit_attention. */
+int soccdpt_op_vit_attention_out(const void* dev_qkv, void* dev_out, int precision, int out_x3, int B, int N, int heads, void* stream);
 
 /* Weight-gradient GEMM from operands as stored (kernel-level entry, tests): out [Nout][taps * C] f32 = sum over k of A[k][n] * B[k + shift(tap)][c] with
  * A [K][ldA] (the output gradient: rows = tokens, or halo pixels of a 3x3 convolution) and B [K][ldB] (the layer input alike), elements bf16 / fp16 / x3 by
@@ -755,7 +758,8 @@ int soccdpt_op_fwd_aux(const soccdpt_fwd_aux_args* args, uint32_t* path_out, voi
 /* Swin-V2 cosine window attention of one block (timm WindowAttention + shift/partition/reverse):
  * qkv [B*res*res][3*heads*32] -> out [B*res*res][heads*32], elements bf16 / f32 / fp16 by `precision` (SOCCDPT_PREC_*).  cpb_table [(2ws-1)^2][heads] f32 is
  * 16*sigmoid(cpb_mlp(coords)); scale[heads] = exp(min(logit_scale, ln 100)); bias_scratch: heads*ceil(ws*ws/32)^2*1024
- * floats.  Window sizes 16 and 8 (single-pass softmax) and 24 and 12 (online softmax over key tiles) are instantiated. */
+ * floats.  Window sizes 16 and 8 (single-pass softmax) and 24 and 12 (online softmax over key tiles) are instantiated.
+ * Refused before anything is launched (non-zero, soccdpt_last_error): a null pointer, B / res / ws / heads <= 0, res % ws != 0, a shift other than 0 or ws / 2. */
 int soccdpt_op_window_attention(const void* dev_qkv, const float* dev_cpb_table, const float* dev_scale, void* dev_out,
                                 float* dev_bias_scratch, int B, int res, int ws, int shift, int heads, int precision, void* stream);
 

@@ -462,7 +462,18 @@ size_t attn_bias_elems(int ws, int heads) {
     return (size_t)heads * nt * nt * 1024;
 }
 
+int window_attention_geometry(const char* who, int B, int res, int ws, int shift, int heads, std::string& err) {
+    const std::string w(who);
+    if (B <= 0 || res <= 0 || ws <= 0 || heads <= 0) { err = w + ": B, res, ws and heads must be positive"; return 1; }
+    if (res % ws != 0) { err = w + ": res % ws != 0"; return 1; }
+    if (shift < 0 || shift >= ws) { err = w + ": shift outside [0, ws)"; return 1; }
+    if (shift != 0 && shift != ws / 2) { err = w + ": shift must be 0 or ws / 2 (the shift mask is evaluated for the half-window shift)"; return 1; }
+    return 0;
+}
+
 int launch_attn_bias(const float* table, float* bias_acc, int ws, int heads, hipStream_t st, std::string& err) {
+    if (!table || !bias_acc) { err = "attn_bias: null argument"; return 1; }
+    if (ws <= 0 || heads <= 0) { err = "attn_bias: ws and heads must be positive"; return 1; }
     const size_t total = attn_bias_elems(ws, heads);
     size_t blocks = (total + 255) / 256;
     if (blocks > 2048) blocks = 2048;
@@ -472,7 +483,8 @@ int launch_attn_bias(const float* table, float* bias_acc, int ws, int heads, hip
 
 int launch_window_attention_f32(const float* qkv, const float* bias_acc, const float* table, const float* scale, float* out, int B, int res,
                                 int ws, int shift, int heads, hipStream_t st, std::string& err, int x3) {
-    if (res % ws != 0) { err = "window_attention: res % ws != 0"; return 1; }
+    if (!qkv || !scale || !out) { err = "window_attention_f32: null argument"; return 1; }
+    if (window_attention_geometry("window_attention_f32", B, res, ws, shift, heads, err)) return 1;
     const int nw = res / ws;
     static const bool force_any = getenv("SOCCDPT_ATTN_F32_ANY") != nullptr;   // A/B switch: the one-thread-per-query kernel
     // 16 x 16 / 8 x 8 windows too (round 3, late): 0.507 -> 0.296 ms per tiny_256 forward at B = 8 against the whole-score-matrix kernel below
@@ -480,6 +492,7 @@ int launch_window_attention_f32(const float* qkv, const float* bias_acc, const f
     static const int flash_small = getenv("SOCCDPT_ATTN_F32_FLASH16") ? atoi(getenv("SOCCDPT_ATTN_F32_FLASH16")) : 1;
     const bool flash = (ws == 24 || ws == 12) || ((ws == 16 || ws == 8) && flash_small == 1);
     if (flash && !force_any) {   // the streaming MFMA-f32 kernel
+        if (!bias_acc) { err = "window_attention_f32: null bias_acc"; return 1; }
         const int NT = (ws * ws + 31) / 32, NQB = (NT + 3) / 4;
         const unsigned blocksf = (unsigned)(B * nw * nw * heads * NQB);
         if (ws == 24) SOCCDPT_LAUNCH((window_attention_f32_flash_kernel<24>), dim3(blocksf), dim3(256), 0, st, qkv, bias_acc, scale, out, res, shift, heads, x3);
@@ -489,11 +502,13 @@ int launch_window_attention_f32(const float* qkv, const float* bias_acc, const f
         return check_launch("window_attention_f32_flash", err);
     }
     if (ws != 16 && !(ws == 8 && shift == 0)) {  // any other window size: the generic exact kernel (parity mode of base_384)
+        if (!table) { err = "window_attention_f32: null table"; return 1; }
         const int nqb = (ws * ws + 63) / 64;
         SOCCDPT_LAUNCH(window_attention_f32_any_kernel, dim3((unsigned)(B * nw * nw * heads * nqb)), dim3(64), 0, st, qkv, table, scale, out, res, ws,
                            shift, heads, x3);
         return check_launch("window_attention_f32_any", err);
     }
+    if (!bias_acc) { err = "window_attention_f32: null bias_acc"; return 1; }
     const unsigned blocks = (unsigned)(B * nw * nw * heads);
     static PerDeviceOnce attr_done;
     if (attr_done.need()) {
@@ -515,7 +530,8 @@ int launch_window_attention_f32(const float* qkv, const float* bias_acc, const f
 
 int launch_window_attention(const bf16_t* qkv, const float* bias_acc, const float* scale, bf16_t* out, int hf, int B, int res, int ws,
                             int shift, int heads, hipStream_t st, std::string& err, int out_x3) {
-    if (res % ws != 0) { err = "window_attention: res % ws != 0"; return 1; }
+    if (!qkv || !bias_acc || !scale || !out) { err = "window_attention: null argument"; return 1; }
+    if (window_attention_geometry("window_attention", B, res, ws, shift, heads, err)) return 1;
     if (out_x3 && !hf) { err = "window_attention: the x3 output form belongs to the fp16 kernels"; return 1; }
     const int nw = res / ws;
     const unsigned blocks = (unsigned)(B * nw * nw * heads);

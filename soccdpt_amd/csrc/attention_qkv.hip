@@ -266,8 +266,9 @@ bool window_attention_qkv_supported(int ws, int C, int x2w) {
 
 int launch_window_attention_qkv(const bf16_t* x, const void* wqkv, const float* qkv_bias, const float* bias_acc, const float* scale, bf16_t* out, int hf, int x2w,
                                 int B, int res, int ws, int shift, int heads, hipStream_t st, std::string& err, int out_x3, unsigned long long* stamps) {
+    if (!x || !wqkv || !qkv_bias || !bias_acc || !scale || !out) { err = "window_attention_qkv: null argument"; return 1; }
+    if (window_attention_geometry("window_attention_qkv", B, res, ws, shift, heads, err)) return 1;
     const int C = heads * 32;
-    if (res % ws != 0) { err = "window_attention_qkv: res % ws != 0"; return 1; }
     if (!window_attention_qkv_supported(ws, C, x2w)) { err = "window_attention_qkv: window size / width not instantiated"; return 1; }
     if ((out_x3 || x2w) && !hf) { err = "window_attention_qkv: the x3 output and the x2w weights belong to the fp16 kernels"; return 1; }
     if (ws == 8 && shift != 0) { err = "window_attention_qkv: shifted 8x8 windows are not instantiated"; return 1; }

@@ -801,13 +801,18 @@ int soccdpt_op_fwd_aux(const soccdpt_fwd_aux_args* args, uint32_t* path_out, voi
     return 0;
 }
 
-int soccdpt_op_vit_attention(const void* dev_qkv, void* dev_out, int precision, int B, int N, int heads, void* stream) {
+int soccdpt_op_vit_attention_out(const void* dev_qkv, void* dev_out, int precision, int out_x3, int B, int N, int heads, void* stream) {
     std::string err;
     if (!dev_qkv || !dev_out) return fail(nullptr, "soccdpt_op_vit_attention: null argument");
     if (precision != SOCCDPT_PREC_BF16 && precision != SOCCDPT_PREC_F32 && precision != SOCCDPT_PREC_F16 && precision != SOCCDPT_PREC_F16X3)
         return fail(nullptr, "soccdpt_op_vit_attention: unknown precision");
-    if (launch_vit_attention(dev_qkv, dev_out, precision, B, N, heads, (hipStream_t)stream, err)) return fail(nullptr, err);
+    if (out_x3 && precision != SOCCDPT_PREC_F16) return fail(nullptr, "soccdpt_op_vit_attention: the x3 output form belongs to the fp16 kernel");
+    if (launch_vit_attention(dev_qkv, dev_out, precision, B, N, heads, (hipStream_t)stream, err, out_x3 ? 1 : 0)) return fail(nullptr, err);
     return 0;
+}
+
+int soccdpt_op_vit_attention(const void* dev_qkv, void* dev_out, int precision, int B, int N, int heads, void* stream) {
+    return soccdpt_op_vit_attention_out(dev_qkv, dev_out, precision, 0, B, N, heads, stream);
 }
 
 int soccdpt_op_window_attention(const void* dev_qkv, const float* dev_cpb_table, const float* dev_scale, void* dev_out,
@@ -815,6 +820,12 @@ int soccdpt_op_window_attention(const void* dev_qkv, const float* dev_cpb_table,
     std::string err;
     if (precision != SOCCDPT_PREC_BF16 && precision != SOCCDPT_PREC_F32 && precision != SOCCDPT_PREC_F16 && precision != SOCCDPT_PREC_F16X3)
         return fail(nullptr, "soccdpt_op_window_attention: unknown precision");
+    if (!dev_qkv || !dev_cpb_table || !dev_scale || !dev_out || !dev_bias_scratch) return fail(nullptr, "soccdpt_op_window_attention: null argument");
+    if (window_attention_geometry("soccdpt_op_window_attention", B, res, ws, shift, heads, err)) return fail(nullptr, err);   // before the bias launch: nothing runs on a refusal
+    if (precision == SOCCDPT_PREC_BF16 || precision == SOCCDPT_PREC_F16) {   // what launch_window_attention has no instantiation for, refused here as well: before the bias launch
+        if (ws != 16 && ws != 8 && ws != 24 && ws != 12) return fail(nullptr, "soccdpt_op_window_attention: window size not instantiated (16, 8, 24, 12 are)");
+        if (ws == 8 && shift != 0) return fail(nullptr, "soccdpt_op_window_attention: shifted 8x8 windows are not instantiated");
+    }
     if (launch_attn_bias(dev_cpb_table, dev_bias_scratch, ws, heads, (hipStream_t)stream, err)) return fail(nullptr, err);
     if (precision == SOCCDPT_PREC_F32 || precision == SOCCDPT_PREC_F16X3) {   // F16X3: f32 qkv in, x3 operand out
         if (launch_window_attention_f32(static_cast<const float*>(dev_qkv), dev_bias_scratch, dev_cpb_table, dev_scale, static_cast<float*>(dev_out), B,
@@ -834,6 +845,8 @@ int soccdpt_op_window_attention_qkv(const void* dev_x, const void* dev_wqkv, con
     if (!dev_x || !dev_wqkv || !dev_qkv_bias || !dev_cpb_table || !dev_scale || !dev_out || !dev_bias_scratch) return fail(nullptr, "soccdpt_op_window_attention_qkv: null argument");
     if (precision != SOCCDPT_PREC_BF16 && precision != SOCCDPT_PREC_F16 && precision != SOCCDPT_PREC_F16X2W)
         return fail(nullptr, "soccdpt_op_window_attention_qkv: precision is SOCCDPT_PREC_BF16, _F16 or _F16X2W (16-bit activations)");
+    if (window_attention_geometry("soccdpt_op_window_attention_qkv", B, res, ws, shift, heads, err)) return fail(nullptr, err);   // before the bias launch
+    if (ws == 8 && shift != 0) return fail(nullptr, "soccdpt_op_window_attention_qkv: shifted 8x8 windows are not instantiated");
     if (!window_attention_qkv_supported(ws, heads * 32, precision == SOCCDPT_PREC_F16X2W)) return fail(nullptr, "soccdpt_op_window_attention_qkv: window size / width not instantiated (16 x 16 and 8 x 8 windows)");
     if (launch_attn_bias(dev_cpb_table, dev_bias_scratch, ws, heads, (hipStream_t)stream, err)) return fail(nullptr, err);
     if (launch_window_attention_qkv(static_cast<const bf16_t*>(dev_x), dev_wqkv, dev_qkv_bias, dev_bias_scratch, dev_scale, static_cast<bf16_t*>(dev_out),

@@ -131,6 +131,10 @@ int launch_vit_attention(const void* qkv, void* out, int prec, int B, int N, int
 // bias_acc: CPB bias pre-arranged in MFMA accumulator order, see attention.hip
 size_t attn_bias_elems(int ws, int heads);
 int launch_attn_bias(const float* table, float* bias_acc, int ws, int heads, hipStream_t st, std::string& err);
+// The geometry every window-attention launcher (and the C entries, before they launch anything) insists on: B, res, ws, heads > 0, res % ws == 0 and
+// shift == 0 or ws / 2 -- the kernels evaluate the shift mask for the half-window shift only, and a shift outside [0, ws) would index outside the image.
+// 0 = fine; otherwise err = "<who>: ..." and 1.
+int window_attention_geometry(const char* who, int B, int res, int ws, int shift, int heads, std::string& err);
 // out_x3 != 0 (fp16 kernels only): `out` is written in the x3 operand format from the f32 accumulators (SOCCDPT_PREC_MIXED: the proj GEMM is an x3 launch)
 int launch_window_attention(const bf16_t* qkv, const float* bias_acc, const float* scale, bf16_t* out, int hf, int B, int res, int ws,
                             int shift, int heads, hipStream_t st, std::string& err, int out_x3 = 0);

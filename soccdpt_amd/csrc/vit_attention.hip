@@ -371,6 +371,7 @@ __global__ __launch_bounds__(256) void vit_attention_f32_kernel(const float* __r
 }  // namespace
 
 int launch_vit_attention(const void* qkv, void* out, int prec, int B, int N, int heads, hipStream_t st, std::string& err, int out_x3) {
+    if (!qkv || !out) { err = "vit_attention: null argument"; return 1; }
     if (B <= 0 || N <= 0 || heads <= 0) { err = "vit_attention: bad geometry"; return 1; }
     if (prec == SOCCDPT_PREC_F32 || prec == SOCCDPT_PREC_F16X3) {   // qkv plain f32 in both; the F16X3 mode wants its output in the x3 operand format
         const int NQB = (N + 127) / 128;

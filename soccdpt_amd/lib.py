@@ -254,6 +254,7 @@ def _prototypes() -> dict:
         "soccdpt_op_gn_finish": (ci, [vp, vp, ci, ci, ci, ci, ci, cf, vp]),
         "soccdpt_op_gn_apply": (ci, [vp, vp, vp, ci, vp, vp, vp, vp, vp, ci, vp, vp, vp, vp, vp, vp, ci, ci, cs, ci, ci, ci, ci, cf, vp]),
         "soccdpt_op_vit_attention": (ci, [vp, vp, ci, ci, ci, ci, vp]),
+        "soccdpt_op_vit_attention_out": (ci, [vp, vp, ci, ci, ci, ci, ci, vp]),
         "soccdpt_op_wgrad_tn": (ci, [vp, ctypes.c_long, vp, ctypes.c_long, cs, ci, ci, ci, ci, ci, vp, cs, vp, vp]),
         "soccdpt_op_train_layer_bwd_scratch_bytes": (cs, [P(TrainLayerBwdArgs)]),
         "soccdpt_op_train_layer_bwd": (ci, [vp, P(TrainLayerBwdArgs), vp, cs, P(ctypes.c_uint32), vp]),
@@ -825,9 +826,12 @@ def op_gn_apply(raw, stats, gamma, beta, hw, w, cpg, part=None, tps=0, raw2=None
           int(w), int(C), int(cpg), float(eps), device=raw.device, guard=False)
 
 
-def op_vit_attention(qkv, out, B, N, heads, precision=PREC_BF16):
-    """Kernel-level entry (tests): softmax(q k^T / 8) v of one ViT block on the current stream."""
-    _call("soccdpt_op_vit_attention", _ptr(qkv), _ptr(out), int(precision), B, N, heads, device=qkv.device, guard=False)
+def op_vit_attention(qkv, out, B, N, heads, precision=PREC_BF16, out_x3=False):
+    """Kernel-level entry (tests): softmax(q k^T / 8) v of one ViT block on the current stream; out_x3 (PREC_F16): `out` as x3 operand pairs."""
+    if out_x3:
+        _call("soccdpt_op_vit_attention_out", _ptr(qkv), _ptr(out), int(precision), 1, B, N, heads, device=qkv.device, guard=False)
+    else:
+        _call("soccdpt_op_vit_attention", _ptr(qkv), _ptr(out), int(precision), B, N, heads, device=qkv.device, guard=False)
 
 
 def op_input_transform_u8(frames: torch.Tensor, Hd: int, Wd: int, mean=(0.5, 0.5, 0.5), std=(0.5, 0.5, 0.5)) -> torch.Tensor:

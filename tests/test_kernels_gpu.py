@@ -456,8 +456,10 @@ def test_window_attention_f16(gpu_device, B, res, ws, shift, heads):
 @pytest.mark.parametrize("B,res,ws,shift,heads", [(2, 64, 16, 8, 3), (2, 8, 8, 0, 24), (1, 96, 24, 12, 4), (2, 48, 24, 12, 8), (2, 24, 24, 0, 16), (3, 12, 12, 0, 32),
                                                    (1, 32, 8, 4, 3)])
 def test_window_attention_f32(gpu_device, B, res, ws, shift, heads, precision):
-    """Exact-f32 cosine window attention (MFMA f32): the 16 x 16 / 8 x 8 kernel, the streaming kernel of the 24 x 24 / 12 x 12 windows (ragged last
-    key tile at 144 tokens, shifted and unshifted) and the generic fallback (shifted 8 x 8), f32 output and the x3 operand output of F16X3."""
+    """Exact-f32 cosine window attention (MFMA f32), f32 output and the x3 operand output of F16X3.  Every case here -- 16 x 16, 8 x 8 shifted and unshifted,
+    24 x 24, 12 x 12 (ragged last key tile at 144 tokens) -- runs window_attention_f32_flash_kernel: launch_window_attention_f32 sends these four window sizes
+    to the streaming kernel unless SOCCDPT_ATTN_F32_FLASH16=0 or SOCCDPT_ATTN_F32_ANY is set.  window_attention_f32_kernel<16> / <8> and
+    window_attention_f32_any_kernel are reached by tests/test_attention_fwd_gpu.py (a child process with the switch, and 6 x 6 / 10 x 10 windows)."""
     from soccdpt_amd.lib import PREC_F16X3, PREC_F32, op_window_attention, x3_decode
     g = torch.Generator().manual_seed(res * 100 + shift + heads)
     C = heads * 32
