@@ -52,6 +52,8 @@ extern "C" {
 #define SOCCDPT_BACKBONE_SWIN2B24_384 1 /* dpt_swin2_base_384 */
 #define SOCCDPT_BACKBONE_VITB_RN50_384 2 /* dpt_hybrid_384: ResNetV2-50 stem + ViT-B/16 (model/loader.py:115-120, backbones/vit.py:147-258) */
 #define SOCCDPT_BACKBONE_SWIN2L24_384 3 /* dpt_swin2_large_384 (model/loader.py:58-63): forward only, soccdpt_train_* refuses it */
+/* 4 is reserved for vitl16_384 (dpt_large_384: DESIGN.md section 14) */
+#define SOCCDPT_BACKBONE_SWINL12_384 5 /* dpt_swin_large_384: Swin-V1-L, timm swin_large_patch4_window12_384 (model/loader.py:79-84): forward only, soccdpt_train_* refuses it */
 
 /* dtype codes for soccdpt_bind_weight */
 #define SOCCDPT_DTYPE_F32 0

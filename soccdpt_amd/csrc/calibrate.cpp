@@ -133,7 +133,7 @@ int calib_weights_are_the_shipped_draw(Handle& h, unsigned long long* tmp, hipSt
         case SOCCDPT_BACKBONE_SWIN2T16_256: want = 0x1a63bad6fc751bull; break;
         case SOCCDPT_BACKBONE_SWIN2B24_384: want = 0x1c0e44312bb69eull; break;
         case SOCCDPT_BACKBONE_VITB_RN50_384: want = 0x77b3b69d1638caull; break;
-        default: return 0;   // SOCCDPT_BACKBONE_SWIN2L24_384: no shipped map, so no weights are its draw
+        default: return 0;   // SOCCDPT_BACKBONE_SWIN2L24_384, _SWINL12_384: no shipped map, so no weights are its draw
     }
     unsigned long long got = 0;
     const int rc = calib_fingerprint(h, tmp, st, &got, err);

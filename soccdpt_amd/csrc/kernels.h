@@ -170,6 +170,20 @@ int launch_window_attention_qkv(const bf16_t* x, const void* wqkv, const float* 
 int launch_window_attention_f32(const float* qkv, const float* bias_acc, const float* table, const float* scale, float* out, int B, int res,
                                 int ws, int shift, int heads, hipStream_t st, std::string& err, int x3 = 0);
 
+// swin1.hip: what the Swin-V1 block (dpt_swin_large_384) needs beside the launchers above.  Operand format codes fmt: 0 bf16, 1 fp16, 2 f32, 3 x3.
+// Scaled dot-product window attention, S = (q 32^-0.5) k^T + bias, 12 x 12 windows only (any other size is refused before anything is launched); bias_acc is
+// launch_attn_bias' arrangement of the relative-position-bias table [(2 ws - 1)^2][heads]; argument checks as launch_window_attention / _f32.
+int launch_window_attention_sdp(const bf16_t* qkv, const float* bias_acc, bf16_t* out, int hf, int B, int res, int ws, int shift, int heads, hipStream_t st,
+                                std::string& err, int out_x3 = 0);
+int launch_window_attention_sdp_f32(const float* qkv, const float* bias_acc, float* out, int B, int res, int ws, int shift, int heads, hipStream_t st,
+                                    std::string& err, int x3 = 0);
+// pre-norm rows: out[row] = LN(xf[row]) g + beta in format fmt; xf [rows][C] f32 is read only.  C = 192 / 384 / 768 / 1536
+bool ln_prenorm_supported(int C);
+int launch_ln_prenorm(const float* xf, const float* g, const float* beta, void* out, int fmt, int rows, int C, float eps, hipStream_t st, std::string& err);
+// PatchMerging of Swin-V1 up to the reduction: xf [B][R][R][C] f32 -> out [B (R/2)^2][4C] = LN over 4C of cat(x[0::2,0::2], x[1::2,0::2], x[0::2,1::2], x[1::2,1::2]);
+// R even, C = 192 / 384 / 768
+int launch_merge_ln(const float* xf, const float* g, const float* beta, void* out, int fmt, int B, int R, int C, float eps, hipStream_t st, std::string& err);
+
 // fwd_aux.cpp: one of the launchers above on caller-supplied tensors (soccdpt_op_fwd_aux, include/soccdpt_hip.h: tests)
 int fwd_aux(const soccdpt_fwd_aux_args& a, unsigned* path, hipStream_t st, std::string& err);
 

@@ -203,6 +203,13 @@ int lay_out(Handle& h, Arena& ar, Prepared& P, hipStream_t st, std::string& err)
             bw.proj_w = cvt(b.proj.w, (size_t)C * C, GF(gblk(s, j, "proj")));
             bw.fc1_w = cvt(b.fc1.w, (size_t)4 * C * C, GF(gblk(s, j, "fc1")));
             bw.fc2_w = cvt(b.fc2.w, (size_t)4 * C * C, GF(gblk(s, j, "fc2")));
+            if (a.swin1) {   // Swin-V1: the qkv bias is read as bound, the logits' scale is a constant; only the bias table is re-arranged
+                bw.bias_acc = ar.take<float>(attn_bias_elems(ws, H));
+                if (!bw.qkv_w || !bw.proj_w || !bw.fc1_w || !bw.fc2_w) return 1;
+                if (run && launch_attn_bias(W(b.rpb_table), bw.bias_acc, ws, H, st, err)) return 1;
+                P.blocks[s].push_back(bw);
+                continue;
+            }
             bw.qkv_bias = ar.take<float>(3 * C);
             bw.scale = ar.take<float>(H);
             bw.table = ar.take<float>((size_t)(2 * ws - 1) * (2 * ws - 1) * H);
@@ -305,7 +312,8 @@ void carve(const Handle& h, int B, Arena& ar, Workspace& w) {
     } else {
         w.xf = ar.take<float>(M0 * C0);
         w.y = ar.take<float>(M0 * C0);
-        w.xb = F32 ? static_cast<void*>(w.xf) : op(M0 * C0);
+        // Swin-V1 is pre-norm: the operand is LN(xf), never xf itself, so it has a buffer of its own in the exact-f32 mode too
+        w.xb = (F32 && !a.swin1) ? static_cast<void*>(w.xf) : op(M0 * C0);
         w.qkv = op(M0 * 3 * C0);
         w.attn = op(M0 * C0);
         w.hbuf = op(M0 * 4 * C0);
@@ -348,6 +356,7 @@ int model_init(Handle& h, std::string& err) {
         case SOCCDPT_BACKBONE_SWIN2B24_384: h.arch = arch_swin2b24_384(); break;
         case SOCCDPT_BACKBONE_VITB_RN50_384: h.arch = arch_vitb_rn50_384(); break;
         case SOCCDPT_BACKBONE_SWIN2L24_384: h.arch = arch_swin2l24_384(); break;
+        case SOCCDPT_BACKBONE_SWINL12_384: h.arch = arch_swinl12_384(); break;
         default: err = "soccdpt_create: backbone not implemented on the HIP path"; return 1;
     }
     h.img = h.arch.img;
@@ -461,6 +470,9 @@ void model_prec_default(Handle& h) {
         case SOCCDPT_BACKBONE_SWIN2L24_384:
             // dpt_swin2_large_384: no shipped map (none has been derived for this model).  The empty map is never run as it stands: no weights are "the
             // shipped draw" for this backbone (calibrate.cpp), so soccdpt_prepare switches every group to x3 until soccdpt_prec_calibrate has run.
+            break;
+        case SOCCDPT_BACKBONE_SWINL12_384:
+            // dpt_swin_large_384: no shipped map either; as above, every group runs x3 until soccdpt_prec_calibrate has run
             break;
         default:
             // dpt_swin2_tiny_256: budget 0.0005, worst of the seven quantities 4.24e-04 (fp16 everywhere: 9.85e-04); 22 groups x3, 21 x2w of 66; 181 forwards
@@ -748,11 +760,58 @@ static int run_chunk(Handle& h, const Workspace& w, const float* x, int B, float
     // Every launch-site group carries its own operand format (uniform modes: the same one everywhere).  A producer writes each operand
     // copy in the format of the group that READS it: fa / fm = this block's attention / MLP group, fnext = the group that reads the
     // block's output (the next block's attention, or the PatchMerging reduction), fhook = the decoder's layer_rn conv of this stage.
-    { const int f0 = GF(gblk(0, 0, "qkv"));
+    { const int f0 = a.swin1 ? 2 : GF(gblk(0, 0, "qkv"));   // Swin-V1: block 0 reads LN1 of the stream, not the stream: no operand copy
       PROF("patch_embed_ln", 0.0, (double)B * a.img * a.img * 12.0 + (double)B * a.grid() * a.grid() * a.embed * 6.0);
     RUN(launch_patch_embed(x, P.patch_wT, W(MP.swin.patch.b), W(MP.swin.patch_norm.g),
                            W(MP.swin.patch_norm.b), w.xf, f0 == 2 ? nullptr : static_cast<bf16_t*>(w.xb), f0 == 2 ? 0 : f0, B, a.img, a.embed, st, err)); }
-    for (int s = 0; s < 4; ++s) {
+    for (int s = 0; s < 4 && a.swin1; ++s) {
+        // ---- Swin-V1 stage (timm 0.6.12 SwinTransformerBlock / PatchMerging): pre-norm, so every GEMM operand is LN(xf) written by its own launch and the
+        // residual adds ride in the proj / fc2 epilogues (res1 = out_f32 = xf, in place).  Group names and formats as below.
+        const int C = a.dim(s), res = a.res(s), M = B * res * res, wsz = a.ws(s), H = a.heads[s];
+        const int fhook = GF(gname("lrn", s));
+        auto prenorm = [&](const GB& n, int fmt) {
+            PROF("ln_prenorm", 0.0, (double)M * C * (4.0 + (fmt >= 2 ? 4 : 2)));
+            return launch_ln_prenorm(w.xf, W(n.g), W(n.b), w.xb, fmt, M, C, 1e-5f, st, err);
+        };
+        for (int j = 0; j < a.depths[s]; ++j) {
+            const BlockW& bw = P.blocks[s][j];
+            const SwinBlockP& bp = MP.swin.blk[s][j];
+            const int fa = GF(gblk(s, j, "qkv")), fp = GF(gblk(s, j, "proj")), fm = GF(gblk(s, j, "fc1")), f2 = GF(gblk(s, j, "fc2"));
+            RUN(prenorm(bp.n1, fa));
+            IgemmDesc d;
+            d.X = w.xb; d.Wt = bw.qkv_w; d.M = M; d.N = 3 * C; d.Cin = C; d.ldx = C; d.bias = W(bp.qkv_b);
+            if (MIX) { d.out_op = w.qkv; d.out_fmt = 1; }   // mixed mode: fp16 q, k, v for the fp16 attention kernel whatever the GEMM ran in
+            else to_plain(d, w.qkv, fa);
+            RUN(gemm(d, fa));
+            { PROF("window_attention_sdp", 4.0 * M * (double)(wsz * wsz) * C, (double)M * C * 8.0);
+              if (!MIX && fa >= 2) RUN(launch_window_attention_sdp_f32(static_cast<const float*>(w.qkv), bw.bias_acc, static_cast<float*>(w.attn), B, res, wsz, a.shift(s, j), H,
+                                                                       st, err, fa == 3 ? 1 : 0));
+              else RUN(launch_window_attention_sdp(static_cast<const bf16_t*>(w.qkv), bw.bias_acc, static_cast<bf16_t*>(w.attn), MIX ? 1 : fa, B, res, wsz, a.shift(s, j), H,
+                                                   st, err, (MIX && fp == 3) ? 1 : 0)); }
+            d = IgemmDesc();
+            d.X = w.attn; d.Wt = bw.proj_w; d.M = M; d.N = C; d.Cin = C; d.ldx = C; d.bias = W(bp.proj.b); d.res1 = w.xf; d.out_f32 = w.xf;   // x += attn (in place)
+            RUN(gemm(d, fp));
+            RUN(prenorm(bp.n2, fm));
+            d = IgemmDesc();
+            d.X = w.xb; d.Wt = bw.fc1_w; d.M = M; d.N = 4 * C; d.Cin = C; d.ldx = C; d.bias = W(bp.fc1.b); d.act = ACT_GELU; d.out_op = w.hbuf; d.out_fmt = MIX ? f2 : -1;
+            RUN(gemm(d, fm));
+            d = IgemmDesc();
+            d.X = w.hbuf; d.Wt = bw.fc2_w; d.M = M; d.N = C; d.Cin = 4 * C; d.ldx = 4 * C; d.bias = W(bp.fc2.b); d.res1 = w.xf; d.out_f32 = w.xf;   // x += mlp (in place)
+            if (j == a.hooks[s]) {   // the hooked block (the stage's last): the same launch writes the zero-halo feature image for its lrn<s> reader
+                d.out_op = w.feat[s]; d.out_halo = 1; d.H = res; d.W = res; d.out_fmt = MIX ? fhook : -1;
+            }
+            RUN(gemm(d, f2));
+        }
+        if (s < 3) {   // PatchMerging: gather + LayerNorm(4C) in one launch, then the reduction (no bias) into the new stream
+            const int fg = GF(gname("merge", s));
+            { PROF("merge_ln", 0.0, (double)M * C * (4.0 + (fg >= 2 ? 4 : 2)));
+              RUN(launch_merge_ln(w.xf, W(MP.swin.merge[s].norm.g), W(MP.swin.merge[s].norm.b), w.xb, fg, B, res, C, 1e-5f, st, err)); }
+            IgemmDesc d;
+            d.X = w.xb; d.Wt = P.merge_w[s]; d.M = M / 4; d.N = 2 * C; d.Cin = 4 * C; d.ldx = 4 * C; d.out_f32 = w.xf;
+            RUN(gemm(d, fg));
+        }
+    }
+    for (int s = 0; s < 4 && !a.swin1; ++s) {
         const int C = a.dim(s), res = a.res(s), M = B * res * res, wsz = a.ws(s), H = a.heads[s];
         bool merged = false;   // the stage's last block wrote its operand copy straight into the PatchMerging layout (w.hbuf)
         const int fhook = GF(gname("lrn", s));

@@ -20,6 +20,9 @@ struct Arch {
     int hooks[4] = {1, 1, 5, 1};
     // ViT-hybrid (vitb_rn50_384; /root/reference/SOccDPT/model/backbones/vit.py:147-258, model/blocks.py:103-112): ResNetV2 (3, 4, 9) stem +
     // 12 ViT-B blocks; the reassembled pyramid is [256, 512, 768, 768] channels at 1/4, 1/8, 1/16, 1/32 of the input
+    // Swin-V1 block (swinl12_384, timm swin_large_patch4_window12_384; hooks /root/reference/SOccDPT/model/dpt.py:73-78): pre-norm, scaled dot-product
+    // attention with a learned relative-position-bias table and a full qkv bias, PatchMerging = gather, LayerNorm(4C), reduction.  pretrained_window is unused.
+    bool swin1 = false;
     bool hybrid = false;
     int vit_depth = 12, vit_heads = 12, vit_dim = 768, stem_ch = 64;
     int rn_layers[3] = {3, 4, 9};
@@ -50,6 +53,13 @@ inline Arch arch_swin2l24_384() {
     for (int i = 0; i < 4; ++i) a.heads[i] = hd[i];
     return a;
 }
+// swin_large_patch4_window12_384: Swin-V2-L's widths, depths, heads and hooks with 12 x 12 windows at every stage (stage 3: res == window, unshifted)
+inline Arch arch_swinl12_384() {
+    Arch a = arch_swin2l24_384();
+    a.swin1 = true; a.window = 12;
+    for (int i = 0; i < 4; ++i) a.pretrained_window[i] = 0;
+    return a;
+}
 inline Arch arch_vitb_rn50_384() {
     Arch a;
     a.hybrid = true; a.img = 384; a.patch = 16;
@@ -76,15 +86,16 @@ inline Span span_of(PRef r) { return r.i < 0 ? Span{} : Span{r.i, r.i + 1}; }
 
 struct WB { PRef w, b; };   // <module>.weight, <module>.bias
 struct GB { PRef g, b; };   // the same pair of a normalisation layer: gamma, beta
-struct SwinBlockP {          // timm SwinTransformerV2Block
+struct SwinBlockP {          // timm SwinTransformerV2Block; Swin-V1 (Arch::swin1): rpb_table, qkv_w, qkv_b instead of the first six
     PRef logit_scale, q_bias, v_bias, cpb0_w, cpb0_b, cpb2_w, qkv_w;
+    PRef rpb_table, qkv_b;   // attn.relative_position_bias_table [(2 ws - 1)^2][H], attn.qkv.bias [3C]
     WB proj;
     GB n1;
     WB fc1, fc2;
     GB n2;
     Span upto;               // everything of the encoder at or before this block in forward order
 };
-struct MergeP { PRef red_w; GB norm; };   // PatchMerging of Swin-V2: reduction, then norm
+struct MergeP { PRef red_w; GB norm; };   // PatchMerging of Swin-V2: reduction, then norm [2C]; of Swin-V1: norm [4C], then reduction
 struct RnBlockP {            // ResNetV2 bottleneck (weight-standardised convolutions + GroupNorm) and its geometry
     int cin = 0, cout = 0, mid = 0, stride = 1, rin = 0, rout = 0;
     bool proj = false;       // the first block of a stage: shortcut projection ds_w / ds_n
@@ -203,6 +214,20 @@ inline ModelP build_params(const Arch& a, int features, int num_classes, std::ve
             for (int j = 0; j < a.depths[s]; ++j) {
                 const std::string b = ENC + "layers." + n(s) + ".blocks." + n(j) + ".";
                 SwinBlockP p;
+                if (a.swin1) {   // timm 0.6.12 SwinTransformerBlock; the buffers (attn.relative_position_index, attn_mask) are never consumed
+                    const int64_t T = (int64_t)(2 * a.ws(s) - 1) * (2 * a.ws(s) - 1);
+                    p.n1 = gb(b + "norm1", C);
+                    p.rpb_table = add(b + "attn.relative_position_bias_table", {T, H});
+                    p.qkv_w = add(b + "attn.qkv.weight", {3 * C, C});
+                    p.qkv_b = add(b + "attn.qkv.bias", {3 * C});
+                    p.proj = wb(b + "attn.proj", {C, C}, C);
+                    p.n2 = gb(b + "norm2", C);
+                    p.fc1 = wb(b + "mlp.fc1", {4 * C, C}, 4 * C);
+                    p.fc2 = wb(b + "mlp.fc2", {C, 4 * C}, C);
+                    p.upto = Span{P.encoder.lo, here()};
+                    S.blk[s].push_back(p);
+                    continue;
+                }
                 p.logit_scale = add(b + "attn.logit_scale", {H, 1, 1});
                 p.q_bias = add(b + "attn.q_bias", {C});
                 p.v_bias = add(b + "attn.v_bias", {C});
@@ -221,7 +246,7 @@ inline ModelP build_params(const Arch& a, int features, int num_classes, std::ve
             if (s < 3) {
                 const std::string d = ENC + "layers." + n(s) + ".downsample.";
                 S.merge[s].red_w = add(d + "reduction.weight", {2 * C, 4 * C});
-                S.merge[s].norm = gb(d + "norm", 2 * C);
+                S.merge[s].norm = gb(d + "norm", a.swin1 ? 4 * C : 2 * C);
             }
         }
     }

@@ -487,6 +487,7 @@ int check_train(Handle& h, int B, const void* ws, size_t ws_bytes, std::string& 
     if (h.cfg.precision != SOCCDPT_PREC_F32) { err = "soccdpt_train_*: the training step is built for SOCCDPT_PREC_F32 handles only"; return 1; }
     if (h.arch.hybrid && h.arch.grid() != 24) { err = "soccdpt_train_*: the ViT-hybrid encoder trains at 384 x 384 (position embedding used as stored)"; return 1; }
     if (h.cfg.features != 256 || h.cfg.num_classes != 3) { err = "soccdpt_train_*: features must be 256 and num_classes 3"; return 1; }
+    if (h.cfg.backbone == SOCCDPT_BACKBONE_SWINL12_384) { err = "soccdpt_train_*: no training step is built for dpt_swin_large_384 (Swin-V1-L): it is forward-only"; return 1; }
     if (!train_backbone_ok(h)) { err = "soccdpt_train_*: the training step is built for dpt_swin2_tiny_256, dpt_swin2_base_384 and dpt_hybrid_384; dpt_swin2_large_384 is forward-only"; return 1; }
     if (B < 1 || !ws) { err = "soccdpt_train_*: bad arguments"; return 1; }
     for (const auto& w : h.weights)

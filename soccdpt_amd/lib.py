@@ -16,7 +16,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SOCCDPT_LIB_PATH") or os.path.join(_HERE, "libsoccdpt_hip.so")   # override: A/B of two builds in one GPU call (tools/ab_bench.sh)
 
 ABI_VERSION = 11
-BACKBONE_IDS = {"swin2t16_256": 0, "swin2b24_384": 1, "vitb_rn50_384": 2, "swin2l24_384": 3}
+BACKBONE_IDS = {"swin2t16_256": 0, "swin2b24_384": 1, "vitb_rn50_384": 2, "swin2l24_384": 3, "swinl12_384": 5}   # 4 is reserved for vitl16_384
 PREC_BF16 = 0
 PREC_F32 = 1
 PREC_F16 = 2
@@ -155,7 +155,7 @@ _lib = None
 # nothing inside soccdpt_forward, so editing them does not invalidate PMC counters collected for the forward's kernels.
 FORWARD_SOURCES = ("Makefile", "attention.hip", "attention_body.h", "attention_qkv.hip", "conv8p.hip", "depth_tail.hip", "elementwise.hip", "gelu.h", "half16.h", "hybrid.hip", "igemm.h",
                    "igemm.hip", "igemm_kernel.h", "kernels.h", "launch.h", "ln_body.h", "mlp_fused.hip", "model.cpp", "projection.hip", "resample.h",
-                   "vit_attention.hip", "wino.hip")
+                   "swin1.hip", "vit_attention.hip", "wino.hip")
 
 
 def csrc_sha() -> str:
@@ -327,6 +327,20 @@ def _pack_prototypes() -> dict:
 
 
 PACK_PROTOTYPES = _pack_prototypes()
+
+
+def _swin1_prototypes() -> dict:
+    """The same table for include/soccdpt_swin1.h (the Swin-V1 block's kernels on caller-supplied tensors, csrc/swin1.hip), in that header's order;
+    tests/test_swin1_large_cpu.py holds it against the header.  A fifth header and a fifth table: soccdpt_hip.h and its ABI version do not change."""
+    vp, ci, cf = ctypes.c_void_p, ctypes.c_int, ctypes.c_float
+    return {
+        "soccdpt_swin1_window_attention": (ci, [vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, vp]),
+        "soccdpt_swin1_ln_rows": (ci, [vp, vp, vp, vp, ci, ci, ci, cf, vp]),
+        "soccdpt_swin1_merge_ln": (ci, [vp, vp, vp, vp, ci, ci, ci, ci, cf, vp]),
+    }
+
+
+SWIN1_PROTOTYPES = _swin1_prototypes()
 PACK_INDEX_BITS = (1, 2, 4, 8)   # k of include/soccdpt_pack.h
 
 
@@ -340,7 +354,7 @@ def load_library() -> ctypes.CDLL:
             f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "(make -C soccdpt_amd/csrc).  The SOccDPT MI355X path has no CPU fallback.")
     L = ctypes.CDLL(LIB_PATH)
-    for table in (PROTOTYPES, VIS_PROTOTYPES, DATA_PROTOTYPES, PACK_PROTOTYPES):
+    for table in (PROTOTYPES, VIS_PROTOTYPES, DATA_PROTOTYPES, PACK_PROTOTYPES, SWIN1_PROTOTYPES):
         for symbol, (restype, argtypes) in table.items():
             fn = getattr(L, symbol)
             fn.restype, fn.argtypes = restype, argtypes
@@ -1010,3 +1024,21 @@ def op_wino_conv(x_halo, u, B, H, W, C, N, bias=None, res1=None, res2=None, res2
     _call("soccdpt_op_wino_conv", _ptr(x_halo), _ptr(u), B, H, W, C, N, _ptr(bias), _ptr(res1), _ptr(res2), int(res2_hw[0]), int(res2_hw[1]), 1 if relu else 0,
           1 if act_on_f32 else 0, _ptr(out_f32), _ptr(out_op), 1 if out_halo else 0, 1 if out_x3 else 0, int(precision), _ptr(stamps),
           device=x_halo.device, guard=False)
+
+
+def op_swin1_window_attention(qkv, table, out, B, res, ws, shift, heads, precision=PREC_BF16, out_x3=False):
+    """soccdpt_swin1_window_attention (include/soccdpt_swin1.h): Swin-V1 scaled dot-product window attention, table = relative_position_bias_table."""
+    nt = (ws * ws + 31) // 32 if ws > 0 else 1
+    scratch = torch.empty((max(heads, 1) * nt * nt * 1024,), dtype=torch.float32, device=out.device)
+    _call("soccdpt_swin1_window_attention", _ptr(qkv), _ptr(table), _ptr(out), _ptr(scratch), B, res, ws, shift, heads, int(precision), 1 if out_x3 else 0,
+          device=out.device, guard=False)
+
+
+def op_swin1_ln_rows(xf, g, beta, out, rows, C, precision=PREC_BF16, eps=1e-5):
+    """soccdpt_swin1_ln_rows: out = LayerNorm(xf) g + beta per row in the operand format `precision`; xf is read only."""
+    _call("soccdpt_swin1_ln_rows", _ptr(xf), _ptr(g), _ptr(beta), _ptr(out), int(precision), rows, C, float(eps), device=out.device, guard=False)
+
+
+def op_swin1_merge_ln(xf, g, beta, out, B, R, C, precision=PREC_BF16, eps=1e-5):
+    """soccdpt_swin1_merge_ln: Swin-V1 PatchMerging up to its reduction, [B][R][R][C] f32 -> [B (R/2)^2][4C] in the operand format `precision`."""
+    _call("soccdpt_swin1_merge_ln", _ptr(xf), _ptr(g), _ptr(beta), _ptr(out), int(precision), B, R, C, float(eps), device=out.device, guard=False)

@@ -22,7 +22,7 @@ from .base_model import BaseModel
 from .blocks import Interpolate
 from .dpt import DPTDepthModel
 from .scaled_tanh import ScaledTanh
-from .spec import DEFAULT_DEPTH_WEIGHTS, HYBRID_ARCHS, MODEL_TYPE_TO_BACKBONE, SWIN_ARCHS, VIT_ARCHS, backbone_image_size, model_types  # noqa: F401
+from .spec import DEFAULT_DEPTH_WEIGHTS, HYBRID_ARCHS, MODEL_TYPE_TO_BACKBONE, SWIN1_ARCHS, SWIN_ARCHS, VIT_ARCHS, backbone_image_size, model_types  # noqa: F401
 
 # /root/reference/SOccDPT/datasets/bdd_helper.py:53-56
 DATASET_BASE = "~/Datasets/Depth_Dataset_Bengaluru"
@@ -108,7 +108,7 @@ class SOccDPT(BaseModel):
 
     # -- engine plumbing --
     def _engine_backbone(self) -> str:
-        return self.backbone if (self.backbone in SWIN_ARCHS or self.backbone in HYBRID_ARCHS or self.backbone in VIT_ARCHS) else "swin2t16_256"
+        return self.backbone if (self.backbone in SWIN_ARCHS or self.backbone in SWIN1_ARCHS or self.backbone in HYBRID_ARCHS or self.backbone in VIT_ARCHS) else "swin2t16_256"
 
     def _sigmoid_flag(self) -> bool:
         return True
@@ -502,6 +502,10 @@ class SOccDPT_V3(SOccDPT):
 
     def network(self, x: torch.Tensor):
         """Stage-level: encoder + decoder + heads only -> (inv_depth [B,S,S], segmentation [B,C,S,S])."""
+        # soccdpt_network reads and writes at the handle's image size whatever the tensor's: checked before the engine exists, so on a CPU tensor too
+        img = backbone_image_size(self._engine_backbone())
+        assert x.dim() == 4 and x.shape[1] == 3 and x.shape[2] == img and x.shape[3] == img, \
+            f"expected x [B,3,{img},{img}], got {tuple(x.shape)}"
         eng = self._engine(x.device)
         self._sync_weights(eng)
         B, S = x.shape[0], x.shape[2]

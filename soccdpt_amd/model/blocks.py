@@ -5,6 +5,7 @@ convolutions with fused ReLU / bias / residual epilogues, bilinear resize) runs 
 import torch.nn as nn
 
 from .backbones.swin2 import _make_pretrained_swin2b24_384, _make_pretrained_swin2l24_384, _make_pretrained_swin2t16_256
+from .backbones.swin import _make_pretrained_swinl12_384
 from .backbones.vit import _make_pretrained_vitb_rn50_384, _make_pretrained_vitl16_384
 from .spec import arch_of
 
@@ -22,6 +23,8 @@ def _make_encoder(backbone, features, use_pretrained, groups=1, expand=False, ex
         pretrained = _make_pretrained_swin2b24_384(use_pretrained, hooks=hooks)
     elif backbone == "swin2l24_384":
         pretrained = _make_pretrained_swin2l24_384(use_pretrained, hooks=hooks)
+    elif backbone == "swinl12_384":
+        pretrained = _make_pretrained_swinl12_384(use_pretrained, hooks=hooks)   # scratch [192, 384, 768, 1536] (model/blocks.py:79-83)
     elif backbone == "vitb_rn50_384":
         pretrained = _make_pretrained_vitb_rn50_384(use_pretrained, hooks=hooks, use_vit_only=use_vit_only, use_readout=use_readout)
     elif backbone == "vitl16_384":

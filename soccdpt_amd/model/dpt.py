@@ -3,7 +3,7 @@ import torch.nn as nn
 
 from .base_model import BaseModel
 from .blocks import FeatureFusionBlock_custom, Interpolate, _make_encoder
-from .spec import HYBRID_ARCHS, SWIN_ARCHS, VIT_ARCHS, arch_of
+from .spec import HYBRID_ARCHS, SWIN1_ARCHS, SWIN_ARCHS, VIT_ARCHS, arch_of
 
 
 def _make_fusion_block(features, use_bn, size=None):
@@ -15,7 +15,7 @@ class DPT(BaseModel):
     def __init__(self, head, features=256, backbone="swin2t16_256", readout="project", channels_last=False,
                  use_bn=False, return_features=False, **kwargs):
         super().__init__()
-        assert backbone in SWIN_ARCHS or backbone in HYBRID_ARCHS or backbone in VIT_ARCHS, f"Backbone '{backbone}' not implemented on the MI355X path"
+        assert backbone in SWIN_ARCHS or backbone in SWIN1_ARCHS or backbone in HYBRID_ARCHS or backbone in VIT_ARCHS, f"Backbone '{backbone}' not implemented on the MI355X path"
         assert features == 256 and not use_bn
         self.channels_last = channels_last
         self.return_features = return_features

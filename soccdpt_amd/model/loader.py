@@ -6,7 +6,7 @@ import numpy as np
 import torch
 
 from .base_model import BaseModel
-from .spec import HYBRID_ARCHS, MODEL_TYPE_TO_BACKBONE, SWIN_ARCHS
+from .spec import HYBRID_ARCHS, MODEL_TYPE_TO_BACKBONE, SWIN1_ARCHS, SWIN_ARCHS
 from .transforms import InputTransform
 
 
@@ -45,7 +45,7 @@ def load_transforms(model_type: str = "dpt_large_384", height: int = 0, square: 
     backbone = MODEL_TYPE_TO_BACKBONE[model_type]
     size = SWIN_ARCHS[backbone].img if backbone in SWIN_ARCHS else (HYBRID_ARCHS[backbone].img if backbone in HYBRID_ARCHS else 384)
     net_w = net_h = size
-    keep_aspect_ratio = False if backbone in SWIN_ARCHS else (not square)
+    keep_aspect_ratio = False if (backbone in SWIN_ARCHS or backbone in SWIN1_ARCHS) else (not square)   # dpt_swin_large_384: loader.py:205-212
     if height != 0:
         net_w = net_h = height
     return InputTransform(net_w, net_h, keep_aspect_ratio=keep_aspect_ratio, ensure_multiple_of=32, resize_method="minimal"), net_w, net_h

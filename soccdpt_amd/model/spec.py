@@ -53,6 +53,42 @@ SWIN_ARCHS: Dict[str, SwinV2Arch] = {
                                (2, 2, 18, 2), (6, 12, 24, 48), 24, (12, 12, 12, 6), (1, 1, 17, 1)),
 }
 
+@dataclass(frozen=True)
+class SwinV1Arch:
+    """timm 0.6.12 swin_large_patch4_window12_384 as the reference creates it (/root/reference/SOccDPT/model/backbones/swin.py, hooks model/dpt.py:73-78):
+    pre-norm blocks, scaled dot-product window attention with a relative-position-bias table, PatchMerging = gather, LayerNorm(4C), reduction."""
+    name: str
+    timm_name: str
+    img: int
+    patch: int
+    embed: int
+    depths: Tuple[int, ...]
+    heads: Tuple[int, ...]
+    window: int
+    hooks: Tuple[int, ...]
+
+    @property
+    def grid(self) -> int:
+        return self.img // self.patch
+
+    def dims(self) -> List[int]:
+        return [self.embed << i for i in range(len(self.depths))]
+
+    def stage_res(self, s: int) -> int:
+        return self.grid >> s
+
+    def window_shift(self, s: int, j: int) -> Tuple[int, int]:
+        res = self.stage_res(s)
+        ws = min(res, self.window)
+        shift = 0 if (j % 2 == 0 or res <= self.window) else self.window // 2
+        return ws, shift
+
+
+# A table of its own: SWIN_ARCHS is iterated as "Swin-V2, with a training plan"
+SWIN1_ARCHS: Dict[str, SwinV1Arch] = {
+    "swinl12_384": SwinV1Arch("swinl12_384", "swin_large_patch4_window12_384", 384, 4, 192, (2, 2, 18, 2), (6, 12, 24, 48), 12, (1, 1, 17, 1)),
+}
+
 # model_type -> backbone (only the backbones this build implements on the HIP path
 # are constructible; the other ids are kept so the switch reports them by name).
 MODEL_TYPE_TO_BACKBONE: Dict[str, str] = {
@@ -71,14 +107,18 @@ MODEL_TYPE_TO_BACKBONE: Dict[str, str] = {
 
 # Backbones with no training step: swin2l24_384 has a forward path (soccdpt_train_* refuses it with the same sentence: csrc/train_step.cpp check_train);
 # vitl16_384 so far exists in this mirror only (tables, module tree, weights) -- the library does not build it yet
-FORWARD_ONLY_BACKBONES = ("swin2l24_384", "vitl16_384")
+# swinl12_384 (Swin-V1-L) has a forward path too and a refusal sentence of its own
+FORWARD_ONLY_BACKBONES = ("swin2l24_384", "vitl16_384", "swinl12_384")
 TRAIN_REFUSAL = ("the training step is built for dpt_swin2_tiny_256, dpt_swin2_base_384 and dpt_hybrid_384; "
                  "dpt_swin2_large_384 is forward-only")
 TRAIN_REFUSAL_VIT_LARGE = "no training step is built for dpt_large_384 (ViT-L/16)"
+TRAIN_REFUSAL_SWIN1_LARGE = "no training step is built for dpt_swin_large_384 (Swin-V1-L): it is forward-only"   # csrc/train_step.cpp check_train says the same
 
 
 def train_refusal(backbone: str) -> str:
     """The sentence training on a backbone without a training step is refused with."""
+    if backbone == "swinl12_384":
+        return TRAIN_REFUSAL_SWIN1_LARGE
     return TRAIN_REFUSAL_VIT_LARGE if backbone == "vitl16_384" else TRAIN_REFUSAL
 
 
@@ -86,6 +126,8 @@ def backbone_image_size(backbone: str) -> int:
     """Network input size of a backbone this build implements (model/loader.py:141-272 net_w / net_h)."""
     if backbone in SWIN_ARCHS:
         return SWIN_ARCHS[backbone].img
+    if backbone in SWIN1_ARCHS:
+        return SWIN1_ARCHS[backbone].img
     if backbone in HYBRID_ARCHS:
         return HYBRID_ARCHS[backbone].img
     if backbone in VIT_ARCHS:
@@ -259,7 +301,7 @@ VIT_ARCHS: Dict[str, VitArch] = {"vitl16_384": VitArch()}
 
 def arch_of(backbone: str):
     """The architecture row of a backbone this build implements."""
-    for table in (SWIN_ARCHS, HYBRID_ARCHS, VIT_ARCHS):
+    for table in (SWIN_ARCHS, SWIN1_ARCHS, HYBRID_ARCHS, VIT_ARCHS):
         if backbone in table:
             return table[backbone]
     raise AssertionError(f"Backbone '{backbone}' not implemented on the MI355X path")
@@ -311,6 +353,54 @@ def vit_param_shapes(arch: VitArch) -> "OrderedDict[str, Tuple[int, ...]]":
     return p
 
 
+def swin1_state_shapes(arch: SwinV1Arch) -> "OrderedDict[str, Tuple[int, ...]]":
+    """timm-0.6.12 SwinTransformer state-dict names / shapes in state_dict() order, the buffers included (a module's own parameters, then its own
+    buffers, then its children in registration order): attn_mask [nW, N, N] first in a shifted block, relative_position_index [N, N] after the bias table."""
+    p: "OrderedDict[str, Tuple[int, ...]]" = OrderedDict()
+    C0 = arch.embed
+    p["patch_embed.proj.weight"] = (C0, 3, arch.patch, arch.patch)
+    p["patch_embed.proj.bias"] = (C0,)
+    p["patch_embed.norm.weight"] = (C0,)
+    p["patch_embed.norm.bias"] = (C0,)
+    for s, depth in enumerate(arch.depths):
+        C = C0 << s
+        H = arch.heads[s]
+        for j in range(depth):
+            b = f"layers.{s}.blocks.{j}."
+            ws, shift = arch.window_shift(s, j)
+            N = ws * ws
+            if shift:
+                p[b + "attn_mask"] = ((arch.stage_res(s) // ws) ** 2, N, N)
+            p[b + "norm1.weight"] = (C,)
+            p[b + "norm1.bias"] = (C,)
+            p[b + "attn.relative_position_bias_table"] = ((2 * ws - 1) ** 2, H)
+            p[b + "attn.relative_position_index"] = (N, N)
+            p[b + "attn.qkv.weight"] = (3 * C, C)
+            p[b + "attn.qkv.bias"] = (3 * C,)
+            p[b + "attn.proj.weight"] = (C, C)
+            p[b + "attn.proj.bias"] = (C,)
+            p[b + "norm2.weight"] = (C,)
+            p[b + "norm2.bias"] = (C,)
+            p[b + "mlp.fc1.weight"] = (4 * C, C)
+            p[b + "mlp.fc1.bias"] = (4 * C,)
+            p[b + "mlp.fc2.weight"] = (C, 4 * C)
+            p[b + "mlp.fc2.bias"] = (C,)
+        if s < len(arch.depths) - 1:
+            d = f"layers.{s}.downsample."
+            p[d + "reduction.weight"] = (2 * C, 4 * C)
+            p[d + "norm.weight"] = (4 * C,)
+            p[d + "norm.bias"] = (4 * C,)
+    Cl = C0 << (len(arch.depths) - 1)
+    p["norm.weight"] = (Cl,)
+    p["norm.bias"] = (Cl,)
+    p["head.weight"] = (1000, Cl)
+    p["head.bias"] = (1000,)
+    return p
+
+
+SWIN1_BUFFER_LEAVES = ("attn_mask", "relative_position_index")     # derived from the geometry, never consumed by the library
+
+
 def scratch_param_shapes(arch, features: int = 256) -> "OrderedDict[str, Tuple[int, ...]]":
     """depth_net.scratch.* (blocks.py:139-193, dpt.py:133-140,199-219)."""
     p: "OrderedDict[str, Tuple[int, ...]]" = OrderedDict()
@@ -358,6 +448,10 @@ def v3_state_shapes(backbone: str, features: int = 256, num_classes: int = 3) ->
         arch = VIT_ARCHS[backbone]
         for k, v in vit_param_shapes(arch).items():
             out["depth_net.pretrained." + k] = v
+    elif backbone in SWIN1_ARCHS:
+        arch = SWIN1_ARCHS[backbone]
+        for k, v in swin1_state_shapes(arch).items():
+            out["depth_net.pretrained.model." + k] = v
     else:
         arch = SWIN_ARCHS[backbone]
         for k, v in encoder_param_shapes(arch).items():

@@ -90,6 +90,18 @@ def synth_state_dict(backbone: str = "swin2t16_256", features: int = 256, num_cl
         # The filter takes the pixels' scale instead (2^-8: exact), which leaves maps of 0.5 .. 4 like the other models'.
         k = "depth_net.pretrained.model.patch_embed.proj.weight"
         sd[k] = sd[k] * (1.0 / 256.0)
+    if backbone == "swinl12_384":
+        # Swin-V1's buffers are functions of the geometry, not weights: timm's own values (nothing on the library's path reads them)
+        from ..model.backbones.swin import relative_position_index, shift_attn_mask
+        from ..model.spec import SWIN1_ARCHS
+        arch = SWIN1_ARCHS[backbone]
+        for s, depth in enumerate(arch.depths):
+            for j in range(depth):
+                b = f"depth_net.pretrained.model.layers.{s}.blocks.{j}."
+                ws, shift = arch.window_shift(s, j)
+                sd[b + "attn.relative_position_index"] = relative_position_index(ws)
+                if shift:
+                    sd[b + "attn_mask"] = shift_attn_mask(arch.stage_res(s), ws, shift)
     if alias_pretrained:  # the reference registers the encoder twice (model/SOccDPT.py:650)
         for k in list(sd.keys()):
             if k.startswith("depth_net.pretrained."):

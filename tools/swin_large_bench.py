@@ -5,6 +5,10 @@ precision map exists for dpt_swin2_large_384, so its "mixed" row runs every grou
 synthetic frames (4 select, 2 hold out), reports its cost, and times "mixed_calibrated" too.
 
     python tools/swin_large_bench.py [--out profiles/swin2_large_384_forward.json] [--calibrate] [--blocks 5] [--iters 10] [--modes f16,mixed,f16x3,f32]
+
+--model-type dpt_swin_large_384 times the Swin-V1-L model instead, beside dpt_swin2_large_384, with the same protocol (default --out
+profiles/swin_large_384_forward.json), and adds `kernel_shares`: the library's per-family event timing (soccdpt_profile_*) of its fp16 forward at each
+batch size, with the share of the pre-norm LayerNorm and merge-LN launches in the network's kernel time.
 """
 import argparse
 import contextlib
@@ -21,7 +25,9 @@ import torch
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
 
-MODELS = (("dpt_swin2_large_384", "swin2l24_384"), ("dpt_swin2_base_384", "swin2b24_384"))
+# --model-type -> (the model timed, the model it is timed beside)
+MODELS = {"dpt_swin2_large_384": (("dpt_swin2_large_384", "swin2l24_384"), ("dpt_swin2_base_384", "swin2b24_384")),
+          "dpt_swin_large_384": (("dpt_swin_large_384", "swinl12_384"), ("dpt_swin2_large_384", "swin2l24_384"))}
 
 
 def build(model_type, sd, precision, dev, calib):
@@ -46,9 +52,27 @@ def time_forward(m, x, warmup, blocks, iters):
     return {"min_ms": min(ms), "median_ms": statistics.median(ms), "max_ms": max(ms), "blocks": blocks, "iters": iters}
 
 
+def kernel_shares(m, x, iters):
+    """Per-family event times of `iters` network forwards (ms per forward) and the share of the Swin-V1 block's own LayerNorm launches."""
+    eng = m._engine(x.device)
+    m.network(x)
+    torch.cuda.synchronize()
+    eng.profile_enable(True)
+    for _ in range(iters):
+        m.network(x)
+    torch.cuda.synchronize()
+    stats = eng.profile_collect()
+    eng.profile_enable(False)
+    total = sum(v["ms"] for v in stats.values())
+    fam = {k: {"ms_per_forward": v["ms"] / iters, "launches_per_forward": v["launches"] / iters, "share": v["ms"] / total} for k, v in sorted(stats.items(), key=lambda kv: -kv[1]["ms"])}
+    return {"kernel_ms_per_forward": total / iters, "ln_prenorm_share": fam.get("ln_prenorm", {}).get("share"), "merge_ln_share": fam.get("merge_ln", {}).get("share"),
+            "window_attention_sdp_share": fam.get("window_attention_sdp", {}).get("share"), "families": fam}
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join(REPO, "profiles", "swin2_large_384_forward.json"))
+    ap.add_argument("--model-type", choices=sorted(MODELS), default="dpt_swin2_large_384")
+    ap.add_argument("--out", default=None)
     ap.add_argument("--calibrate", action="store_true")
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--blocks", type=int, default=5)
@@ -56,6 +80,9 @@ def main():
     ap.add_argument("--modes", default="f16,mixed,f16x3,f32")
     ap.add_argument("--batches", default="1,8")
     args = ap.parse_args()
+    subject = args.model_type
+    if args.out is None:
+        args.out = os.path.join(REPO, "profiles", "swin2_large_384_forward.json" if subject == "dpt_swin2_large_384" else "swin_large_384_forward.json")
     if not torch.cuda.is_available():
         raise SystemExit("tools/swin_large_bench.py measures on an MI355X: no GPU visible")
     from soccdpt_amd.lib import PREC_F16, PREC_F16X3, PREC_F32, PREC_MIXED
@@ -66,9 +93,9 @@ def main():
     dev = torch.device("cuda:0")
     calib = write_synth_calib(os.path.join(tempfile.mkdtemp(), "calib.yaml"))
     res = {"what": "full forward (network + projection + occupancy), ms per forward: min / median / max over blocks of forwards ending in a device synchronise",
-           "device": torch.cuda.get_device_name(0), "note": "dpt_swin2_large_384 has no shipped precision map: 'mixed' runs every group in x3 until calibrated",
+           "device": torch.cuda.get_device_name(0), "note": f"{subject} has no shipped precision map: 'mixed' runs every group in x3 until calibrated",
            "rows": [], "calibration": None}
-    for model_type, backbone in MODELS:
+    for model_type, backbone in MODELS[subject]:
         sd = synth_state_dict(backbone, alias_pretrained=True)
         xs = {B: synth_input(B, size=384, seed0=40).to(dev) for B in batches}
         for mode in modes:
@@ -78,7 +105,11 @@ def main():
                 row["frames_per_s"] = B * 1e3 / row["median_ms"]
                 res["rows"].append(row)
                 print(json.dumps(row), flush=True)
-            if mode == "mixed" and args.calibrate and model_type == "dpt_swin2_large_384":
+            if mode == "f16" and model_type == subject and subject == "dpt_swin_large_384":
+                res["kernel_shares"] = {f"B{B}": kernel_shares(m, xs[B], args.iters) for B in batches}
+                print(json.dumps({k: {kk: v[kk] for kk in ("kernel_ms_per_forward", "ln_prenorm_share", "merge_ln_share", "window_attention_sdp_share")}
+                                  for k, v in res["kernel_shares"].items()}), flush=True)
+            if mode == "mixed" and args.calibrate and model_type == subject:
                 frames = synth_input(6, size=384, seed0=200).to(dev)
                 torch.cuda.synchronize()
                 t0 = time.perf_counter()
