@@ -44,8 +44,10 @@ extern "C" {
  *   10 (soccdpt_train_aux_args, soccdpt_op_train_aux_scratch_bytes and soccdpt_op_train_aux are new -- a stateless test entry into the training
  *     step's non-GEMM launchers; soccdpt_sizeof(6); nothing that existed changed);
  *   11 (soccdpt_fwd_aux_args and soccdpt_op_fwd_aux are new -- a stateless test entry into the forward path's non-GEMM launchers; soccdpt_sizeof(7);
- *     nothing that existed changed). */
-#define SOCCDPT_ABI_VERSION 11
+ *     nothing that existed changed);
+ *   12 (soccdpt_op_attention_bwd, soccdpt_op_attention_bwd_slots, soccdpt_op_vit_attention_bwd, soccdpt_op_attn_param_grads and soccdpt_op_qv_bias_grad are
+ *     new -- stateless test entries into the attention backward of the training step; nothing that existed changed). */
+#define SOCCDPT_ABI_VERSION 12
 
 /* backbone ids: model/loader.py:65-77 (model_type switch), model/blocks.py:59-78 */
 #define SOCCDPT_BACKBONE_SWIN2T16_256 0 /* dpt_swin2_tiny_256 */
@@ -756,6 +758,32 @@ typedef struct soccdpt_fwd_aux_args {
     void* out[6];
 } soccdpt_fwd_aux_args;
 int soccdpt_op_fwd_aux(const soccdpt_fwd_aux_args* args, uint32_t* path_out, void* stream);
+
+/* Test entries into the attention backward of the training step (csrc/train_attn.hip, csrc/train.hip): ONE launcher call on caller-supplied f32 device tensors.
+ * No handle, no allocation, no synchronisation; a refused call has launched nothing; errors through soccdpt_last_error(NULL).
+ * soccdpt_op_attention_bwd: tr_attention_bwd_mfma, the Swin-V2 cosine window attention backward (two launches).  qkv [B res res][3 heads 32], attn_out and dout
+ *   [B res res][heads 32], cpb_table [(2ws-1)^2][heads], scale [heads] -> ds [nwin][heads][N][N] (N = ws ws, nwin = B (res/ws)^2), rowstat [nwin][heads][N][2] =
+ *   {m + ln l, delta}, dscale_part [nwin][heads][soccdpt_op_attention_bwd_slots(ws)] (per-wave partials of d scale; slots of waves that own no query are 0),
+ *   dqkv [B res res][3 heads 32] = dq | dk | dv.  precision: SOCCDPT_PREC_F32, _BF16 or _F16 = the operands of the dP, dq / dk and dv products (the scores are
+ *   f32 in every form).  Refused: a null pointer, B / res / ws / heads <= 0, res % ws != 0, a shift other than 0 or ws / 2, a window size other than 8, 12, 16, 24,
+ *   SOCCDPT_PREC_F16X3, any other precision.
+ * soccdpt_op_attention_bwd_slots: tr_attention_bwd_mfma_slots (0: the window size is not instantiated).
+ * soccdpt_op_vit_attention_bwd: th_vit_attention_bwd_mfma, softmax(q k^T / 8) v backward with head dimension 64.  qkv [B N][3 heads 64], attn_out and dout
+ *   [B N][heads 64] -> rowstat [B][heads][N][2], dqkv [B N][3 heads 64].  Refused: a null pointer, B / N / heads <= 0, precision as above.
+ * soccdpt_op_attn_param_grads: tr_attn_param_grads.  ds (soccdpt_op_attention_bwd's; slab 0 is OVERWRITTEN by the sum over the nwin slabs when a table gradient
+ *   is asked for), dscale_part, cpb_table, logit_scale [heads], w0 [512][2], b0 [512], w2 [heads][512] -> dls [heads], dw0 [512][2], db0 [512], dw2 [heads][512],
+ *   each opt (at least one; only what is asked for is written); scratch dtable and dt [(2ws-1)^2][heads], hid 2 (2ws-1)^2 512 floats (needed by dw0 / db0 / dw2).
+ *   pws: the pretrained window size of the coordinate table (0: ws).
+ * soccdpt_op_qv_bias_grad: tr_qv_bias_grad.  dqkv_bias [3C] -> dq [C] opt, dv [C] opt (at least one). */
+int soccdpt_op_attention_bwd(const float* dev_qkv, const float* dev_attn_out, const float* dev_dout, const float* dev_cpb_table, const float* dev_scale, float* dev_ds,
+                             float* dev_rowstat, float* dev_dscale_part, float* dev_dqkv, int B, int res, int ws, int shift, int heads, int precision, void* stream);
+int soccdpt_op_attention_bwd_slots(int ws);
+int soccdpt_op_vit_attention_bwd(const float* dev_qkv, const float* dev_attn_out, const float* dev_dout, float* dev_rowstat, float* dev_dqkv, int B, int N, int heads,
+                                 int precision, void* stream);
+int soccdpt_op_attn_param_grads(float* dev_ds, const float* dev_dscale_part, const float* dev_cpb_table, const float* dev_logit_scale, const float* dev_w0,
+                                const float* dev_b0, const float* dev_w2, float* dev_dtable, float* dev_dt, float* dev_hid, float* dev_dls, float* dev_dw0,
+                                float* dev_db0, float* dev_dw2, int nwin, int ws, int pws, int heads, void* stream);
+int soccdpt_op_qv_bias_grad(const float* dev_dqkv_bias, float* dev_dq, float* dev_dv, int C, void* stream);
 
 /* Swin-V2 cosine window attention of one block (timm WindowAttention + shift/partition/reverse):
  * qkv [B*res*res][3*heads*32] -> out [B*res*res][heads*32], elements bf16 / f32 / fp16 by `precision` (SOCCDPT_PREC_*).  cpb_table [(2ws-1)^2][heads] f32 is

@@ -801,6 +801,67 @@ int soccdpt_op_fwd_aux(const soccdpt_fwd_aux_args* args, uint32_t* path_out, voi
     return 0;
 }
 
+// ---- the attention backward of the training step on caller-supplied tensors (tests): no handle, refusals before the first launch ----
+static int attn_bwd_fmt(const char* who, int precision, OpFmt* fmt) {
+    switch (precision) {
+        case SOCCDPT_PREC_F32: *fmt = OpFmt::F32; return 0;
+        case SOCCDPT_PREC_BF16: *fmt = OpFmt::BF16; return 0;
+        case SOCCDPT_PREC_F16: *fmt = OpFmt::F16; return 0;
+        case SOCCDPT_PREC_F16X3: *fmt = OpFmt::X3; return 0;   // the launchers refuse it themselves
+        default: return fail(nullptr, std::string(who) + ": unknown precision");
+    }
+}
+
+int soccdpt_op_attention_bwd_slots(int ws) { return tr_attention_bwd_mfma_slots(ws); }
+
+int soccdpt_op_attention_bwd(const float* dev_qkv, const float* dev_attn_out, const float* dev_dout, const float* dev_cpb_table, const float* dev_scale, float* dev_ds,
+                             float* dev_rowstat, float* dev_dscale_part, float* dev_dqkv, int B, int res, int ws, int shift, int heads, int precision, void* stream) {
+    std::string err;
+    OpFmt fmt;
+    if (attn_bwd_fmt("soccdpt_op_attention_bwd", precision, &fmt)) return 1;
+    if (tr_attention_bwd_mfma(dev_qkv, dev_attn_out, dev_dout, dev_cpb_table, dev_scale, dev_ds, dev_rowstat, dev_dscale_part, dev_dqkv, B, res, ws, shift, heads,
+                              (hipStream_t)stream, err, fmt))
+        return fail(nullptr, "soccdpt_op_attention_bwd: " + err);
+    return 0;
+}
+
+int soccdpt_op_vit_attention_bwd(const float* dev_qkv, const float* dev_attn_out, const float* dev_dout, float* dev_rowstat, float* dev_dqkv, int B, int N, int heads,
+                                 int precision, void* stream) {
+    std::string err;
+    OpFmt fmt;
+    if (attn_bwd_fmt("soccdpt_op_vit_attention_bwd", precision, &fmt)) return 1;
+    if (th_vit_attention_bwd_mfma(dev_qkv, dev_attn_out, dev_dout, dev_rowstat, dev_dqkv, B, N, heads, (hipStream_t)stream, err, fmt))
+        return fail(nullptr, "soccdpt_op_vit_attention_bwd: " + err);
+    return 0;
+}
+
+int soccdpt_op_attn_param_grads(float* dev_ds, const float* dev_dscale_part, const float* dev_cpb_table, const float* dev_logit_scale, const float* dev_w0,
+                                const float* dev_b0, const float* dev_w2, float* dev_dtable, float* dev_dt, float* dev_hid, float* dev_dls, float* dev_dw0,
+                                float* dev_db0, float* dev_dw2, int nwin, int ws, int pws, int heads, void* stream) {
+    std::string err;
+    const char* who = "soccdpt_op_attn_param_grads: ";
+    if (nwin <= 0 || ws <= 0 || heads <= 0 || pws < 0) return fail(nullptr, std::string(who) + "nwin, ws and heads must be positive, pws >= 0");
+    const int slots = tr_attention_bwd_mfma_slots(ws);
+    if (slots == 0) return fail(nullptr, std::string(who) + "no attention backward is instantiated for this window size");
+    if (pws == 1 || (pws == 0 && ws == 1)) return fail(nullptr, std::string(who) + "the coordinates divide by the (pretrained) window size - 1");
+    if (!dev_dls && !dev_dw0 && !dev_db0 && !dev_dw2) return fail(nullptr, std::string(who) + "no output requested");
+    if (dev_dls && (!dev_dscale_part || !dev_logit_scale)) return fail(nullptr, std::string(who) + "dls needs dscale_part and logit_scale");
+    if ((dev_dw0 || dev_db0 || dev_dw2) && (!dev_ds || !dev_cpb_table || !dev_w0 || !dev_b0 || !dev_w2 || !dev_dtable || !dev_dt || !dev_hid))
+        return fail(nullptr, std::string(who) + "the table gradients need dS, the table, w0, b0, w2 and the dtable / dt / hid scratch");
+    if (tr_attn_param_grads(dev_ds, dev_dscale_part, dev_cpb_table, dev_logit_scale, dev_w0, dev_b0, dev_w2, dev_dtable, dev_dt, dev_hid, dev_dls, dev_dw0, dev_db0,
+                            dev_dw2, nwin, ws, pws, heads, slots, (hipStream_t)stream, err))
+        return fail(nullptr, who + err);
+    return 0;
+}
+
+int soccdpt_op_qv_bias_grad(const float* dev_dqkv_bias, float* dev_dq, float* dev_dv, int C, void* stream) {
+    std::string err;
+    if (!dev_dqkv_bias || (!dev_dq && !dev_dv)) return fail(nullptr, "soccdpt_op_qv_bias_grad: null argument (the input and at least one output)");
+    if (C <= 0) return fail(nullptr, "soccdpt_op_qv_bias_grad: C must be positive");
+    if (tr_qv_bias_grad(dev_dqkv_bias, dev_dq, dev_dv, C, (hipStream_t)stream, err)) return fail(nullptr, "soccdpt_op_qv_bias_grad: " + err);
+    return 0;
+}
+
 int soccdpt_op_vit_attention_out(const void* dev_qkv, void* dev_out, int precision, int out_x3, int B, int N, int heads, void* stream) {
     std::string err;
     if (!dev_qkv || !dev_out) return fail(nullptr, "soccdpt_op_vit_attention: null argument");

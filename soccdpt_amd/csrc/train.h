@@ -58,7 +58,8 @@ int tr_merge_scatter(const float* dg, float* dx, int B, int R, int C, hipStream_
 int tr_patch_im2col(const float* x, float* out, int B, int S, hipStream_t st, std::string& err);
 int tr_pad_cols(const float* in, float* out, int N, int cin, int cout, hipStream_t st, std::string& err);
 // Cosine window attention backward on the matrix cores (train_attn.hip): rowstat holds {m + ln l, delta}; dscale_part has tr_attention_bwd_mfma_slots(ws) per
-// (window, head); a window size without an instantiation is an error
+// (window, head); refused before anything is launched: a null pointer, what window_attention_geometry refuses (the shift is 0 or ws / 2), a window size without
+// an instantiation, x3
 int tr_attention_bwd_mfma(const float* qkv, const float* attn_out, const float* dO, const float* table, const float* scale, float* dS, float* rowstat,
                           float* dscale_part, float* dqkv, int B, int res, int ws, int shift, int heads, hipStream_t st, std::string& err, OpFmt fmt);   // fmt: F32, BF16 or F16 products
 int tr_attention_bwd_mfma_slots(int ws);

@@ -726,7 +726,7 @@ __global__ __launch_bounds__(64) void attn_table_grad_kernel(const float* __rest
     for (int o = 1; o < 64; o <<= 1) s += __shfl_xor(s, o);
     if (threadIdx.x == 0) dtable[i] = s;
 }
-// logit_scale gradient: scale = exp(min(ls, ln 100)); d ls = scale * d scale when ls < ln 100
+// logit_scale gradient: scale = exp(min(ls, ln 100)); d ls = scale * d scale when ls <= ln 100 (torch.clamp passes the gradient at the bound itself)
 __global__ void attn_scale_reduce_kernel(const float* __restrict__ part, const float* __restrict__ ls, float* __restrict__ dls, int nwin, int heads, int nqb) {
     __shared__ float red[256];
     const int h = blockIdx.x;
@@ -740,7 +740,7 @@ __global__ void attn_scale_reduce_kernel(const float* __restrict__ part, const f
     }
     if (threadIdx.x == 0) {
         const float l = ls[h];
-        dls[h] = l < LN100 ? red[0] * __expf(l) : 0.f;
+        dls[h] = l <= LN100 ? red[0] * __expf(l) : 0.f;
     }
 }
 

@@ -683,7 +683,10 @@ int tr_attention_bwd_mfma_slots(int ws) {
 int tr_attention_bwd_mfma(const float* qkv, const float* attn_out, const float* dO, const float* table, const float* scale, float* dS, float* rowstat,
                           float* dscale_part, float* dqkv, int B, int res, int ws, int shift, int heads, hipStream_t st, std::string& err, OpFmt fmt) {
     if (fmt == OpFmt::X3) { err = "attention_bwd_mfma: products are f32, bf16 or fp16"; return 1; }
-    if (res % ws) { err = "attention_bwd_mfma: res must be a multiple of the window size"; return 1; }
+    // what the forward refuses (attention.hip window_attention_geometry): the kernels dereference every pointer, and their mask is the half-window shift's
+    if (!qkv || !attn_out || !dO || !table || !scale || !dS || !rowstat || !dscale_part || !dqkv) { err = "attention_bwd_mfma: null argument"; return 1; }
+    if (window_attention_geometry("attention_bwd_mfma", B, res, ws, shift, heads, err)) return 1;
+    if (tr_attention_bwd_mfma_slots(ws) == 0) { err = "attention_bwd_mfma: no instantiation for this window size"; return 1; }
     switch (ws) {
         case 8: launch_ws<8>(qkv, attn_out, dO, table, scale, dS, rowstat, dscale_part, dqkv, B, res, shift, heads, st, fmt); break;
         case 16: launch_ws<16>(qkv, attn_out, dO, table, scale, dS, rowstat, dscale_part, dqkv, B, res, shift, heads, st, fmt); break;
@@ -700,6 +703,8 @@ int tr_attention_bwd_mfma(const float* qkv, const float* attn_out, const float* 
 // ViT form: qkv [B*N][3E], O / dO [B*N][E], rowstat B * heads * N * 2 floats of scratch, dqkv [B*N][3E]
 int th_vit_attention_bwd_mfma(const float* qkv, const float* O, const float* dO, float* rowstat, float* dqkv, int B, int N, int heads, hipStream_t st, std::string& err, OpFmt fmt) {
     if (fmt == OpFmt::X3) { err = "vit_attention_bwd_mfma: products are f32, bf16 or fp16"; return 1; }
+    if (!qkv || !O || !dO || !rowstat || !dqkv) { err = "vit_attention_bwd_mfma: null argument"; return 1; }
+    if (B <= 0 || N <= 0 || heads <= 0) { err = "vit_attention_bwd_mfma: B, N and heads must be positive"; return 1; }
     const int NT = (N + 31) / 32, NOB = (NT + 3) / 4;
     const unsigned blocks = (unsigned)(B * heads * NOB);
 #define VIT_BWD(P, OPV) SOCCDPT_LAUNCH((vit_attn_bwd_mfma_kernel<P, OPV>), dim3(blocks), dim3(256), 0, st, qkv, dO, O, rowstat, dqkv, N, heads)

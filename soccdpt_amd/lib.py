@@ -15,7 +15,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SOCCDPT_LIB_PATH") or os.path.join(_HERE, "libsoccdpt_hip.so")   # override: A/B of two builds in one GPU call (tools/ab_bench.sh)
 
-ABI_VERSION = 11
+ABI_VERSION = 12
 BACKBONE_IDS = {"swin2t16_256": 0, "swin2b24_384": 1, "vitb_rn50_384": 2, "swin2l24_384": 3, "swinl12_384": 5}   # 4 is reserved for vitl16_384
 PREC_BF16 = 0
 PREC_F32 = 1
@@ -261,6 +261,11 @@ def _prototypes() -> dict:
         "soccdpt_op_train_aux_scratch_bytes": (cs, [P(TrainAuxArgs)]),
         "soccdpt_op_train_aux": (ci, [P(TrainAuxArgs), vp, cs, vp]),
         "soccdpt_op_fwd_aux": (ci, [P(FwdAuxArgs), P(ctypes.c_uint32), vp]),
+        "soccdpt_op_attention_bwd": (ci, [vp, vp, vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, vp]),
+        "soccdpt_op_attention_bwd_slots": (ci, [ci]),
+        "soccdpt_op_vit_attention_bwd": (ci, [vp, vp, vp, vp, vp, ci, ci, ci, ci, vp]),
+        "soccdpt_op_attn_param_grads": (ci, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, vp]),
+        "soccdpt_op_qv_bias_grad": (ci, [vp, vp, vp, ci, vp]),
         "soccdpt_op_window_attention": (ci, [vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, vp]),
         "soccdpt_op_window_attention_qkv": (ci, [vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, vp, vp]),
         "soccdpt_op_wino_weights": (ci, [vp, vp, vp, ci, ci, ci, vp]),
@@ -993,6 +998,35 @@ def op_fwd_aux(args: FwdAuxArgs, device: torch.device) -> int:
     path = ctypes.c_uint32(0)
     _call("soccdpt_op_fwd_aux", ctypes.byref(args), ctypes.byref(path), device=device, guard=False)
     return int(path.value)
+
+
+def op_attention_bwd_slots(ws: int) -> int:
+    """d scale partials per (window, head) that op_attention_bwd writes (0: the window size is not instantiated)."""
+    return int(load_library().soccdpt_op_attention_bwd_slots(int(ws)))
+
+
+def op_attention_bwd(qkv, attn_out, dout, cpb_table, scale, ds, rowstat, dscale_part, dqkv, B, res, ws, shift, heads, precision=PREC_F32):
+    """Kernel-level entry (tests): the Swin-V2 window attention backward of the training step on caller-supplied f32 tensors
+    (include/soccdpt_hip.h soccdpt_op_attention_bwd); precision = the operand format of the dP, dq / dk and dv products."""
+    _call("soccdpt_op_attention_bwd", _ptr(qkv), _ptr(attn_out), _ptr(dout), _ptr(cpb_table), _ptr(scale), _ptr(ds), _ptr(rowstat), _ptr(dscale_part), _ptr(dqkv),
+          B, res, ws, shift, heads, int(precision), device=dqkv.device, guard=False)
+
+
+def op_vit_attention_bwd(qkv, attn_out, dout, rowstat, dqkv, B, N, heads, precision=PREC_F32):
+    """Kernel-level entry (tests): the ViT attention backward of the hybrid's training step (soccdpt_op_vit_attention_bwd)."""
+    _call("soccdpt_op_vit_attention_bwd", _ptr(qkv), _ptr(attn_out), _ptr(dout), _ptr(rowstat), _ptr(dqkv), B, N, heads, int(precision), device=dqkv.device, guard=False)
+
+
+def op_attn_param_grads(ds, dscale_part, cpb_table, logit_scale, w0, b0, w2, dtable, dt, hid, dls, dw0, db0, dw2, nwin, ws, pws, heads):
+    """Kernel-level entry (tests): dS and the d scale partials -> the gradients of logit_scale and the CPB MLP (soccdpt_op_attn_param_grads); dls / dw0 / db0 /
+    dw2 may be None, dtable / dt / hid are the caller's scratch."""
+    _call("soccdpt_op_attn_param_grads", _ptr(ds), _ptr(dscale_part), _ptr(cpb_table), _ptr(logit_scale), _ptr(w0), _ptr(b0), _ptr(w2), _ptr(dtable), _ptr(dt),
+          _ptr(hid), _ptr(dls), _ptr(dw0), _ptr(db0), _ptr(dw2), nwin, ws, pws, heads, device=logit_scale.device, guard=False)
+
+
+def op_qv_bias_grad(dqkv_bias, dq, dv, C):
+    """Kernel-level entry (tests): q_bias / v_bias gradients from the qkv bias gradient [3C] (soccdpt_op_qv_bias_grad); dq or dv may be None."""
+    _call("soccdpt_op_qv_bias_grad", _ptr(dqkv_bias), _ptr(dq), _ptr(dv), C, device=dqkv_bias.device, guard=False)
 
 
 def op_window_attention(qkv, cpb_table, scale, out, B, res, ws, shift, heads, precision=PREC_BF16):
