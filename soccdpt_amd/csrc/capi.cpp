@@ -719,6 +719,11 @@ int soccdpt_op_igemm(const soccdpt_igemm_args* a, void* stream) {
     std::string err;
     if (a->gn_stats && a->gn_count && (a->gn_hw <= 0 || a->gn_cpg <= 0 || a->M % a->gn_hw || a->N % a->gn_cpg))
         return fail(nullptr, "soccdpt_op_igemm: GroupNorm statistics requested with gn_hw / gn_cpg that do not divide M / N");
+    // x3 tile 12 has no generalised-addressing instantiation, and for such a descriptor the tile rule (igemm.hip: pick_cfg_f32) passes tune 12 over and runs
+    // tile 4 or 1: at this entry a tune names the tile under test, so the launch is refused
+    if (d.x3 && d.tune == 12 && d.splitk <= 1 && !d.ln_g &&
+        (d.stride != 1 || d.pad != 1 || d.in_halo != 1 || d.Hi || d.Wi || d.gather1 || d.grp_rows || d.seg2_k || d.stamps))
+        return fail(nullptr, "soccdpt_op_igemm: x3 configuration 12 has no generalised addressing");
     if (launch_igemm(d, (hipStream_t)stream, err)) return fail(nullptr, err);
     if (a->gn_stats && a->gn_count && (gn_bm <= 0 || a->gn_hw % gn_bm))
         return fail(nullptr, "soccdpt_op_igemm: statistics requested but the chosen tile has no statistics epilogue (tune forces a tile without one)");

@@ -300,18 +300,21 @@ def w_fmt(family):
     return "x3" if family == "x2w" else family
 
 
+def draw_values(g, dataset, shape, mag=4):
+    """The two data sets (module docstring): "exact" -- nonzero integers of magnitude <= mag; "real" -- randn with a power-of-two scale per row."""
+    if dataset == "exact":
+        v = torch.randint(1, mag + 1, shape, generator=g).float()
+        return v * (torch.randint(0, 2, shape, generator=g).float() * 2 - 1)
+    scale = 2.0 ** torch.randint(-3, 4, (shape[0],) + (1,) * (len(shape) - 1), generator=g).float()
+    return torch.randn(shape, generator=g) * scale
+
+
 def make_data(c: Case, family, dataset, seed=0):
     """dict(X | xh, Wt, bias, res1) of float64 CPU tensors.  Linear: X is [M][ldx] with NaN in the 16 padding columns; conv: xh is the zero-halo NHWC image.
     X_src / Wt_src: the f32 tensors the operands were rounded or encoded from (device_operand makes the launch's operand from them the same way)."""
     g = torch.Generator().manual_seed(seed * 7919 + c.M * 31 + c.N * 17 + c.Cin + (1 if dataset == "real" else 0))
     K = c.taps * c.Cin
-
-    def draw(*shape):
-        if dataset == "exact":
-            v = torch.randint(1, 5, shape, generator=g).float()
-            return v * (torch.randint(0, 2, shape, generator=g).float() * 2 - 1)
-        scale = 2.0 ** torch.randint(-3, 4, (shape[0],) + (1,) * (len(shape) - 1), generator=g).float()
-        return torch.randn(shape, generator=g) * scale
+    draw = lambda *shape: draw_values(g, dataset, shape)
     d = {}
     if c.kind == "linear":
         x = torch.full((c.M, c.ldx), float("nan"))
