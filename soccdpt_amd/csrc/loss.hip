@@ -72,10 +72,10 @@ __global__ __launch_bounds__(256) void loss_up_stats_kernel(LossParams P, const 
         raw_up[(size_t)b * npix + i] = raw;
         if (mask[(size_t)b * npix + i]) {
             const float p = clamp_pred(raw), t = y[(size_t)b * npix + i];
-            a[0] += (double)(p * p);
+            a[0] += (double)p * (double)p;  // exact products: the solve subtracts these sums (an f32-rounded product costs 1e-5 of a small scale)
             a[1] += (double)p;
             a[2] += 1.0;
-            a[3] += (double)(p * t);
+            a[3] += (double)p * (double)t;
             a[4] += (double)t;
 #pragma unroll
             for (int k = 1; k < NSC; ++k)
@@ -100,7 +100,10 @@ __global__ __launch_bounds__(256) void loss_up_stats_kernel(LossParams P, const 
 }
 
 // scale / shift of image b in f32 like the reference (x_0, x_1; zero when det == 0) -- recomputed wherever needed
-// (the 2x2 solve and its derivative are evaluated in f64: they subtract sums of ~1e6 terms of similar size)
+// (the 2x2 solve and its derivative are evaluated in f64: they subtract sums of ~1e6 terms of similar size).
+// With fewer than two valid pixels the reference's determinant a00 a11 - a01^2 is identically zero in any precision (p^2 * 1 - p * p),
+// whereas a sum of rounded terms minus an exact square need not be (with a00 from f32-rounded products det was the rounding error of
+// one product, and the single pixel was "fitted": scale 1.4e7 on a clamped pixel): a11 < 2 is singular by count, not by a threshold.
 struct Solve {
     float s, t;
     double det, a00, a01, a11, b0, b1;
@@ -110,7 +113,7 @@ __device__ __forceinline__ Solve solve_image(const LossParams& P, const double* 
     Solve q;
     q.a00 = img[IMG_A00]; q.a01 = img[IMG_A01]; q.a11 = img[IMG_A11]; q.b0 = img[IMG_B0]; q.b1 = img[IMG_B1];
     q.det = q.a00 * q.a11 - q.a01 * q.a01;
-    q.ok = P.compute_ss && q.det != 0.0;
+    q.ok = P.compute_ss && q.a11 >= 2.0 && q.det != 0.0;
     q.s = P.compute_ss ? 0.f : 1.f;
     q.t = 0.f;
     if (q.ok) {
@@ -190,7 +193,7 @@ __global__ __launch_bounds__(256) void loss_terms_kernel(LossParams P, const flo
             g += P.alpha * invMk[k] * m * acc_sign;  // d(diff)/d(ssi) = m
         }
         g_out[(size_t)b * npix + i] = g;
-        gs += (double)(g * p);
+        gs += (double)g * (double)p;
         gt += (double)g;
     }
     double s = block_sum_d(e0, sh);
@@ -314,7 +317,7 @@ __global__ __launch_bounds__(256) void loss_bce_kernel(LossParams P, const float
         int X0 = (int)ceilf((float)xs / sx) - 1, X1 = (int)ceilf((float)(xs + 1) / sx) + 1;
         Y0 = Y0 < 0 ? 0 : Y0; X0 = X0 < 0 ? 0 : X0;
         Y1 = Y1 > P.H - 1 ? P.H - 1 : Y1; X1 = X1 > P.W - 1 ? P.W - 1 : X1;
-        float gacc = 0.f;
+        double gacc = 0.0;  // sum of (q - t) over the footprint: mixed targets cancel, an f32 running sum loses ~10 ulp of the cell at 64 pixels
         for (int Y = Y0; Y <= Y1; ++Y) {
             if (nearest_src(Y, P.h, sy) != ys) continue;
             const size_t ro = (bc * P.H + Y) * P.W;
@@ -323,10 +326,10 @@ __global__ __launch_bounds__(256) void loss_bce_kernel(LossParams P, const float
                 const float t = y_seg[ro + X];
                 lsum += (double)(-(t * lq + (1.f - t) * l1q));
                 nsum += 1.0;
-                gacc += (qv - t) * inv_den;
+                gacc += (double)qv - (double)t;
             }
         }
-        d_seg[i] = gacc;
+        d_seg[i] = (float)(gacc * (double)inv_den);
     }
     double s = block_sum_d(lsum, sh);
     if (threadIdx.x == 0) atomicAdd(&glob[GLOB_BCE], s);
