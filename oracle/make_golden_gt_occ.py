@@ -51,5 +51,35 @@ def main():
     print("wrote", path, "occupied cells:", int(grid.sum()), "per class", [int(grid[..., c].sum()) for c in range(C)])
 
 
+def geometries():
+    """tests/golden/gt_occupancy_geoms.npz: the same class at the rows of tests/gt_occ_refs.GOLDEN -- other cameras (one with odd H), grids, scales,
+    pc_scale / pc_shift, thresholds and C; the rotation stays the (7, 0, 0) that process_frame hard-codes.  The frames are small: packed grid bits and the
+    whole depth and point cloud are recorded."""
+    from tests import gt_occ_refs as T
+    rec = {}
+    for g in T.GOLDEN:
+        _, disparity, seg_class = T.inputs(g.name)
+        assert g.B == 1 and tuple(g.angles) == (7.0, 0.0, 0.0)
+        colors = {c: (40 * c + 10, 40 * c + 10, 40 * c + 10) for c in range(g.C)}
+        seg_frame = np.zeros((g.H, g.W, 3), dtype=np.uint8)
+        for c, col in colors.items():
+            seg_frame[seg_class[0] == c] = col
+        proc = ref.OccupancyProcessor(intrinsic_matrix=T.intrinsics(g), height=g.H, width=g.W, grid_size=tuple(g.grid), scale=T.scale_of(g),
+                                      shift=(0.0, 0.0, 0.0), pc_scale=g.pc_scale, pc_shift=g.pc_shift, point_count_threshold=g.threshold,
+                                      class_2_color=dict(colors), color_2_class={v: k for k, v in colors.items()}, num_classes=g.C)
+        out = proc.process_frame(dict(rgb_frame=np.zeros((g.H, g.W, 3), dtype=np.uint8), disparity_frame=disparity[0].copy(), seg_frame=seg_frame))
+        grid, pts, depth = np.asarray(out["occupancy_grid"]), np.asarray(out["points"]), np.asarray(out["depth"])
+        assert grid.dtype == bool and pts.dtype == np.float64 and depth.dtype == np.float32
+        key = g.name.replace(" ", "_")
+        rec[key + "/grid_bits"], rec[key + "/grid_shape"] = np.packbits(grid.reshape(-1)), np.array(grid.shape)
+        rec[key + "/depth"], rec[key + "/points"] = depth, pts
+        print(g.name, "occupied cells:", int(grid.sum()))
+    path = os.path.join(REPO, "tests", "golden", "gt_occupancy_geoms.npz")
+    np.savez_compressed(path, **rec)
+    print("wrote", path)
+
+
 if __name__ == "__main__":
-    main()
+    if "geoms" not in sys.argv[1:]:          # `python oracle/make_golden_gt_occ.py geoms` records the geometry rows only
+        main()
+    geometries()

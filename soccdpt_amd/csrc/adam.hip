@@ -2,7 +2,7 @@
 // /root/reference/SOccDPT/scripts/train_SOccDPT.py:311-318: torch.optim.Adam(lr, betas=(0.9, 0.999), eps=1e-8,
 // weight_decay, amsgrad=False)).  torch's single-tensor path issues ~8 elementwise ATen kernels per parameter tensor and step
 // (330 tensors for SOccDPT_V3); here up to 48 tensors share one launch (descriptor table in the kernel arguments) and every
-// element is read and written once: p, m, v updated in place from g.
+// element is read and written once: p, m, v updated in place from g.  A tensor of 0 elements is stepped over, null pointers and all.
 //   g' = g + wd * p;  m = m + (1 - b1) (g' - m);  v = b2 v + (1 - b2) g'^2
 //   p -= (lr / (1 - b1^t)) * m / (sqrt(v) / sqrt(1 - b2^t) + eps)            (torch/optim/adam.py _single_tensor_adam)
 #include "kernels.h"
@@ -52,19 +52,23 @@ int launch_adam(int n_tensors, float* const* params, const float* const* grads, 
     const double bc1 = 1.0 - pow(beta1, (double)step), bc2 = 1.0 - pow(beta2, (double)step);
     AdamScalars s{(float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), (float)weight_decay, (float)(lr / bc1),
                   (float)(1.0 / sqrt(bc2)), (float)eps};
-    for (int base = 0; base < n_tensors; base += kAdamChunk) {
+    // a tensor of 0 elements is stepped over like torch does (its pointers may be null: torch.empty(0).data_ptr() == 0) and takes no
+    // slot of a table; every pointer is checked before the first launch, so a refused call has written nothing
+    for (int i = 0; i < n_tensors; ++i)
+        if (sizes[i] && (!params[i] || !grads[i] || !exp_avg[i] || !exp_avg_sq[i])) { err = "adam: null tensor pointer"; return 1; }
+    for (int i = 0; i < n_tensors;) {
         AdamTable t{};
-        const int cnt = n_tensors - base < kAdamChunk ? n_tensors - base : kAdamChunk;
+        int cnt = 0;
         size_t nmax = 0;
-        for (int k = 0; k < cnt; ++k) {
-            if (!params[base + k] || !grads[base + k] || !exp_avg[base + k] || !exp_avg_sq[base + k]) { err = "adam: null tensor pointer"; return 1; }
-            t.p[k] = params[base + k]; t.g[k] = grads[base + k]; t.m[k] = exp_avg[base + k]; t.v[k] = exp_avg_sq[base + k];
-            t.n[k] = sizes[base + k];
-            nmax = sizes[base + k] > nmax ? sizes[base + k] : nmax;
+        for (; i < n_tensors && cnt < kAdamChunk; ++i) {
+            if (!sizes[i]) continue;
+            t.p[cnt] = params[i]; t.g[cnt] = grads[i]; t.m[cnt] = exp_avg[i]; t.v[cnt] = exp_avg_sq[i];
+            t.n[cnt++] = sizes[i];
+            nmax = sizes[i] > nmax ? sizes[i] : nmax;
         }
-        unsigned gx = (unsigned)((nmax + 255) / 256);
-        if (gx > 512) gx = 512;
-        if (gx < 1) gx = 1;
+        if (!cnt) break;
+        const size_t blocks = (nmax + 255) / 256;      // >= 1: no empty tensor is in the table
+        const unsigned gx = blocks > 512 ? 512u : (unsigned)blocks;
         SOCCDPT_LAUNCH(adam_kernel, dim3(gx, cnt), dim3(256), 0, st, t, s);
         if (check_launch("adam", err)) return 1;
     }

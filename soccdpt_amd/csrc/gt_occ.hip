@@ -7,6 +7,9 @@
 // One thread per pixel in float64 where numpy computes in float64; the float contract is the one of oracle/gt_occ_ref.c
 // (pinned bit for bit by the reference's own class: tests/golden/gt_occupancy.npz).  This translation unit is compiled with
 // -ffp-contract=off: the only fused operations are the explicit fma() of the three K = 3 dgemm-order rotations.
+// Class ids: a pixel whose id lies outside [0, C) contributes nothing.  The reference's np.add.at would wrap -1 to the last class and raise
+// IndexError on an id >= C; its rgb_seg_to_class produces neither, so no frame of the reference tells the two apart (pinned by
+// tests/gt_occ_refs.py: ids -1, C, 255 and INT32_MIN among valid ones).
 #include "kernels.h"
 
 namespace soccdpt {

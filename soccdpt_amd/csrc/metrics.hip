@@ -4,8 +4,12 @@
 //                                                                                 over ALL masked pixels of the batch)
 //   IoU@0.5 per image        /root/reference/SOccDPT/utils/__init__.py:314-330
 // The reference round-trips every prediction to the host (`.cpu().numpy()`) per batch; here predictions stay in HBM.
-// Sums are accumulated per thread in f32 over short runs, per block in f64, and merged with one f64 atomic per block
-// and quantity (the reference sums in f32; differences are at the 1e-6 level).
+// Every term is formed in f32 like the reference's (p * p, |g - q| / g, ...) and added in f64: per thread, per block, and merged with
+// one f64 atomic per block and quantity (the reference sums in f32; differences are at the 1e-6 level).
+// Masked-out pixels: the kernels test the mask byte (any non-zero byte is "inside") and never read a masked-out value into a sum.  The
+// reference multiplies by the mask, so a NaN or inf OUTSIDE the mask poisons its sums (0 * NaN) and not ours.  That divergence is deliberate:
+// a depth map with holes marked NaN under a zero mask evaluates here (pinned by tests/metrics_refs.py: every case runs again with NaN / inf
+// at every masked-out pixel and must give the same bits).
 #include "kernels.h"
 
 namespace soccdpt {
@@ -52,7 +56,10 @@ __global__ __launch_bounds__(256) void lsq_sums_kernel(const float* __restrict__
 // scale/shift per image from the 5 sums (x0, x1 of the reference; zero when det == 0), computed in f32 like the reference
 __device__ __forceinline__ void solve_lsq(const double* s, float& scale, float& shift) {
     const float a00 = (float)s[0], a01 = (float)s[1], a11 = (float)s[2], b0 = (float)s[3], b1 = (float)s[4];
-    const float det = a00 * a11 - a01 * a01;
+    // explicit operations, so that "det == 0" does not hang on the compiler's choice of contraction: a01 * a01 is rounded on its own (__fmul_rn is
+    // never fused), then one fma.  One masked pixel gives a00 = rn(p p), a11 = 1, a01 = p and det = rn(p p) - rn(p p) = 0 exactly, like the reference's
+    // unfused float32; an fma over the SECOND product would leave the rounding error of p p there and divide by it.
+    const float det = fmaf(a00, a11, -__fmul_rn(a01, a01));
     scale = 0.f;
     shift = 0.f;
     if (det != 0.f) {

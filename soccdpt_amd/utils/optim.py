@@ -43,6 +43,8 @@ class Adam:
             if st is None:
                 st = self.state[p] = dict(step=0, exp_avg=torch.zeros_like(p), exp_avg_sq=torch.zeros_like(p))
             st["step"] += 1
+            if p.numel() == 0:      # stepped over like torch does: the count advances, nothing is launched for it (its data_ptr() is 0)
+                continue
             groups.setdefault((st["step"], p.device), []).append((p, st))
         for (step, dev), items in groups.items():
             n = len(items)
