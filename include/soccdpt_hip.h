@@ -412,9 +412,12 @@ int soccdpt_gt_occupancy(int B, int H, int W, int C, const double* intr, const d
  *   x_f32[m][:] += LayerNorm(fc2(GELU(fc1(x_op[m][:]))))      fc1: w1 [4C][C] + b1, fc2: w2 [C][4C] + b2, LayerNorm eps 1e-5
  * (timm Mlp + res-post-norm).  x_op [M][C] 16-bit operand copy of x (bf16 / fp16 by precision), w1 / w2 in the
  * same format; x_op_out (may alias x_op) receives the operand copy of the new x, halo (nullable) a zero-halo NHWC image of it
- * ([B][H+2][W+2][C], M = B*H*W).  C in {96, 128, 192, 256}. */
+ * ([B][H+2][W+2][C], M = B*H*W; only the interior is written).  merge != 0 (the last block of a stage in the network): x_op_out receives the copy in the
+ * operand layout of the following PatchMerging instead, [B][H/2][W/2][4C] with token (b, y, x) in row (b, y/2, x/2) at channel block (y & 1) + 2 (x & 1)
+ * -- timm's cat([x[0::2, 0::2], x[1::2, 0::2], x[0::2, 1::2], x[1::2, 1::2]], -1); it needs the token grid with H and W even and an x_op_out that is
+ * neither NULL nor x_op (x_f32 and halo keep the plain layout).  C in {96, 128, 192, 256}. */
 int soccdpt_op_mlp_ln(const void* x_op, float* x_f32, const void* w1, const float* b1, const void* w2, const float* b2, const float* ln_g,
-                      const float* ln_b, void* x_op_out, void* halo, int precision, int M, int C, int H, int W, void* stream);
+                      const float* ln_b, void* x_op_out, void* halo, int precision, int M, int C, int H, int W, int merge, void* stream);
 
 /* ---- input transform (model/loader.py:256-270 Compose([Resize, NormalizeImage, PrepareForNet])) ----
  * img [B,Hs,Ws,3] u8 (RGB frames as the datasets hand them over, datasets/bengaluru_driving_dataset.py:118-130) ->

@@ -644,11 +644,11 @@ int soccdpt_input_transform_u8(const uint8_t* img, int B, int Hs, int Ws, int Hd
 }
 
 int soccdpt_op_mlp_ln(const void* x_op, float* x_f32, const void* w1, const float* b1, const void* w2, const float* b2, const float* ln_g,
-                      const float* ln_b, void* x_op_out, void* halo, int precision, int M, int C, int H, int W, void* stream) {
+                      const float* ln_b, void* x_op_out, void* halo, int precision, int M, int C, int H, int W, int merge, void* stream) {
     std::string err;
     if (precision != SOCCDPT_PREC_BF16 && precision != SOCCDPT_PREC_F16) return fail(nullptr, "soccdpt_op_mlp_ln: 16-bit operand modes only");
     if (launch_mlp_ln(static_cast<const bf16_t*>(x_op), x_f32, static_cast<const bf16_t*>(w1), b1, static_cast<const bf16_t*>(w2), b2, ln_g, ln_b,
-                      static_cast<bf16_t*>(x_op_out), static_cast<bf16_t*>(halo), precision == SOCCDPT_PREC_F16, M, C, H, W, 0, (hipStream_t)stream, err))
+                      static_cast<bf16_t*>(x_op_out), static_cast<bf16_t*>(halo), precision == SOCCDPT_PREC_F16, M, C, H, W, merge ? 1 : 0, (hipStream_t)stream, err))
         return fail(nullptr, err);
     return 0;
 }

@@ -237,7 +237,7 @@ def _prototypes() -> dict:
         "soccdpt_training_loss": (ci, [ci, ci, ci, ci, ci, ci, ci, cf, cf, cf, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
         # ---- ground-truth occupancy generator ----
         "soccdpt_gt_occupancy": (ci, [ci, ci, ci, ci, vp, vp, vp, vp, vp, vp, cf, vp, vp, vp, vp, vp, vp, vp]),
-        "soccdpt_op_mlp_ln": (ci, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, vp]),
+        "soccdpt_op_mlp_ln": (ci, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, vp]),
         # ---- input transform ----
         "soccdpt_input_transform_u8": (ci, [vp, ci, ci, ci, ci, ci, P(cd), P(cd), vp, vp]),
         "soccdpt_adam_step": (ci, [ci, vp, vp, vp, vp, vp, cd, cd, cd, cd, cd, ci, vp]),
@@ -942,11 +942,12 @@ def op_pack_expand(idx: torch.Tensor, k: int, palette: torch.Tensor, H: int, W: 
     return out
 
 
-def op_mlp_ln(x_op, x_f32, w1, b1, w2, b2, ln_g, ln_b, x_op_out=None, halo=None, precision=PREC_BF16, H=0, W=0):
-    """Kernel-level entry (tests): x_f32 += LN(fc2(GELU(fc1(x_op)))) in one launch (soccdpt_op_mlp_ln) on the current stream."""
+def op_mlp_ln(x_op, x_f32, w1, b1, w2, b2, ln_g, ln_b, x_op_out=None, halo=None, precision=PREC_BF16, H=0, W=0, merge=False):
+    """Kernel-level entry (tests): x_f32 += LN(fc2(GELU(fc1(x_op)))) in one launch (soccdpt_op_mlp_ln) on the current stream.  merge: x_op_out [M / 4][4C] in the
+    PatchMerging operand layout (include/soccdpt_hip.h)."""
     M, C = x_op.shape
     _call("soccdpt_op_mlp_ln", _ptr(x_op), _ptr(x_f32), _ptr(w1), _ptr(b1), _ptr(w2), _ptr(b2), _ptr(ln_g), _ptr(ln_b), _ptr(x_op_out), _ptr(halo),
-          int(precision), M, C, H, W, device=x_op.device, guard=False)
+          int(precision), M, C, int(H), int(W), 1 if merge else 0, device=x_op.device, guard=False)
 
 
 def op_wgrad_tn(a, lda, b, ldb, K, Nout, C, taps=1, rp=0, precision=PREC_BF16, b_row0=0):

@@ -210,6 +210,20 @@ def test_prototype_table_matches_the_header():
             assert _ctypes_class(a) == w, f"{name}: parameter {i} is {w} in the header, {a} in the table"
 
 
+def test_op_mlp_ln_takes_merge_before_the_stream():
+    """soccdpt_op_mlp_ln reaches the kernel's PatchMerging operand layout: `int merge` sits between W and the stream in the header, the table has the 17 parameters
+    and op_mlp_ln hands it on (default off) -- tests/test_mlp_fused_gpu.py runs the layout through it."""
+    import inspect
+    from soccdpt_amd.lib import PROTOTYPES, op_mlp_ln
+    text = open(os.path.join(REPO, "include", "soccdpt_hip.h")).read()
+    params = re.search(r"int\s+soccdpt_op_mlp_ln\s*\(([^)]*)\)\s*;", text).group(1)
+    names = [" ".join(p.split()) for p in params.split(",")]
+    assert len(names) == 17 and names[-6:] == ["int M", "int C", "int H", "int W", "int merge", "void* stream"], names[-6:]
+    restype, argtypes = PROTOTYPES["soccdpt_op_mlp_ln"]
+    assert restype is ctypes.c_int and len(argtypes) == 17 and argtypes[10:16] == [ctypes.c_int] * 6 and argtypes[16] is ctypes.c_void_p
+    assert inspect.signature(op_mlp_ln).parameters["merge"].default is False
+
+
 def test_load_library_leaves_no_function_on_ctypes_defaults():
     from soccdpt_amd.lib import PROTOTYPES, load_library
     L = load_library()
