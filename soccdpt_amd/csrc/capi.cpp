@@ -11,8 +11,10 @@
 #include "kernels.h"
 #include "occ_eval.h"
 #include "visualise.h"
+#include "occ_view.h"
 #include "batch_targets.h"
 #include "../../include/soccdpt_vis.h"
+#include "../../include/soccdpt_occ_view.h"
 #include "../../include/soccdpt_data.h"
 
 using namespace soccdpt;
@@ -1023,6 +1025,55 @@ int soccdpt_vis_half_size(int H, int W, int32_t* Hd, int32_t* Wd) {
 int soccdpt_vis_shrink_half(const uint8_t* dev_src, int B, int H, int W, int swap_rb, uint8_t* dev_dst, void* stream) {
     std::string err;
     if (launch_vis_shrink_half(dev_src, B, H, W, swap_rb, dev_dst, (hipStream_t)stream, err)) return fail(nullptr, "soccdpt_" + err);
+    return 0;
+}
+
+// ---- occupancy grid pictures (include/soccdpt_occ_view.h; csrc/occ_view.hip) ----
+int soccdpt_occ_view_columns(const uint32_t* dev_bits, int rows, const int32_t* host_grid, int C, int axis, int from_high, uint8_t* dev_top,
+                             int32_t* dev_first, int32_t* dev_count, uint8_t* dev_classes, void* stream) {
+    std::string err;
+    if (launch_occ_view_columns(dev_bits, rows, host_grid, C, axis, from_high, dev_top, dev_first, dev_count, dev_classes, (hipStream_t)stream, err))
+        return fail(nullptr, "soccdpt_" + err);
+    return 0;
+}
+
+int soccdpt_occ_view_paint(const uint8_t* dev_top, const int32_t* dev_first, int rows, int A, int B, int depth_len, int from_high,
+                           const uint8_t* dev_class_colors, int C, const uint8_t* host_background, int shade, int zoom, int flip_a, int flip_b,
+                           int transpose, uint8_t* dev_dst, size_t dst_pitch_px, size_t dst_offset_px, size_t dst_frame_px, size_t dst_total_px,
+                           void* stream) {
+    std::string err;
+    const VisDst d{dst_pitch_px, dst_offset_px, dst_frame_px, dst_total_px};
+    if (launch_occ_view_paint(dev_top, dev_first, rows, A, B, depth_len, from_high, dev_class_colors, C, host_background, shade, zoom, flip_a, flip_b,
+                              transpose, dev_dst, d, (hipStream_t)stream, err))
+        return fail(nullptr, "soccdpt_" + err);
+    return 0;
+}
+
+int soccdpt_occ_view_iou2d(const uint8_t* dev_pred_classes, int pred_rows, const uint8_t* dev_gt_classes, int rows, size_t ncol, int C,
+                           uint64_t* dev_counts, void* stream) {
+    std::string err;
+    if (launch_occ_view_iou2d(dev_pred_classes, pred_rows, dev_gt_classes, rows, ncol, C, dev_counts, (hipStream_t)stream, err))
+        return fail(nullptr, "soccdpt_" + err);
+    return 0;
+}
+
+int soccdpt_occ_view_splat(const uint32_t* dev_bits, int rows, const int32_t* host_grid, int C, const double* host_voxel_to_camera,
+                           const double* host_intrinsics, double half_extent_m, int max_radius_px, double z_near, int H, int W, uint64_t* dev_zbuf,
+                           void* stream) {
+    std::string err;
+    if (launch_occ_view_splat(dev_bits, rows, host_grid, C, host_voxel_to_camera, host_intrinsics, half_extent_m, max_radius_px, z_near, H, W, dev_zbuf,
+                              (hipStream_t)stream, err))
+        return fail(nullptr, "soccdpt_" + err);
+    return 0;
+}
+
+int soccdpt_occ_view_resolve(const uint64_t* dev_zbuf, const uint8_t* dev_frames, int frame_rows, int rows, int H, int W, int C,
+                             const uint8_t* dev_class_colors, int alpha, uint8_t* dev_dst, size_t dst_pitch_px, size_t dst_offset_px,
+                             size_t dst_frame_px, size_t dst_total_px, void* stream) {
+    std::string err;
+    const VisDst d{dst_pitch_px, dst_offset_px, dst_frame_px, dst_total_px};
+    if (launch_occ_view_resolve(dev_zbuf, dev_frames, frame_rows, rows, H, W, C, dev_class_colors, alpha, dev_dst, d, (hipStream_t)stream, err))
+        return fail(nullptr, "soccdpt_" + err);
     return 0;
 }
 

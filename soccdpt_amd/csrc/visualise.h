@@ -14,6 +14,10 @@ struct VisDst {
     size_t pitch_px, offset_px, frame_px, total_px;
 };
 
+// the two argument checks every picture launcher makes (also occ_view.hip's): the image sizes, and that the destination rectangle fits its buffer
+bool vis_image_ok(int B, int H, int W, const char* what, std::string& err);
+bool vis_dst_ok(int B, int H, int W, const VisDst& d, const char* what, std::string& err);
+
 size_t vis_minmax_scratch_bytes(int B, size_t npix);
 int launch_vis_minmax(const float* x, int B, size_t npix, float* minmax, void* scratch, size_t scratch_bytes, hipStream_t st, std::string& err);
 int launch_vis_colorize(const float* x, const float* minmax, const uint8_t* lut, int B, int H, int W, uint8_t* dst, const VisDst& d, hipStream_t st,

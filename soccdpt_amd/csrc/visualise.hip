@@ -303,6 +303,9 @@ dim3 image_grid(int B, int H, int W) {
 
 }  // namespace
 
+bool vis_image_ok(int B, int H, int W, const char* what, std::string& err) { return image_ok(B, H, W, what, err); }
+bool vis_dst_ok(int B, int H, int W, const VisDst& d, const char* what, std::string& err) { return dst_ok(B, H, W, d, what, err); }
+
 static size_t minmax_blocks(size_t npix) {
     const size_t blocks = ((npix + kPx - 1) / kPx + 255) / 256;
     return blocks > 1024 ? 1024 : blocks;

@@ -346,6 +346,23 @@ def _swin1_prototypes() -> dict:
 
 
 SWIN1_PROTOTYPES = _swin1_prototypes()
+
+
+def _occ_view_prototypes() -> dict:
+    """The same table for include/soccdpt_occ_view.h (pictures of the packed occupancy grid, csrc/occ_view.hip), in that header's order;
+    tests/test_occ_view_cpu.py holds it against the header.  A sixth header and a sixth table: soccdpt_hip.h and its ABI version do not change."""
+    vp, ci, cs, cd = ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t, ctypes.c_double
+    i32, u8, f64 = ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_uint8), ctypes.POINTER(cd)
+    return {
+        "soccdpt_occ_view_columns": (ci, [vp, ci, i32, ci, ci, ci, vp, vp, vp, vp, vp]),
+        "soccdpt_occ_view_paint": (ci, [vp, vp, ci, ci, ci, ci, ci, vp, ci, u8, ci, ci, ci, ci, ci, vp, cs, cs, cs, cs, vp]),
+        "soccdpt_occ_view_iou2d": (ci, [vp, ci, vp, ci, cs, ci, vp, vp]),
+        "soccdpt_occ_view_splat": (ci, [vp, ci, i32, ci, f64, f64, cd, ci, cd, ci, ci, vp, vp]),
+        "soccdpt_occ_view_resolve": (ci, [vp, vp, ci, ci, ci, ci, ci, vp, ci, vp, cs, cs, cs, cs, vp]),
+    }
+
+
+OCC_VIEW_PROTOTYPES = _occ_view_prototypes()
 PACK_INDEX_BITS = (1, 2, 4, 8)   # k of include/soccdpt_pack.h
 
 
@@ -359,7 +376,7 @@ def load_library() -> ctypes.CDLL:
             f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "(make -C soccdpt_amd/csrc).  The SOccDPT MI355X path has no CPU fallback.")
     L = ctypes.CDLL(LIB_PATH)
-    for table in (PROTOTYPES, VIS_PROTOTYPES, DATA_PROTOTYPES, PACK_PROTOTYPES, SWIN1_PROTOTYPES):
+    for table in (PROTOTYPES, VIS_PROTOTYPES, DATA_PROTOTYPES, PACK_PROTOTYPES, SWIN1_PROTOTYPES, OCC_VIEW_PROTOTYPES):
         for symbol, (restype, argtypes) in table.items():
             fn = getattr(L, symbol)
             fn.restype, fn.argtypes = restype, argtypes

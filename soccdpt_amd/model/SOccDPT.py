@@ -212,23 +212,57 @@ class SOccDPT(BaseModel):
         self.last_occ_frame_bits = frame_bits
         return occ
 
+    def _last_bits(self, frame, what: str) -> torch.Tensor:
+        """The packed grid of the last forward: the union (frame=None) or frame b's own row; RuntimeError when there is none."""
+        if frame is not None:
+            rows = self.last_occ_frame_bits
+            if not self.occupancy_per_frame or rows is None:
+                raise RuntimeError(f"{what}(frame=...) needs a forward of a model built with compute_occ=True and occupancy_per_frame=True")
+            return rows[int(frame)]
+        if self.last_occ_bits is None:
+            raise RuntimeError(f"{what}() needs a forward of a model built with compute_occ=True first")
+        return self.last_occ_bits
+
     def occupancy_points(self, class_2_color=None, frame=None):
         """The last forward's occupancy grid as the reference's point list (utils/__init__.py:532-568 occupancy_grid_to_points on occupancy[0]):
         float64 [N,4] rows (x, y, z, class_id) in metres, class-major, straight from the packed bits `last_occ_bits` -- no dense grid is read,
         so it works the same with share_occupancy_rows=True and under occ_exchange.  With class_2_color also the [N,3] u8 colours.
         frame=None lists the union grid; frame=b (a model built with occupancy_per_frame=True) lists frame b's own grid from `last_occ_frame_bits`."""
-        if frame is not None:
-            rows = self.last_occ_frame_bits
-            if not self.occupancy_per_frame or rows is None:
-                raise RuntimeError("occupancy_points(frame=...) needs a forward of a model built with compute_occ=True and occupancy_per_frame=True")
-            bits = rows[int(frame)]
-        else:
-            bits = self.last_occ_bits
-        if bits is None:
-            raise RuntimeError("occupancy_points() needs a forward of a model built with compute_occ=True first")
+        bits = self._last_bits(frame, "occupancy_points")
         from ..utils.occupancy import occupancy_bits_to_points
         res = occupancy_bits_to_points(bits, self.grid_size, self.scale, num_classes=self.num_classes, class_2_color=class_2_color)
         return res.points if class_2_color is None else (res.points, res.colors)
+
+    def voxel_to_camera(self) -> np.ndarray:
+        """3 x 4 float64: voxel-centre index (i + 0.5 per axis) of this model's grid -> camera coordinates in metres, composed on the host from the
+        model's own constants: the inverse of p . Ra . Rb . Rc followed by / occupancy_shape * grid_size (model/SOccDPT.py:374-463 of the reference).
+        The reference scales and shifts the first three POINTS of the cloud by pc_scale / pc_shift (an indexing quirk, :351-353, which the forward
+        path reproduces); those three points are ignored here: pc_scale and pc_shift do not enter the matrix."""
+        from ..lib import host_rotation_matrices
+        from ..utils.occupancy_views import model_voxel_to_camera
+        return model_voxel_to_camera(self.grid_size, self.occupancy_shape, host_rotation_matrices(self.correction_angle))
+
+    def occupancy_view(self, frame=None, class_2_color=None, **kw) -> torch.Tensor:
+        """utils.occupancy_views.bird_eye_view of the last forward's grid (`last_occ_bits`; frame=b: frame b's own grid, as in occupancy_points):
+        u8 [1, g2 * zoom, g0 * zoom, 3].  Keywords of occupancy_view (axis=, from_high=, flip=, transpose=, ...) replace the bird's-eye defaults."""
+        from ..utils.occupancy_views import BEV, occupancy_view
+        bits = self._last_bits(frame, "occupancy_view")
+        return occupancy_view(bits, self.grid_size, class_2_color or self._dataset_colors(), num_classes=self.num_classes, **{**BEV, **kw})
+
+    def occupancy_overlay(self, frames_bgr, frame=None, class_2_color=None, **kw) -> torch.Tensor:
+        """utils.occupancy_views.occupancy_overlay of the last forward's grid over camera frames u8 [H,W,3] / [1,H,W,3] (cuda), through
+        voxel_to_camera() and the model's intrinsics: u8 [1, H, W, 3].  frame= as in occupancy_points."""
+        from ..utils.occupancy_views import occupancy_overlay
+        bits = self._last_bits(frame, "occupancy_overlay")
+        return occupancy_overlay(bits, frames_bgr, self.voxel_to_camera(), (self.fx, self.fy, self.cx, self.cy), self.grid_size,
+                                 class_2_color or self._dataset_colors(), num_classes=self.num_classes, **kw)
+
+    def _dataset_colors(self):
+        """The Bengaluru dataset's class colours, the default of the two pictures above; other class counts have to bring their own."""
+        from ..datasets.bengaluru_driving_dataset import class_2_color
+        if self.num_classes != len(class_2_color):
+            raise ValueError(f"pass class_2_color: the default table has {len(class_2_color)} classes, the model {self.num_classes}")
+        return class_2_color
 
 
 class SOccDPT_V3(SOccDPT):

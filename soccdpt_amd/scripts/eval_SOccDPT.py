@@ -13,7 +13,7 @@ the CPU-free model output, so the numbers are meaningful only as a smoke/regress
 eval_SOccDPT.py:136-243 are opt-in (`--visuals [DIR]`, default off; see write_visuals); the FPS loop synchronises the stream before stopping the clock (the reference does
 not); metrics run on the GPU (soccdpt_amd.utils.metrics).  `-l/--load` may be omitted for random weights.
 
-    python -m soccdpt_amd.scripts.eval_SOccDPT -v 3 -dt bdd -t dpt_swin2_tiny_256 -d cuda:0 [-l ckpt.pth] [-o] [--visuals [DIR]]
+    python -m soccdpt_amd.scripts.eval_SOccDPT -v 3 -dt bdd -t dpt_swin2_tiny_256 -d cuda:0 [-l ckpt.pth] [-o] [--visuals [DIR]] [--occupancy-views [DIR]]
 """
 import argparse
 import os
@@ -56,12 +56,17 @@ def build_parser() -> argparse.ArgumentParser:
     parser.add_argument("--visuals", nargs="?", const=os.path.join("media", "visuals"), default=None, metavar="DIR", help="also write the reference's PNG "
                         "dumps of the validation frames (RGB, GT_Depth, GT_Seg, Pred_Depth, Pred_Seg) and the evaluation panel under "
                         "DIR/{model_type}_{dataset}_{version}/ (bare flag: media/visuals), coloured on the GPU")
+    parser.add_argument("--occupancy-views", dest="occupancy_views", nargs="?", const=os.path.join("media", "occupancy_views"), default=None, metavar="DIR",
+                        help="implies --occupancy; also write pictures of the occupancy grid of every validation frame under DIR/{Occ_BEV,Occ_Overlay,Occ_Panel}/ "
+                        "(bare flag: media/occupancy_views): the grid from above and over the camera frame, prediction left, ground truth right "
+                        "(the frame's own grid with --occupancy-per-frame), and print their mean 2-D IoU (BEV_IOU)")
     return parser
 
 
 # class -> colour of the 3-class bdd layout, in the channel order of the frames (datasets/bengaluru_driving_dataset.py:59-64)
 CLASS_2_COLOR_BDD = {0: (0, 0, 0), 1: (0, 0, 142), 2: (220, 20, 60)}
 VISUAL_DIRS = ("RGB", "GT_Depth", "GT_Seg", "Pred_Depth", "Pred_Seg", "Panel")
+OCCUPANCY_VIEW_DIRS = ("Occ_BEV", "Occ_Overlay", "Occ_Panel")
 
 
 def write_visuals(net, dataset, device, root: str, class_2_color=None) -> str:
@@ -103,6 +108,56 @@ def write_visuals(net, dataset, device, root: str, class_2_color=None) -> str:
         panel = evaluation_panel(frame, y_disp_pred, y_seg_pred[0], class_2_color, disp_gt=y_disp, seg_gt=y_seg[0])
         write_png(os.path.join(root, "Panel", f"{index:04d}.png"), panel)               # already R, G, B
     return root
+
+
+def write_occupancy_views(net, dataset, device, root: str, class_maps=None, class_2_color=None, point_count_threshold: float = 10.0) -> dict:
+    """Pictures of the occupancy grid for every frame of `dataset` (utils/occupancy_views.py, painted on the GPU; only the finished u8 pictures are
+    copied to the host for the PNG encoder): root/Occ_BEV/000N.png the grid from above, root/Occ_Overlay/000N.png the grid over the camera frame --
+    prediction left, ground truth right in both -- and root/Occ_Panel/000N.png the four of them in one picture.  The ground truth is the grid
+    evaluate_occupancy_set scores against; the prediction is frame 0's own grid for a model built with occupancy_per_frame=True, else the union
+    grid of the forward.  Returns dict(root, bev_iou): the mean over the frames of bev_iou(pred, gt)["iou_2D"].  Like write_visuals it runs every
+    frame through the model once more and leaves the metric loops as they are."""
+    from ..utils.gt_occupancy import OccupancyProcessor
+    from ..utils.occupancy import pack_occupancy
+    from ..utils.occupancy_views import _Rect, _grid_bits, _overlay_into, _table, _view_into, BEV, bev_iou, occupancy_panel, view_size
+    from ..utils.visualise import resize_bgr, write_png
+    class_2_color = class_2_color or CLASS_2_COLOR_BDD
+    for d in OCCUPANCY_VIEW_DIRS:
+        os.makedirs(os.path.join(root, d), exist_ok=True)
+    proc = OccupancyProcessor(intrinsic_matrix=net.intrinsic_matrix, height=net.height, width=net.width, grid_size=net.grid_size, scale=net.scale, shift=net.shift,
+                              pc_scale=net.pc_scale, pc_shift=net.pc_shift, point_count_threshold=point_count_threshold, num_classes=net.num_classes,
+                              correction_angle=net.correction_angle)
+    H, W, C = net.height, net.width, net.num_classes
+    M, K = net.voxel_to_camera(), np.array([net.fx, net.fy, net.cx, net.cy], dtype=np.float64)
+    zoom = 2
+    bh, bw = view_size(net.grid_size, zoom=zoom, axis=BEV["axis"], transpose=BEV["transpose"])
+    ious = []
+    for index, batch in enumerate(dataset):
+        x, x_raw, y_disp, y_seg = batch[0], batch[1], batch[3], batch[-1]
+        x = x.to(device=device, dtype=torch.float32)
+        seg_class = class_maps[index] if class_maps is not None else y_seg.to(device).argmax(dim=1)
+        gt = proc.process(y_disp.to(device=device, dtype=torch.float32), seg_class, want_points=False, want_depth=False)
+        net(x)
+        if x_raw is None:
+            rgb = ((x[0] * 0.5 + 0.5) * 255.0).clamp(0.0, 255.0).to(torch.uint8).permute(1, 2, 0)
+            frame = resize_bgr(rgb.flip(2).contiguous(), (W, H))
+        else:
+            frame = x_raw[0].to(device=device, dtype=torch.uint8)
+        pred_bits = net.last_occ_frame_bits[0] if getattr(net, "occupancy_per_frame", False) else net.last_occ_bits
+        gt_bits = pack_occupancy(gt["occupancy_grid"][0], 0.5)
+        table = _table(class_2_color, C, frame.device)
+        bev = torch.empty((bh, 2 * bw, 3), dtype=torch.uint8, device=frame.device)
+        overlay = torch.empty((H, 2 * W, 3), dtype=torch.uint8, device=frame.device)
+        for k, b in enumerate((pred_bits, gt_bits)):
+            bits, g = _grid_bits(b, net.grid_size, C, "write_occupancy_views")
+            _view_into(bits, g, C, table, BEV["axis"], BEV["from_high"], zoom, 128, (32, 32, 32), BEV["flip"], BEV["transpose"], _Rect.tile(bev, 0, k * bw))
+            _overlay_into(bits, g, C, frame.unsqueeze(0), H, W, M, K, table, 160, None, 12, 0.1, _Rect.tile(overlay, 0, k * W))
+        panel = occupancy_panel(frame, pred_bits, gt_bits, voxel_to_camera=M, intrinsics=K, grid_size=net.grid_size, class_2_color=class_2_color, num_classes=C)
+        write_png(os.path.join(root, "Occ_BEV", f"{index:04d}.png"), bev, bgr=True)
+        write_png(os.path.join(root, "Occ_Overlay", f"{index:04d}.png"), overlay, bgr=True)
+        write_png(os.path.join(root, "Occ_Panel", f"{index:04d}.png"), panel)              # already R, G, B
+        ious.append(bev_iou(pred_bits, gt_bits, net.grid_size, num_classes=C)["iou_2D"])
+    return dict(root=root, bev_iou=float(torch.cat(ious).mean().item()))
 
 
 def synthetic_val_set(net, device, img: int, n: int = 10):
@@ -161,7 +216,8 @@ def main(args) -> dict:
     calib = calib or write_synth_calib(os.path.join(tempfile.mkdtemp(), "calib.yaml"))
     model_kwargs = dict(num_classes=num_classes, camera_intrinsics_yaml=calib)
     per_frame = bool(getattr(args, "occupancy_per_frame", False))
-    occupancy = bool(getattr(args, "occupancy", False)) or per_frame
+    occupancy_views = getattr(args, "occupancy_views", None)
+    occupancy = bool(getattr(args, "occupancy", False)) or per_frame or bool(occupancy_views)
     if per_frame:
         model_kwargs.update(compute_occ=True, occupancy_per_frame=True)
     elif occupancy:
@@ -233,6 +289,10 @@ def main(args) -> dict:
     if getattr(args, "visuals", None):
         result["visuals"] = write_visuals(net, dataset, device, os.path.join(args.visuals, f"{args.model_type}_{args.dataset}_{args.version}"))
         print(f"VISUALS: {result['visuals']}")
+    if occupancy_views:
+        views = write_occupancy_views(net, dataset, device, occupancy_views, class_maps=class_maps)
+        result["occupancy_views"], result["bev_iou"] = views["root"], views["bev_iou"]
+        print(f"BEV_IOU: {result['bev_iou']:.4f}")
     if real_data:
         result["frames"] = picked
     print("=" * 20)

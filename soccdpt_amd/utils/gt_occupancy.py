@@ -8,7 +8,8 @@ visualisation (:491-521).  `rgb_seg_to_class` (colour -> class id, :10-25) is a 
 (csrc/batch_targets.hip, include/soccdpt_data.h) builds `seg_class` from the uint8 label frames of a batch, which is where `eval_SOccDPT --occupancy`
 takes it from on real recordings.  The `occupancy_points` list of transform_points_to_occupancy_grid_vect (:339-355)
 is available on request (`want_occupancy_points`, csrc/occ_eval.hip); the un-rotation / un-shift / un-scale that process_frame applies to it
-afterwards for drawing (:500-528, numpy matmuls on the host) is not."""
+afterwards for drawing (:500-528, numpy matmuls on the host) is `voxel_to_camera()`: one 3 x 4 matrix that utils/occupancy_views.py hands to the
+overlay kernels, which draw the cells over the camera frame without a point list."""
 from __future__ import annotations
 
 import ctypes
@@ -40,13 +41,19 @@ class OccupancyProcessor:
         Rc = np.array([[math.cos(c), -math.sin(c), 0], [math.sin(c), math.cos(c), 0], [0, 0, 1]])
         self._rot = np.concatenate([Ra.T.reshape(-1), Rb.T.reshape(-1), Rc.T.reshape(-1)]).astype(np.float64)
 
+    def voxel_to_camera(self) -> np.ndarray:
+        """3 x 4 float64: voxel-centre index (i + 0.5 per axis) of this generator's grid -> camera coordinates in metres: the inverse of scale
+        (pc_scale), shift (pc_shift), rotate and / occupancy_shape * grid_size -- what process_frame undoes for drawing (bdd_helper.py:500-524)."""
+        from .occupancy_views import processor_voxel_to_camera
+        return processor_voxel_to_camera(self.grid_size, self.occupancy_shape, self.pc_scale, self.pc_shift, self._rot)
+
     def process(self, disparity: torch.Tensor, seg_class: torch.Tensor, want_points: bool = True, want_depth: bool = True,
                 want_occupancy_points: bool = False) -> Dict[str, Optional[torch.Tensor]]:
         """disparity [B,H,W] (or [H,W]) float, seg_class same shape integer class ids, both cuda ->
         depth [B,H,W] f32, points [B,H*W,3] f64, occupancy_grid [B,g0,g1,g2,C] bool, counts [B,g0,g1,g2,C] int32.
         want_occupancy_points adds `occupancy_points`: a list of B float64 [N_b,4] tensors (x, y, z, class_id), the value
         transform_points_to_occupancy_grid_vect returns under that key (cells with counts >= point_count_threshold, class-major; bdd_helper.py:339-355),
-        built on the GPU from `counts`.  process_frame's later un-rotate / un-shift / un-scale of that list (:500-528, drawing only) is out of scope."""
+        built on the GPU from `counts`.  process_frame's later un-rotate / un-shift / un-scale of that list (:500-528, drawing only) is not applied to it: voxel_to_camera() is that mapping."""
         assert disparity.is_cuda, "the HIP path needs cuda tensors (no CPU fallback)"
         if disparity.dim() == 2:
             disparity, seg_class = disparity.unsqueeze(0), seg_class.unsqueeze(0)

@@ -197,3 +197,22 @@ def evaluate_occupancy(net, val_set, device, amp, x_raw, y_occupancy_grid, y_occ
     print("loss: {}".format(loss))
     experiment.log(log)
     return log
+
+
+def occupancy_pictures(net, x_raw, y_occupancy_grid, y_occupancy_grid_pred, class_2_color) -> dict:
+    """The picture evaluate_occupancy's log lacks: {"plot_occupancy": u8 RGB numpy array}, utils.occupancy_views.occupancy_panel of sample 0 --
+    predicted | ground-truth grid over the camera frame, above both grids seen from above.  Same x_raw / grid arguments as evaluate_occupancy
+    (dense [B,g0,g1,g2,C] or [g0,g1,g2,C], or packed rows); `net` supplies the geometry: grid_size, intrinsics and voxel_to_camera().  Callers merge
+    the dict into their log; evaluate_occupancy itself logs what the reference logs."""
+    from .occupancy_views import occupancy_panel
+
+    def first(t, dev):     # one grid: row 0 of a batch of dense grids or of packed rows
+        t = t.detach().to(dev)
+        return t[0] if t.dim() in (2, 5) else t
+
+    frame_bgr = x_raw[0].detach().squeeze()
+    dev = y_occupancy_grid_pred.device
+    frame_bgr = frame_bgr.to(device=dev, dtype=torch.uint8)
+    panel = occupancy_panel(frame_bgr, first(y_occupancy_grid_pred, dev), first(y_occupancy_grid, dev), voxel_to_camera=net.voxel_to_camera(),
+                            intrinsics=(net.fx, net.fy, net.cx, net.cy), grid_size=net.grid_size, class_2_color=class_2_color, num_classes=net.num_classes)
+    return {"plot_occupancy": panel.cpu().numpy()}
