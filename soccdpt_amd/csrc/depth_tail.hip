@@ -4,8 +4,10 @@
 // The unfused form writes and re-reads a 134 MB up-sampled bf16 image (B=8) and, as an implicit GEMM with N = 32,
 // stages every input pixel 9 times for only 32 output channels (25 FLOP per staged byte).  Here a persistent
 // workgroup keeps the 32 x 1152 weight matrix in REGISTERS (each wave its 16 channels as 36 MFMA fragments), builds the (8+2) x (16+2) up-sampled halo patch of
-// each 8 x 16 output tile directly from the low-resolution map (4 x 16-byte loads + lerp per 8 channels), and runs
-// the 9 taps x 4 k-steps of v_mfma_f32_16x16x32_bf16 out of LDS: no up-sampled image in HBM, ~12x fewer staged bytes.
+// each 8 x 16 output tile directly from the low-resolution map (separably: a thread walks down a patch column and lerps each source row once per 8 channels), and
+// runs the 9 taps x 4 k-steps of v_mfma_f32_16x16x32_bf16 out of LDS: no up-sampled image in HBM, ~12x fewer staged bytes.
+#include <type_traits>
+
 #include "half16.h"
 #include "kernels.h"
 
@@ -28,6 +30,21 @@ constexpr int LDS_BYTES = 2 * P_BYTES + 2 * S_BYTES + T_BYTES + R_BYTES;  // 148
 constexpr int NTHR = 512;                      // 8 waves: one output row of the 8 x 16 tile each
 }  // namespace
 
+// two f32 -> one packed pair of 16-bit operands: pack_h2's clamp and rounding (half16.h), as ONE conversion of the pair
+template <bool F16>
+__device__ __forceinline__ uint32_t pack_pair(float a, float b) {
+    typedef __attribute__((ext_vector_type(2))) float f32x2;
+    if constexpr (F16) {
+        typedef __attribute__((ext_vector_type(2))) _Float16 f16x2;
+        const f32x2 v = {__builtin_amdgcn_fmed3f(a, -65504.f, 65504.f), __builtin_amdgcn_fmed3f(b, -65504.f, 65504.f)};
+        return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, f16x2));
+    } else {
+        typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
+        const f32x2 v = {a, b};
+        return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, bf16x2));
+    }
+}
+
 // d1: 16-bit [B][h][w][128] plain NHWC; wt: 16-bit [32][9*128] tap-major; out: f32 [B][2h][2w].  F16: operands are fp16, else bf16.
 //
 // Round 6 (profiles/r06*_pmc_stall.json: 45 % of the wave cycles of this kernel issue VALU work -- the bilinear build of the patch, ~820
@@ -35,6 +52,13 @@ constexpr int NTHR = 512;                      // 8 waves: one output row of the
 // the patch is double-buffered and a tile's MFMAs run in the same barrier interval as the build of the NEXT tile's patch; the two waves of a SIMD take
 // the two phases in opposite order (waves 0-3 build first, waves 4-7 multiply first), so a SIMD always has one wave for its VALU and one for its
 // matrix core.  Two barriers per tile instead of four.
+//
+// Separable build (profiles/r13_ab_depth_tail_build.txt): the build computed every patch pixel from its four source pixels, ~110 VALU instructions per (pixel, 8-channel chunk): each source
+// value converted to f32 about nine times, 360 horizontal lerps per chunk and tile where 126 distinct ones exist (the scale is ~1/2: a source row serves about
+// three patch rows).  Now a thread owns a patch column and a chunk, walks down a run of patch rows and holds the horizontal lerps T of the current and the next
+// source row (build_rows below): ~21 instructions per pixel plus ~50 per new source row, SQ_INSTS_VALU per launch 27.5 M -> 19.6 M, the same bits (the
+// operations and their order are those the compiler had chosen for the one-expression form).  With the build cheaper the multiply's own waiting showed -- it read
+// two fragments, waited, issued their MFMAs, 24 times per tile -- and its reads now run three groups ahead (multiply below).  91.8 -> 75.5 us in the network.
 template <bool F16>
 __global__ __launch_bounds__(512) void depth_tail_kernel(const bf16_t* __restrict__ d1, const bf16_t* __restrict__ wt, const float* __restrict__ bias,
                                                           const float* __restrict__ w4, float b4, float* __restrict__ out, int B, int h, int w) {
@@ -44,6 +68,7 @@ __global__ __launch_bounds__(512) void depth_tail_kernel(const bf16_t* __restric
     int* Ti = reinterpret_cast<int*>(smem + 2 * P_BYTES + 2 * S_BYTES);  // [0..9] row: src offset (bytes) of the upper row | valid<<30 ; [32..49] col
     float* Tf = reinterpret_cast<float*>(Ti) + 64;                          // [0..9] ly ; [32..49] lx
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int swave = __builtin_amdgcn_readfirstlane(wave);  // the same number where the compiler can see that it is wave-uniform (the build's row ranges)
     const int H = 2 * h, W = 2 * w;
     const int tiles_x = W / TW, tiles_y = H / TH;
     const int ntiles = B * tiles_y * tiles_x;
@@ -87,50 +112,105 @@ __global__ __launch_bounds__(512) void depth_tail_kernel(const bf16_t* __restric
         const int Yc0 = y0 < 0 ? 0 : y0, Xc0 = x0 < 0 ? 0 : x0;
         const int sy0 = (int)(sy * (float)Yc0), sx0 = (int)(sx * (float)Xc0);  // first source row / column any patch pixel touches
         if (tid < PH) {  // rows: byte offset of source row yy0 inside the window, step to yy1, weight
+            // (offset 0 outside the image: a negative one would set the `valid` bit through its sign extension)
             const int Y = y0 + tid;
             const bool ok = Y >= 0 && Y < H;
             const float fy = sy * (float)(ok ? Y : 0);
             const int yy0 = (int)fy;
-            Ti[tid] = ((yy0 - sy0) * SRW * S_ROWB) | ((yy0 < h - 1) ? (1 << 28) : 0) | (ok ? (1 << 30) : 0);
+            Ti[tid] = ((ok ? yy0 - sy0 : 0) * SRW * S_ROWB) | ((yy0 < h - 1) ? (1 << 28) : 0) | (ok ? (1 << 30) : 0);
             Tf[tid] = fy - (float)yy0;
         } else if (tid >= 32 && tid < 32 + PW) {
             const int X = x0 + tid - 32;
             const bool ok = X >= 0 && X < W;
             const float fx = sx * (float)(ok ? X : 0);
             const int xx0 = (int)fx;
-            Ti[tid] = ((xx0 - sx0) * S_ROWB) | ((xx0 < w - 1) ? (1 << 28) : 0) | (ok ? (1 << 30) : 0);
+            Ti[tid] = ((ok ? xx0 - sx0 : 0) * S_ROWB) | ((xx0 < w - 1) ? (1 << 28) : 0) | (ok ? (1 << 30) : 0);
             Tf[tid] = fx - (float)xx0;
         }
     };
-    // the up-sampled halo patch from a staged window: thread = fixed 8-channel chunk, strided pixels
-    auto build = [&](const char* Ss, char* Ps) {
+    // Patch rows r0 .. r0+n-1 (n <= N) of patch column `col`, this thread's 8-channel chunk, walking down.  T(r) = fma(hx, S(r, x0), lx * S(r, x1)), the
+    // horizontal lerp of source row r at this column, is held for the upper source row of the current patch row and for the row below it (TU, TL); a pixel is
+    // fma(hy, TU, ly * TL).  When the walk reaches the next source row (the scale is < 1/2: never more than one row further) TL becomes TU and ONE new T is
+    // computed, from window chunks that were requested when the previous T was (a0, a1: always one source row ahead, so their LDS latency passes behind the
+    // pixels in between).  At the last source row the table's row step is 0 and the lower row is the upper row: the window holds a copy of row h-1 below
+    // row h-1 (issue_window clamps), so the T of "the row below" is that same T, bit for bit, and serves both roles.  The last column likewise takes x1 = x0
+    // from the table's column step.
+    // The products and fmas are spelt out: this file compiles with the default contraction, and these are the operations it chose for the one-expression
+    // form `hy * (hx * a + lx * b) + ly * (hx * c + lx * d)` of the build before it, so the patch has the same bits.
+    // Every lane of a wave walks the SAME rows (r0 and n are wave-uniform), so the row table's entries are read once into scalar registers and the walk is
+    // steered by scalar branches; only the column's validity is per lane (an invalid column has offset 0: its reads stay inside the window).
+    auto build_rows = [&](const char* Ss, char* Ps, int col, int r0, int n, auto nmax) {
+        constexpr int N = decltype(nmax)::value;
+        constexpr int RS = SRW * S_ROWB;  // one source row down in the window
         const int ch = tid & 15;
-        const char* sb = Ss + ch * 16;
-        for (int p = tid >> 4; p < PH * PW; p += NTHR / 16) {
-            const int py = p / PW, px = p - py * PW;
-            const int ty_ = Ti[py], tx_ = Ti[32 + px];
-            uint4 o = make_uint4(0, 0, 0, 0);  // conv zero padding outside the image
-            if ((ty_ & tx_) >> 30) {
-                const float ly = Tf[py], lx = Tf[32 + px], hy = 1.f - ly, hx = 1.f - lx;
-                const int o00 = (ty_ & 0xfffffff) + (tx_ & 0xfffffff);
-                const int dyo = ((ty_ >> 28) & 1) * SRW * S_ROWB, dxo = ((tx_ >> 28) & 1) * S_ROWB;
-                const uint4 a00 = *reinterpret_cast<const uint4*>(sb + o00);
-                const uint4 a01 = *reinterpret_cast<const uint4*>(sb + o00 + dxo);
-                const uint4 a10 = *reinterpret_cast<const uint4*>(sb + o00 + dyo);
-                const uint4 a11 = *reinterpret_cast<const uint4*>(sb + o00 + dyo + dxo);
-                const uint32_t u00[4] = {a00.x, a00.y, a00.z, a00.w}, u01[4] = {a01.x, a01.y, a01.z, a01.w};
-                const uint32_t u10[4] = {a10.x, a10.y, a10.z, a10.w}, u11[4] = {a11.x, a11.y, a11.z, a11.w};
-                uint32_t ov[4];
+        char* pb = Ps + (r0 * PW + col) * P_ROWB + ch * 16;
+        const int tx_ = Ti[32 + col];
+        const float lx = Tf[32 + col], hx = 1.f - lx;
+        const char* s0 = Ss + ch * 16 + (tx_ & 0xfffffff);
+        const char* s1 = s0 + ((tx_ >> 28) & 1) * S_ROWB;
+        const bool colok = (tx_ >> 30) & 1;
+        int ty_[N];
+        float ly_[N];
 #pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const float lo = hy * (hx * h_lo<F16>(u00[j]) + lx * h_lo<F16>(u01[j])) + ly * (hx * h_lo<F16>(u10[j]) + lx * h_lo<F16>(u11[j]));
-                    const float hi = hy * (hx * h_hi<F16>(u00[j]) + lx * h_hi<F16>(u01[j])) + ly * (hx * h_hi<F16>(u10[j]) + lx * h_hi<F16>(u11[j]));
-                    ov[j] = pack_h2<F16>(lo, hi);
-                }
-                o = make_uint4(ov[0], ov[1], ov[2], ov[3]);
-            }
-            *reinterpret_cast<uint4*>(Ps + p * P_ROWB + ch * 16) = o;
+        for (int i = 0; i < N; ++i) {  // (entries past row 9 are other words of the table: never used, i < n)
+            ty_[i] = Ti[r0 + i];
+            ly_[i] = Tf[r0 + i];
         }
+#pragma unroll
+        for (int i = 0; i < N; ++i) {
+            ty_[i] = __builtin_amdgcn_readfirstlane(ty_[i]);
+            ly_[i] = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, ly_[i])));
+        }
+        auto hlerp = [&](const uint4& a0, const uint4& a1, float (&T)[8]) {
+            const uint32_t u0[4] = {a0.x, a0.y, a0.z, a0.w}, u1[4] = {a1.x, a1.y, a1.z, a1.w};
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const float tl = lx * h_lo<F16>(u1[j]), th = lx * h_hi<F16>(u1[j]);
+                T[2 * j] = __builtin_fmaf(hx, h_lo<F16>(u0[j]), tl);
+                T[2 * j + 1] = __builtin_fmaf(hx, h_hi<F16>(u0[j]), th);
+            }
+        };
+        // only patch rows 0 and 9 can lie outside the image and a run has two rows or more: its first or its second row is inside
+        int cur = ((ty_[0] >> 30) & 1) ? (ty_[0] & 0xfffffff) : (ty_[1] & 0xfffffff);
+        uint4 a0 = *reinterpret_cast<const uint4*>(s0 + cur), a1 = *reinterpret_cast<const uint4*>(s1 + cur);
+        const uint4 b0 = *reinterpret_cast<const uint4*>(s0 + cur + RS), b1 = *reinterpret_cast<const uint4*>(s1 + cur + RS);
+        float TU[8], TL[8];
+        hlerp(a0, a1, TU);
+        hlerp(b0, b1, TL);
+        a0 = *reinterpret_cast<const uint4*>(s0 + cur + 2 * RS);
+        a1 = *reinterpret_cast<const uint4*>(s1 + cur + 2 * RS);
+#pragma unroll
+        for (int i = 0; i < N; ++i) {
+            if (i < n) {
+                uint4 o = make_uint4(0, 0, 0, 0);  // conv zero padding outside the image
+                if ((ty_[i] >> 30) & 1) {
+                    const float ly = ly_[i], hy = 1.f - ly;
+                    if ((ty_[i] & 0xfffffff) != cur) {
+                        cur = ty_[i] & 0xfffffff;
+#pragma unroll
+                        for (int j = 0; j < 8; ++j) TU[j] = TL[j];
+                        hlerp(a0, a1, TL);
+                        a0 = *reinterpret_cast<const uint4*>(s0 + cur + 2 * RS);
+                        a1 = *reinterpret_cast<const uint4*>(s1 + cur + 2 * RS);
+                    }
+                    uint32_t ov[4];
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) {
+                        const float tl = ly * TL[2 * j], th = ly * TL[2 * j + 1];
+                        ov[j] = pack_pair<F16>(__builtin_fmaf(hy, TU[2 * j], tl), __builtin_fmaf(hy, TU[2 * j + 1], th));
+                    }
+                    if (colok) o = make_uint4(ov[0], ov[1], ov[2], ov[3]);
+                }
+                *reinterpret_cast<uint4*>(pb + i * (PW * P_ROWB)) = o;
+            }
+        }
+    };
+    // the up-sampled halo patch from a staged window.  18 columns x 16 chunks fill four and a half waves.  Columns 0-15: wave = 4 columns x 16 chunks over the
+    // upper (waves 0-3) or the lower (waves 4-7) five patch rows.  Columns 16-17: half a wave each for rows 0-2, 3-4, 5-7 and 8-9, on waves 0-3 -- the waves
+    // that build before they multiply.  A run of rows pays one extra T where it starts.
+    auto build = [&](const char* Ss, char* Ps) {
+        build_rows(Ss, Ps, (swave & 3) * 4 + (lane >> 4), (swave >> 2) * 5, 5, std::integral_constant<int, 5>{});
+        if (swave < 4 && lane < 32) build_rows(Ss, Ps, 16 + (lane >> 4), (swave >> 1) * 5 + (swave & 1) * 3, 3 - (swave & 1), std::integral_constant<int, 3>{});
     };
     // 9 taps x 4 k-steps: wave = 2 output rows x 16 channels, weights from registers, patch rows from LDS
     f32x4 acc[2];
@@ -138,18 +218,32 @@ __global__ __launch_bounds__(512) void depth_tail_kernel(const bf16_t* __restric
         acc[0] = f32x4{0.f, 0.f, 0.f, 0.f};
         acc[1] = f32x4{0.f, 0.f, 0.f, 0.f};
         // by PATCH row m = 0..3 of the wave's two output rows: row m feeds output row 0 as tap row ky = m and output row 1 as ky = m - 1, so its fragments are
-        // read once for both (48 ds_read_b128 per tile and wave instead of 72; each accumulator still sees its taps in (ky, kx, ks) order: same bits)
+        // read once for both (48 ds_read_b128 per tile and wave instead of 72; each accumulator still sees its taps in (ky, kx, ks) order: same bits).
+        // The twelve (m, kx) groups of four fragments are read DEPTH groups ahead of their MFMAs: left to itself the compiler, short of registers beside the
+        // 144 of the weights, read two fragments, waited for them and issued their MFMAs, 24 LDS round trips in a row per tile, and a wave spent most of the
+        // multiply waiting with nothing else to issue.  The scheduling barriers keep the reads where they are written; the MFMAs of an accumulator and
+        // their order are unchanged.
+        constexpr int DEPTH = 3;
+        h16x8 xf[DEPTH][4];
+        auto read_group = [&](int g, h16x8 (&d)[4]) {
+            const int prow = (2 * rowpair + g / 3) * PW + frow + g % 3;
 #pragma unroll
-        for (int m = 0; m < 4; ++m) {
+            for (int ks = 0; ks < 4; ++ks) d[ks] = *reinterpret_cast<const h16x8*>(Ps + prow * P_ROWB + (ks * 32 + fq * 8) * 2);
+        };
 #pragma unroll
-            for (int kx = 0; kx < 3; ++kx) {
+        for (int g = 0; g < DEPTH; ++g) read_group(g, xf[g]);
+        __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-                for (int ks = 0; ks < 4; ++ks) {
-                    const int prow = (2 * rowpair + m) * PW + frow + kx;
-                    const h16x8 xf = *reinterpret_cast<const h16x8*>(Ps + prow * P_ROWB + (ks * 32 + fq * 8) * 2);
-                    if (m <= 2) acc[0] = mfma_16x16x32<F16>(wf[(m * 3 + kx) * 4 + ks], xf, acc[0]);
-                    if (m >= 1) acc[1] = mfma_16x16x32<F16>(wf[((m - 1) * 3 + kx) * 4 + ks], xf, acc[1]);
-                }
+        for (int g = 0; g < 12; ++g) {
+            const int m = g / 3, kx = g % 3;
+#pragma unroll
+            for (int ks = 0; ks < 4; ++ks) {
+                if (m <= 2) acc[0] = mfma_16x16x32<F16>(wf[(m * 3 + kx) * 4 + ks], xf[g % DEPTH][ks], acc[0]);
+                if (m >= 1) acc[1] = mfma_16x16x32<F16>(wf[((m - 1) * 3 + kx) * 4 + ks], xf[g % DEPTH][ks], acc[1]);
+            }
+            if (g + DEPTH < 12) {
+                read_group(g + DEPTH, xf[g % DEPTH]);
+                __builtin_amdgcn_sched_barrier(0);
             }
         }
     };
