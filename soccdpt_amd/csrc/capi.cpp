@@ -11,9 +11,11 @@
 #include "kernels.h"
 #include "occ_eval.h"
 #include "visualise.h"
+#include "occ_rays.h"
 #include "occ_view.h"
 #include "batch_targets.h"
 #include "../../include/soccdpt_vis.h"
+#include "../../include/soccdpt_occ_rays.h"
 #include "../../include/soccdpt_occ_view.h"
 #include "../../include/soccdpt_data.h"
 
@@ -1073,6 +1075,26 @@ int soccdpt_occ_view_resolve(const uint64_t* dev_zbuf, const uint8_t* dev_frames
     std::string err;
     const VisDst d{dst_pitch_px, dst_offset_px, dst_frame_px, dst_total_px};
     if (launch_occ_view_resolve(dev_zbuf, dev_frames, frame_rows, rows, H, W, C, dev_class_colors, alpha, dev_dst, d, (hipStream_t)stream, err))
+        return fail(nullptr, "soccdpt_" + err);
+    return 0;
+}
+
+// ---- observed space by ray casting, and the 3-D IoU over it (include/soccdpt_occ_rays.h; csrc/occ_rays.hip) ----
+int soccdpt_occ_rays_observed(const float* dev_depth, int rows, int H, int W, const int32_t* host_grid, const double* host_camera_to_voxel,
+                              const double* host_intrinsics, double z_near, double max_depth, int step, int clear, uint32_t* dev_mask, void* stream) {
+    std::string err;
+    if (launch_occ_rays_observed(dev_depth, rows, H, W, host_grid, host_camera_to_voxel, host_intrinsics, z_near, max_depth, step, clear, dev_mask,
+                                 (hipStream_t)stream, err))
+        return fail(nullptr, "soccdpt_" + err);
+    return 0;
+}
+
+int soccdpt_occ_iou_counts_masked(const uint32_t* dev_pred_bits, int pred_rows, const uint32_t* dev_gt_bits, int rows, size_t nvox, int C,
+                                  const uint32_t* dev_mask, int mask_rows, int include_gt, uint64_t* dev_counts, uint64_t* dev_observed,
+                                  void* stream) {
+    std::string err;
+    if (launch_occ_iou_counts_masked(dev_pred_bits, pred_rows, dev_gt_bits, rows, nvox, C, dev_mask, mask_rows, include_gt, dev_counts, dev_observed,
+                                     (hipStream_t)stream, err))
         return fail(nullptr, "soccdpt_" + err);
     return 0;
 }

@@ -363,6 +363,20 @@ def _occ_view_prototypes() -> dict:
 
 
 OCC_VIEW_PROTOTYPES = _occ_view_prototypes()
+
+
+def _occ_rays_prototypes() -> dict:
+    """The same table for include/soccdpt_occ_rays.h (observed space by ray casting and the 3-D IoU over it, csrc/occ_rays.hip), in that header's
+    order; tests/test_occ_rays_cpu.py holds it against the header.  A seventh header and a seventh table: soccdpt_hip.h and its ABI version do not change."""
+    vp, ci, cs, cd = ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t, ctypes.c_double
+    i32, f64 = ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(cd)
+    return {
+        "soccdpt_occ_rays_observed": (ci, [vp, ci, ci, ci, i32, f64, f64, cd, cd, ci, ci, vp, vp]),
+        "soccdpt_occ_iou_counts_masked": (ci, [vp, ci, vp, ci, cs, ci, vp, ci, ci, vp, vp, vp]),
+    }
+
+
+OCC_RAYS_PROTOTYPES = _occ_rays_prototypes()
 PACK_INDEX_BITS = (1, 2, 4, 8)   # k of include/soccdpt_pack.h
 
 
@@ -376,7 +390,7 @@ def load_library() -> ctypes.CDLL:
             f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "(make -C soccdpt_amd/csrc).  The SOccDPT MI355X path has no CPU fallback.")
     L = ctypes.CDLL(LIB_PATH)
-    for table in (PROTOTYPES, VIS_PROTOTYPES, DATA_PROTOTYPES, PACK_PROTOTYPES, SWIN1_PROTOTYPES, OCC_VIEW_PROTOTYPES):
+    for table in (PROTOTYPES, VIS_PROTOTYPES, DATA_PROTOTYPES, PACK_PROTOTYPES, SWIN1_PROTOTYPES, OCC_VIEW_PROTOTYPES, OCC_RAYS_PROTOTYPES):
         for symbol, (restype, argtypes) in table.items():
             fn = getattr(L, symbol)
             fn.restype, fn.argtypes = restype, argtypes

@@ -257,6 +257,13 @@ class SOccDPT(BaseModel):
         return occupancy_overlay(bits, frames_bgr, self.voxel_to_camera(), (self.fx, self.fy, self.cx, self.cy), self.grid_size,
                                  class_2_color or self._dataset_colors(), num_classes=self.num_classes, **kw)
 
+    def observed_voxels(self, depth, **kw) -> torch.Tensor:
+        """utils.occupancy_rays.observed_voxels of a depth map [B,H,W] in camera metres (cuda) through voxel_to_camera() and the model's intrinsics:
+        the voxel mask int32 [B, ceil(g0 g1 g2 / 32)] of the space a camera with that depth map saw in this model's grid, for
+        occupancy_iou_observed / apply_observed.  Keywords: z_near=, max_depth=, step=, out=."""
+        from ..utils.occupancy_rays import observed_voxels
+        return observed_voxels(depth, self.voxel_to_camera(), (self.fx, self.fy, self.cx, self.cy), self.grid_size, **kw)
+
     def _dataset_colors(self):
         """The Bengaluru dataset's class colours, the default of the two pictures above; other class counts have to bring their own."""
         from ..datasets.bengaluru_driving_dataset import class_2_color

@@ -13,7 +13,7 @@ the CPU-free model output, so the numbers are meaningful only as a smoke/regress
 eval_SOccDPT.py:136-243 are opt-in (`--visuals [DIR]`, default off; see write_visuals); the FPS loop synchronises the stream before stopping the clock (the reference does
 not); metrics run on the GPU (soccdpt_amd.utils.metrics).  `-l/--load` may be omitted for random weights.
 
-    python -m soccdpt_amd.scripts.eval_SOccDPT -v 3 -dt bdd -t dpt_swin2_tiny_256 -d cuda:0 [-l ckpt.pth] [-o] [--visuals [DIR]] [--occupancy-views [DIR]]
+    python -m soccdpt_amd.scripts.eval_SOccDPT -v 3 -dt bdd -t dpt_swin2_tiny_256 -d cuda:0 [-l ckpt.pth] [-o] [--visuals [DIR]] [--occupancy-views [DIR]] [--occupancy-observed]
 """
 import argparse
 import os
@@ -53,6 +53,9 @@ def build_parser() -> argparse.ArgumentParser:
     parser.add_argument("--occupancy-per-frame", dest="occupancy_per_frame", action="store_true", help="implies --occupancy, with the model built with "
                         "occupancy_per_frame=True: every frame's own grid (not the union over the batch) is scored against that frame's ground truth, "
                         "and OCC_POINTS is the mean point-list length per frame")
+    parser.add_argument("--occupancy-observed", dest="occupancy_observed", action="store_true", help="implies --occupancy; also score the grid over observed "
+                        "space only: the voxels the rays of the ground truth's depth map cross, plus its occupied voxels (prints IOU_3D_OBSERVED / "
+                        "OBSERVED_FRACTION beside the unchanged IOU_3D)")
     parser.add_argument("--visuals", nargs="?", const=os.path.join("media", "visuals"), default=None, metavar="DIR", help="also write the reference's PNG "
                         "dumps of the validation frames (RGB, GT_Depth, GT_Seg, Pred_Depth, Pred_Seg) and the evaluation panel under "
                         "DIR/{model_type}_{dataset}_{version}/ (bare flag: media/visuals), coloured on the GPU")
@@ -217,7 +220,8 @@ def main(args) -> dict:
     model_kwargs = dict(num_classes=num_classes, camera_intrinsics_yaml=calib)
     per_frame = bool(getattr(args, "occupancy_per_frame", False))
     occupancy_views = getattr(args, "occupancy_views", None)
-    occupancy = bool(getattr(args, "occupancy", False)) or per_frame or bool(occupancy_views)
+    occupancy_observed = bool(getattr(args, "occupancy_observed", False))
+    occupancy = bool(getattr(args, "occupancy", False)) or per_frame or bool(occupancy_views) or occupancy_observed
     if per_frame:
         model_kwargs.update(compute_occ=True, occupancy_per_frame=True)
     elif occupancy:
@@ -283,8 +287,14 @@ def main(args) -> dict:
     print(f"A3: {a3:.4f}")
     result = dict(fps=fps, iou=iou, abs_rel=abs_rel, sq_rel=sq_rel, rmse=rmse, rmse_log=rmse_log, a1=a1, a2=a2, a3=a3)
     if occupancy:
-        result.update(evaluate_occupancy_set(net, dataset, device, class_maps=class_maps))
+        if occupancy_observed:
+            result.update(evaluate_occupancy_set(net, dataset, device, class_maps=class_maps, observed=True))
+        else:
+            result.update(evaluate_occupancy_set(net, dataset, device, class_maps=class_maps))
         print(f"IOU_3D: {result['iou_3D']:.4f}")
+        if occupancy_observed:
+            print(f"IOU_3D_OBSERVED: {result['iou_3D_observed']:.4f}")
+            print(f"OBSERVED_FRACTION: {result['observed_fraction']:.4f}")
         print(f"OCC_POINTS: {result['occ_points']:.1f}")
     if getattr(args, "visuals", None):
         result["visuals"] = write_visuals(net, dataset, device, os.path.join(args.visuals, f"{args.model_type}_{args.dataset}_{args.version}"))
@@ -299,31 +309,42 @@ def main(args) -> dict:
     return result
 
 
-def evaluate_occupancy_set(net, dataset, device, point_count_threshold: float = 10.0, class_maps=None) -> dict:
+def evaluate_occupancy_set(net, dataset, device, point_count_threshold: float = 10.0, class_maps=None, observed: bool = False) -> dict:
     """Mean 3-D IoU of the model's occupancy grid (packed bits of each forward) against the ground-truth grid OccupancyProcessor builds from the
     sample's (y_disp, class ids: class_maps[i] when given -- the recordings' class maps from soccdpt_data_targets --, else argmax y_seg), and the mean length of the model's occupancy point list -- everything on the GPU.  A model built with
     occupancy_per_frame=True is scored row by row: frame b's own grid (net.last_occ_frame_bits[b]) against ground-truth row b, and the list length
-    is the mean over the frames; otherwise the one union grid of each forward is scored against every ground-truth row of its batch."""
+    is the mean over the frames; otherwise the one union grid of each forward is scored against every ground-truth row of its batch.
+    observed=True adds iou_3D_observed and observed_fraction: the same comparison over only the voxels the ground truth's camera saw -- the rays of the
+    generator's own `depth` through the grid (utils/occupancy_rays.py), plus the ground truth's occupied voxels; iou_3D itself does not change."""
     from ..utils.gt_occupancy import OccupancyProcessor
     from ..utils.occupancy import occupancy_iou
+    from ..utils.occupancy_rays import occupancy_iou_observed
     proc = OccupancyProcessor(intrinsic_matrix=net.intrinsic_matrix, height=net.height, width=net.width, grid_size=net.grid_size, scale=net.scale, shift=net.shift,
                               pc_scale=net.pc_scale, pc_shift=net.pc_shift, point_count_threshold=point_count_threshold, num_classes=net.num_classes,
                               correction_angle=net.correction_angle)
-    ious, lengths = [], []
+    ious, lengths, ious_obs, fractions = [], [], [], []
     for i, batch in enumerate(dataset):
         x, y_disp, y_seg = batch[0], batch[3], batch[-1]
         x = x.to(device=device, dtype=torch.float32)
         seg_class = class_maps[i] if class_maps is not None else y_seg.to(device).argmax(dim=1)
-        gt = proc.process(y_disp.to(device=device, dtype=torch.float32), seg_class, want_points=False, want_depth=False)
+        gt = proc.process(y_disp.to(device=device, dtype=torch.float32), seg_class, want_points=False, want_depth=False, want_observed=observed)
         net(x)
         if getattr(net, "occupancy_per_frame", False):
-            rows = net.last_occ_frame_bits
+            pred = rows = net.last_occ_frame_bits
             ious.append(occupancy_iou(rows, gt["occupancy_grid"], num_classes=net.num_classes)["iou_3D"])
             lengths.extend(net.occupancy_points(frame=b).shape[0] for b in range(rows.shape[0]))
         else:
+            pred = net.last_occ_bits
             ious.append(occupancy_iou(net.last_occ_bits, gt["occupancy_grid"], num_classes=net.num_classes)["iou_3D"])
             lengths.append(net.occupancy_points().shape[0])
-    return dict(iou_3D=float(torch.cat(ious).mean().item()), occ_points=float(np.mean(lengths)))
+        if observed:
+            res = occupancy_iou_observed(pred, gt["occupancy_grid"], gt["observed"], num_classes=net.num_classes)
+            ious_obs.append(res["iou_3D"])
+            fractions.append(res["observed_fraction"])
+    out = dict(iou_3D=float(torch.cat(ious).mean().item()), occ_points=float(np.mean(lengths)))
+    if observed:
+        out.update(iou_3D_observed=float(torch.cat(ious_obs).mean().item()), observed_fraction=float(torch.cat(fractions).mean().item()))
+    return out
 
 
 if __name__ == "__main__":

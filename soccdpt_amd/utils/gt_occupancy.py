@@ -47,13 +47,20 @@ class OccupancyProcessor:
         from .occupancy_views import processor_voxel_to_camera
         return processor_voxel_to_camera(self.grid_size, self.occupancy_shape, self.pc_scale, self.pc_shift, self._rot)
 
+    def observed_voxels(self, depth: torch.Tensor, **kw) -> torch.Tensor:
+        """utils.occupancy_rays.observed_voxels of `depth` [B,H,W] (process's output of that name) with this generator's voxel_to_camera() and
+        intrinsics: the voxel mask int32 [B, ceil(g0 g1 g2 / 32)] of the space the camera saw.  Keywords: z_near=, max_depth=, step=, out=."""
+        from .occupancy_rays import observed_voxels
+        return observed_voxels(depth, self.voxel_to_camera(), (self.fx, self.fy, self.cx, self.cy), self.grid_size, **kw)
+
     def process(self, disparity: torch.Tensor, seg_class: torch.Tensor, want_points: bool = True, want_depth: bool = True,
-                want_occupancy_points: bool = False) -> Dict[str, Optional[torch.Tensor]]:
+                want_occupancy_points: bool = False, want_observed: bool = False) -> Dict[str, Optional[torch.Tensor]]:
         """disparity [B,H,W] (or [H,W]) float, seg_class same shape integer class ids, both cuda ->
         depth [B,H,W] f32, points [B,H*W,3] f64, occupancy_grid [B,g0,g1,g2,C] bool, counts [B,g0,g1,g2,C] int32.
         want_occupancy_points adds `occupancy_points`: a list of B float64 [N_b,4] tensors (x, y, z, class_id), the value
         transform_points_to_occupancy_grid_vect returns under that key (cells with counts >= point_count_threshold, class-major; bdd_helper.py:339-355),
-        built on the GPU from `counts`.  process_frame's later un-rotate / un-shift / un-scale of that list (:500-528, drawing only) is not applied to it: voxel_to_camera() is that mapping."""
+        built on the GPU from `counts`.  want_observed adds `observed`: observed_voxels(depth), the voxel mask [B, ceil(g0 g1 g2 / 32)] int32 of the
+        space this frame's rays crossed (utils/occupancy_rays.py).  process_frame's later un-rotate / un-shift / un-scale of that list (:500-528, drawing only) is not applied to it: voxel_to_camera() is that mapping."""
         assert disparity.is_cuda, "the HIP path needs cuda tensors (no CPU fallback)"
         if disparity.dim() == 2:
             disparity, seg_class = disparity.unsqueeze(0), seg_class.unsqueeze(0)
@@ -63,7 +70,7 @@ class OccupancyProcessor:
         d = disparity.detach().to(torch.float32).contiguous()
         sc = seg_class.detach().to(torch.int32).contiguous()
         g = self.grid_size
-        depth = torch.empty((B, H, W), dtype=torch.float32, device=dev) if want_depth else None
+        depth = torch.empty((B, H, W), dtype=torch.float32, device=dev) if want_depth or want_observed else None
         pts = torch.empty((B, H * W, 3), dtype=torch.float64, device=dev) if want_points else None
         counts = torch.empty((B, g[0], g[1], g[2], self.num_classes), dtype=torch.int32, device=dev)
         occ = torch.empty((B, g[0], g[1], g[2], self.num_classes), dtype=torch.uint8, device=dev)
@@ -73,7 +80,9 @@ class OccupancyProcessor:
               arr([float(v) for v in self._rot], ctypes.c_double), arr([float(v) for v in self.occupancy_shape], ctypes.c_float),
               arr(list(g), ctypes.c_int), self.point_count_threshold, _ptr(d), _ptr(sc), _ptr(depth), _ptr(pts),
               _ptr(counts), _ptr(occ), device=dev)
-        out = dict(depth=depth, points=pts, occupancy_grid=occ.bool(), counts=counts)
+        out = dict(depth=depth if want_depth else None, points=pts, occupancy_grid=occ.bool(), counts=counts)
+        if want_observed:
+            out["observed"] = self.observed_voxels(depth)
         if want_occupancy_points:
             from .occupancy import occupancy_bits_to_points, pack_occupancy
             bits = pack_occupancy(counts, self.point_count_threshold, strict=False)           # the list uses >=, the grid above >
