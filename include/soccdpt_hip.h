@@ -46,8 +46,10 @@ extern "C" {
  *   11 (soccdpt_fwd_aux_args and soccdpt_op_fwd_aux are new -- a stateless test entry into the forward path's non-GEMM launchers; soccdpt_sizeof(7);
  *     nothing that existed changed);
  *   12 (soccdpt_op_attention_bwd, soccdpt_op_attention_bwd_slots, soccdpt_op_vit_attention_bwd, soccdpt_op_attn_param_grads and soccdpt_op_qv_bias_grad are
- *     new -- stateless test entries into the attention backward of the training step; nothing that existed changed). */
-#define SOCCDPT_ABI_VERSION 12
+ *     new -- stateless test entries into the attention backward of the training step; nothing that existed changed);
+ *   13 (soccdpt_op_gn_apply_halo is new -- soccdpt_op_gn_apply with the halo image's format as one more argument, a test entry; nothing that existed
+ *     changed). */
+#define SOCCDPT_ABI_VERSION 13
 
 /* backbone ids: model/loader.py:65-77 (model_type switch), model/blocks.py:59-78 */
 #define SOCCDPT_BACKBONE_SWIN2T16_256 0 /* dpt_swin2_tiny_256 */
@@ -548,6 +550,13 @@ int soccdpt_op_gn_apply(const float* dev_raw, float* dev_stats, const float* dev
                         const float* dev_raw2, float* dev_stats2, const float* dev_part2, int tps2, const float* dev_gamma2, const float* dev_beta2,
                         const float* dev_res, float* dev_out_f32, void* dev_out_op, void* dev_out_halo, int out_format, int relu, size_t M, int hw, int w,
                         int C, int cpg, float eps, void* stream);
+/* The same with the halo image in a format of its own: out_halo is written in halo_format (SOCCDPT_PREC_BF16 / _F16 / _F32 / _F16X3) while out_op keeps
+ * out_format -- the form a SOCCDPT_PREC_MIXED handle launches where a hooked stage output feeds the decoder's precision group (GnApplyArgs::halo_mode).
+ * Every other argument, and every refusal, as soccdpt_op_gn_apply. */
+int soccdpt_op_gn_apply_halo(const float* dev_raw, float* dev_stats, const float* dev_part, int tps, const float* dev_gamma, const float* dev_beta,
+                             const float* dev_raw2, float* dev_stats2, const float* dev_part2, int tps2, const float* dev_gamma2, const float* dev_beta2,
+                             const float* dev_res, float* dev_out_f32, void* dev_out_op, void* dev_out_halo, int out_format, int halo_format, int relu, size_t M,
+                             int hw, int w, int C, int cpg, float eps, void* stream);
 
 /* Global softmax attention of one ViT block (timm vision_transformer.Attention between the qkv and proj Linear layers; created by
  * model/backbones/vit.py:248): qkv [B*N][3*heads*64] -> out [B*N][heads*64] = softmax(q k^T / 8) v per (sample, head); elements

@@ -15,7 +15,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SOCCDPT_LIB_PATH") or os.path.join(_HERE, "libsoccdpt_hip.so")   # override: A/B of two builds in one GPU call (tools/ab_bench.sh)
 
-ABI_VERSION = 12
+ABI_VERSION = 13
 BACKBONE_IDS = {"swin2t16_256": 0, "swin2b24_384": 1, "vitb_rn50_384": 2, "swin2l24_384": 3, "swinl12_384": 5}   # 4 is reserved for vitl16_384
 PREC_BF16 = 0
 PREC_F32 = 1
@@ -253,6 +253,7 @@ def _prototypes() -> dict:
         "soccdpt_op_seg_tail": (ci, [vp, ci, vp, vp, vp, ci, ci, ci, ci, vp]),
         "soccdpt_op_gn_finish": (ci, [vp, vp, ci, ci, ci, ci, ci, cf, vp]),
         "soccdpt_op_gn_apply": (ci, [vp, vp, vp, ci, vp, vp, vp, vp, vp, ci, vp, vp, vp, vp, vp, vp, ci, ci, cs, ci, ci, ci, ci, cf, vp]),
+        "soccdpt_op_gn_apply_halo": (ci, [vp, vp, vp, ci, vp, vp, vp, vp, vp, ci, vp, vp, vp, vp, vp, vp, ci, ci, ci, cs, ci, ci, ci, ci, cf, vp]),
         "soccdpt_op_vit_attention": (ci, [vp, vp, ci, ci, ci, ci, vp]),
         "soccdpt_op_vit_attention_out": (ci, [vp, vp, ci, ci, ci, ci, ci, vp]),
         "soccdpt_op_wgrad_tn": (ci, [vp, ctypes.c_long, vp, ctypes.c_long, cs, ci, ci, ci, ci, ci, vp, cs, vp, vp]),
@@ -868,12 +869,17 @@ def op_gn_finish(part, stats, B, tps, groups, hw, cpg, eps=1e-5):
 
 
 def op_gn_apply(raw, stats, gamma, beta, hw, w, cpg, part=None, tps=0, raw2=None, stats2=None, part2=None, tps2=0, gamma2=None, beta2=None, res=None,
-                out_f32=None, out_op=None, out_halo=None, out_format=PREC_F32, relu=True, eps=1e-5):
-    """Kernel-level entry (tests): GroupNorm apply (+ shortcut) (+ ReLU) of raw [M][C] (soccdpt_op_gn_apply) on the current stream."""
+                out_f32=None, out_op=None, out_halo=None, out_format=PREC_F32, relu=True, eps=1e-5, halo_format=None):
+    """Kernel-level entry (tests): GroupNorm apply (+ shortcut) (+ ReLU) of raw [M][C] (soccdpt_op_gn_apply) on the current stream.  halo_format (a PREC_*
+    operand format): out_halo in a format of its own, out_op stays in out_format (soccdpt_op_gn_apply_halo, the SOCCDPT_PREC_MIXED form)."""
     M, C = raw.shape
-    _call("soccdpt_op_gn_apply", _ptr(raw), _ptr(stats), _ptr(part), int(tps), _ptr(gamma), _ptr(beta), _ptr(raw2), _ptr(stats2), _ptr(part2), int(tps2),
-          _ptr(gamma2), _ptr(beta2), _ptr(res), _ptr(out_f32), _ptr(out_op), _ptr(out_halo), int(out_format), 1 if relu else 0, M, int(hw),
-          int(w), int(C), int(cpg), float(eps), device=raw.device, guard=False)
+    head = (_ptr(raw), _ptr(stats), _ptr(part), int(tps), _ptr(gamma), _ptr(beta), _ptr(raw2), _ptr(stats2), _ptr(part2), int(tps2),
+            _ptr(gamma2), _ptr(beta2), _ptr(res), _ptr(out_f32), _ptr(out_op), _ptr(out_halo), int(out_format))
+    tail = (1 if relu else 0, M, int(hw), int(w), int(C), int(cpg), float(eps))
+    if halo_format is None:
+        _call("soccdpt_op_gn_apply", *head, *tail, device=raw.device, guard=False)
+    else:
+        _call("soccdpt_op_gn_apply_halo", *head, int(halo_format), *tail, device=raw.device, guard=False)
 
 
 def op_vit_attention(qkv, out, B, N, heads, precision=PREC_BF16, out_x3=False):

@@ -108,7 +108,11 @@ def check_interval16(got, ref, bound, fmt, what):
 
 def check_x3_interval(raw, shape, ref, bound, what):
     """An x3 output with no f32 twin: hi in the fp16 interval, and the decoded pair within bound + 2^-23 |ref| + 2^-36 of ref."""
-    hi, lo = FR.x3_parts(raw, shape)
+    return check_x3_interval_parts(*FR.x3_parts(raw, shape), ref, bound, what)
+
+
+def check_x3_interval_parts(hi, lo, ref, bound, what):
+    """The same on decoded (hi, lo) values -- for a part of an x3 tensor, such as the interior of a zero-halo image."""
     check_interval16(hi, ref, bound, "f16", what + " (x3 hi)")
     return FR.check_bound(hi + lo / 2048.0, ref, bound + 2.0 ** -23 * ref.abs() + 2.0 ** -36, what + " (x3 decode)")
 

@@ -198,7 +198,7 @@ def test_prototype_table_matches_the_header():
     integer or float of the same width.  A parameter added to the header without the binding following fails here; no built library is needed."""
     from soccdpt_amd.lib import PROTOTYPES
     header = _header_prototypes()
-    assert sorted(header) == _declared() and len(header) == 89, "the prototype regex and the symbol regex disagree about what the header declares"
+    assert sorted(header) == _declared() and len(header) == 90, "the prototype regex and the symbol regex disagree about what the header declares"
     assert sorted(PROTOTYPES) == sorted(header), (sorted(set(header) - set(PROTOTYPES)), sorted(set(PROTOTYPES) - set(header)))
     assert list(PROTOTYPES) == list(header), "the table follows the header's order"
     for name, (restype, argtypes) in PROTOTYPES.items():

@@ -336,7 +336,7 @@ def test_pack_symbols_exported_and_typed():
     for name, (restype, argtypes) in PACK_PROTOTYPES.items():
         f = getattr(L, name)
         assert f.restype is restype and list(f.argtypes) == argtypes, name
-    assert ABI_VERSION == 12 and L.soccdpt_abi_version() == 12      # a fourth header, not a new version of the first
+    assert ABI_VERSION == 13 and L.soccdpt_abi_version() == 13      # a fourth header, not a new version of the first
 
 
 def test_argument_errors_need_no_gpu():

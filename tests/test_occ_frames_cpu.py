@@ -38,17 +38,18 @@ def test_symbols_declared_exported_and_bound():
     assert "eager" in header[header.index("soccdpt_forward_frames:"):].split("*/")[0].lower()    # the header says the call is never graph-replayed
 
 
-def test_abi_version_is_12_in_all_three_places():
+def test_abi_version_is_13_in_all_three_places():
     header = open(os.path.join(REPO, "include", "soccdpt_hip.h")).read()
-    assert int(re.search(r"#define\s+SOCCDPT_ABI_VERSION\s+(\d+)", header).group(1)) == 12
+    assert int(re.search(r"#define\s+SOCCDPT_ABI_VERSION\s+(\d+)", header).group(1)) == 13
     assert re.search(r"^\s*\*\s+8 \(per-frame occupancy", header, flags=re.M), "the header's version history has no line for 8"
     assert re.search(r"^\s*\*\s+9 \(soccdpt_train_layer_bwd_args", header, flags=re.M), "the header's version history has no line for 9"
     assert re.search(r"^\s*\*\s+10 \(soccdpt_train_aux_args", header, flags=re.M), "the header's version history has no line for 10"
     assert re.search(r"^\s*\*\s+11 \(soccdpt_fwd_aux_args", header, flags=re.M), "the header's version history has no line for 11"
     assert re.search(r"^\s*\*\s+12 \(soccdpt_op_attention_bwd", header, flags=re.M), "the header's version history has no line for 12"
+    assert re.search(r"^\s*\*\s+13 \(soccdpt_op_gn_apply_halo", header, flags=re.M), "the header's version history has no line for 13"
     from soccdpt_amd import lib as binding
-    assert binding.ABI_VERSION == 12
-    assert binding.load_library().soccdpt_abi_version() == 12
+    assert binding.ABI_VERSION == 13
+    assert binding.load_library().soccdpt_abi_version() == 13
     # soccdpt_config did not grow
     assert binding.load_library().soccdpt_sizeof(0) == ctypes.sizeof(binding.SoccdptConfig) == 4 * (9 + 4 + 3 + 9 + 27)
 

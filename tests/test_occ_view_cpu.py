@@ -57,7 +57,7 @@ def test_occ_view_symbols_exported_and_typed():
     for name, (restype, argtypes) in OCC_VIEW_PROTOTYPES.items():
         f = getattr(L, name)
         assert f.restype is restype and list(f.argtypes) == argtypes, name
-    assert ABI_VERSION == 12 and L.soccdpt_abi_version() == 12      # a sixth header, not a new version of the first
+    assert ABI_VERSION == 13 and L.soccdpt_abi_version() == 13      # a sixth header, not a new version of the first
 
 
 def test_forward_source_hash_did_not_move_for_occ_view():

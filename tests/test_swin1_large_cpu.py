@@ -162,7 +162,7 @@ def test_swin1_symbols_exported_and_argument_errors_need_no_gpu():
     for name in _swin1_header():
         assert hasattr(raw, name), f"{name} declared in include/soccdpt_swin1.h but not exported"
     lib = load_library()
-    assert ABI_VERSION == 12 and lib.soccdpt_abi_version() == 12      # a fifth header, not a new version of the first
+    assert ABI_VERSION == 13 and lib.soccdpt_abi_version() == 13      # a fifth header, not a new version of the first
     p = 4096      # 16-byte aligned, never dereferenced: every call below fails its argument check
 
     def refused(rc, word):
